@@ -8,6 +8,13 @@ corpus, weak scaling); every step also all-gathers the per-shard top-100 over
 RCCL and merges them on the device (fan-out query over all namespaces).
 
 Prints ONE JSON line on rank 0.  See DESIGN.md §Measurement.
+
+A plain run sets up, warms up, times the --steps steps and prints the line
+(`value`, `ms_per_step`, the kernels' HIP-event times).  Everything else -- the
+batch-of-one latencies, the host traffic models of the roofline, the CPU
+baseline and parity, the secondary workloads (C3, OR, end-to-end, db API, C4,
+C5) -- runs only with --full.  --dump-outputs DIR writes the last timed step's
+hits as DIR/{scores,docs,counts}.npy (dump_outputs).
 """
 from __future__ import annotations
 
@@ -189,6 +196,25 @@ def throughput_fields(nq, world, steps, elapsed_s):
     return {"value": round(nq * steps / elapsed_s, 1),
             "namespace_queries_per_s": round(nq * world * steps / elapsed_s, 1),
             "queries_per_step": nq}
+
+
+def dump_outputs(path, s, d, n, K, shard=None):
+    """--dump-outputs: the hits of the last timed step as a caller receives them,
+    scores.npy (f32 [nq, K]), docs.npy and counts.npy (f64; doc ids are exact in
+    it) and, for merged lists, shards.npy.  Slots past a query's count hold no
+    hit (their device words are undefined), so they are written as score 0,
+    doc / shard -1: two builds that return the same hits dump the same files."""
+    n = np.asarray(n).astype(np.int64).reshape(-1)
+    nq = len(n)
+    hit = np.arange(K)[None, :] < n[:, None]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "scores.npy"), np.where(hit, np.asarray(s, np.float32).reshape(nq, K), np.float32(0)))
+    np.save(os.path.join(path, "docs.npy"),
+            np.where(hit, np.asarray(d).view(np.uint32).reshape(nq, K).astype(np.float64), -1.0))
+    np.save(os.path.join(path, "counts.npy"), n.astype(np.float64))
+    if shard is not None:
+        np.save(os.path.join(path, "shards.npy"),
+                np.where(hit, np.asarray(shard).reshape(nq, K).astype(np.float64), -1.0))
 
 
 def timed_steps(step, steps, warmup, torch):
@@ -939,6 +965,8 @@ def run_config(args, cfg, rank, world, local, dev, backend, threads, torch, dist
     mn = mn.cpu().numpy()
     ms = ms.cpu().numpy().reshape(nq, K)
     md = md.cpu().numpy().view(np.uint32).reshape(nq, K)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, ms, md, mn, K)
     h = hashlib.sha1()
     for i in range(nq):
         h.update(md[i, :mn[i]].tobytes())
@@ -1057,7 +1085,15 @@ def main():
                     help="skip the host traffic models (profiling passes: only kernel times and counters matter)")
     ap.add_argument("--config", choices=["headline", "c4", "c5"], default="headline",
                     help="c4 / c5: BASELINE configs[3] / [4] split over the job's GPUs (strong scaling)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline's timed steps: batch-of-one latencies, the host "
+                         "traffic models (roofline), the CPU baseline and parity, the secondary workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's hits to DIR/{scores,docs,counts}.npy (dump_outputs)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps and the result line only
+        args.no_cpu = args.no_extra = args.no_model = True
+        args.p50_queries = 0
     global NO_MODEL
     NO_MODEL = args.no_model
 
@@ -1195,6 +1231,10 @@ def main():
             m = int(mn_[i])
             h.update(ms_[i * K:i * K + m].tobytes() + md_[i * K:i * K + m].tobytes() + msh_[i * K:i * K + m].tobytes())
         result_sha1 = h.hexdigest()[:16]
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, ms_, md_, mn_, K, msh_)
+    elif rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out_s.cpu().numpy(), out_d.cpu().numpy(), out_n.cpu().numpy(), K)
     qps = tput["value"]
 
     # ---- p50 latency at batch = 1 (host query in, host hits out: plan + PCIe + kernels)

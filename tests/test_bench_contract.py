@@ -40,6 +40,43 @@ def test_headline_value_comes_from_throughput_fields():
     assert "nq * world * args.steps" not in body
 
 
+def test_dump_outputs_writes_the_hits_and_masks_the_rest(tmp_path):
+    """--dump-outputs: scores f32, docs / counts f64, [nq, K]; slots past a
+    query's count (undefined device words) come out as score 0, doc -1, so the
+    files depend on the hits alone."""
+    import numpy as np
+    b = _bench()
+    K = 4
+    n = np.array([4, 2, 0], np.int32)
+    s = np.arange(12, dtype=np.float32) + 0.5
+    d = np.array([7, 6, 5, 4, 0xFFFFFFF0, 2, 99, 98, 97, 96, 95, 94], np.uint32).view(np.int32)  # as torch int32
+    for junk in (0, 12345):  # different leftovers past the counts: identical files
+        s2, d2 = s.copy(), d.copy()
+        s2[6:] += junk
+        d2[6:] += junk
+        out = tmp_path / f"dump{junk}"
+        b.dump_outputs(str(out), s2, d2, n, K)
+        sc, dc, nc = (np.load(out / f"{x}.npy") for x in ("scores", "docs", "counts"))
+        assert sc.dtype == np.float32 and dc.dtype == np.float64 and nc.dtype == np.float64
+        assert sc.shape == dc.shape == (3, K) and nc.tolist() == [4.0, 2.0, 0.0]
+        assert sc.tolist() == [[0.5, 1.5, 2.5, 3.5], [4.5, 5.5, 0, 0], [0, 0, 0, 0]]
+        assert dc.tolist() == [[7, 6, 5, 4], [float(0xFFFFFFF0), 2, -1, -1], [-1, -1, -1, -1]]
+
+
+def test_plain_run_skips_what_full_runs():
+    """Without --full the run is the timed steps and the result line: the CPU
+    baseline, the secondary workloads, the traffic models and the batch-of-one
+    latencies are switched off before anything is set up."""
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    main = next(n for n in ast.parse(src).body if isinstance(n, ast.FunctionDef) and n.name == "main")
+    body = ast.unparse(main)
+    assert "'--full'" in body and "'--dump-outputs'" in body
+    gate = body.index("if not args.full:")
+    assert gate < body.index("import torch")
+    head = body[gate:body.index("import torch")]
+    assert "args.no_cpu = args.no_extra = args.no_model = True" in head and "args.p50_queries = 0" in head
+
+
 def test_roofline_carries_three_fractions():
     """Every kernel line's roofline quotes the model's fraction, the fraction at
     each query's final threshold (frac_pruned) and the measured DRAM fraction; a

@@ -14,7 +14,7 @@ TAG=${1:-r02}
 shift || true
 # --p50-queries 0: only the batch dispatches, so the trace's average kernel
 # duration is the batch kernel the bench's roofline line is computed on
-ARGS="--steps 5 --warmup 1 --no-cpu --p50-queries 0 --no-extra $*"
+ARGS="--full --steps 5 --warmup 1 --no-cpu --p50-queries 0 --no-extra $*"  # --full: the line's traffic models
 OUT=$R/gpurun_out/prof_$TAG
 DRAM="TCC_EA0_RDREQ_DRAM_32B TCC_EA0_WRREQ_WRITE_DRAM_32B"
 mkdir -p "$OUT"

@@ -40,7 +40,7 @@ def main():
         "source": f"{rel}/pmc.json",
         "command": f"bash tools/profile_bench.sh {tag}{extra}  (= rocprofv3 --kernel-trace --stats, then separate --pmc "
                    "passes (FETCH_SIZE / WRITE_SIZE / TCC_EA0_RDREQ_DRAM_32B + TCC_EA0_WRREQ_WRITE_DRAM_32B) of python3 "
-                   f"bench.py --steps 5 --warmup 1 --no-cpu --p50-queries 0 --no-extra{extra})",
+                   f"bench.py --full --steps 5 --warmup 1 --no-cpu --p50-queries 0 --no-extra{extra})",
         "workload": {"n_docs": cfg["n_docs"], "batch": cfg["batch"], "k": cfg["k"], "terms": cfg["terms"]},
         "lib_id": pmc.get("lib_id"),
         f"{kname}_hbm_bytes_per_launch": pmc.get(f"{kname}_hbm_bytes_per_launch"),
