@@ -1,5 +1,6 @@
-// Host-side internals of libfugu shared by fugu.cpp (snapshot build, plans,
-// execution, the C ABI) and model.cpp (the byte / line models of the roofline):
+// Host-side internals of libfugu shared by fugu.cpp (snapshot build, execution,
+// the C ABI), plan.cpp (batch planning) and model.cpp (the byte / line models of
+// the roofline):
 // the opaque handles of include/fugu.h and their memory pools.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -509,4 +510,19 @@ void term_ratio(const fg_index* ix, uint32_t t, float* rdn, float* rup);
 float term_max_now(const fg_index* ix, uint32_t t);
 float term_max_scaled(const fg_index* ix, uint32_t t, float rup);  // tmaxs[t] x rup, rounded up
 float term_kth_now(const fg_index* ix, uint32_t t, uint32_t k, bool with_floor);
+
+// ---- planning (plan.cpp)
+// One bin geometry of a query's score histogram (DevPlan::hist) over the union
+// of spans whose largest lo and largest hi (f32 bit patterns) are given: bin 0
+// at lo, the top bin at max(hi, lo), bins of 2^shift f32 ulps
+struct Bins { uint32_t lo, hi, shift; };
+Bins union_bins(uint32_t lo, uint32_t hi);
+// fg_plan_create_multi with the upload on stream `up`.  sync = false
+// (fg_search_batch, fg_search_sharded): the upload stays in flight on `up`,
+// where the plan's execute is queued behind it; the pinned staging is returned
+// when the plan is destroyed
+int plan_create_multi(fg_index* const* ixs, uint32_t n_segs, const fg_query_batch* q, uint32_t k, fg_plan** out,
+                      bool sync, hipStream_t up);
+// f(0 .. n-1) on fugu.cpp's persistent worker threads (ShardWorkers); returns when all have run
+void run_parallel(uint32_t n, const std::function<void(uint32_t)>& f);
 }  // namespace fgh

@@ -1,5 +1,5 @@
-// libfugu host side: index snapshot build + HBM upload, batch planning,
-// execution and the C ABI of include/fugu.h.
+// libfugu host side: index snapshot build + HBM upload, plan execution and
+// the C ABI of include/fugu.h (batch planning: plan.cpp).
 //
 // The BM25 statistics follow tantivy 0.24.1 as fugu uses it (SURVEY.md
 // Appendix A): N = max_doc (deleted docs included), avgdl = total tokens / N,
@@ -55,6 +55,7 @@ using fgh::fail;
 using fgh::hw_threads;
 using fgh::parallel_dynamic;
 using fgh::parallel_ranges;
+using fgh::plan_create_multi;  // plan.cpp
 
 // ---------------------------------------------------------------- tantivy constants
 constexpr float kK1 = 1.2f;
@@ -103,14 +104,6 @@ float term_score_host(uint32_t tfp, uint32_t fn_t, uint32_t fn_n, float wt, floa
     s += wn * (tf / (tf + cache[256 + fn_n]));
   }
   return s;
-}
-
-// Bin width (2^shift f32 ulps) of a query score histogram spanning the f32
-// bit patterns [lo, hi] in fewer than kQBins bins (DevPlan::hist).
-uint32_t bin_shift(uint32_t lo, uint32_t hi) {
-  uint32_t sh = 0;
-  while (sh < 31 && ((uint64_t)(hi - lo) >> sh) >= fg::kQBins - 1) ++sh;
-  return sh;
 }
 
 // FUGU_BUILD_TRACE=1: per-phase wall time of a snapshot build on stderr
@@ -2313,857 +2306,6 @@ int fg_index_bm25(const fg_index* ix, uint32_t term, float* w_text, float* w_nam
   return FG_OK;
 }
 
-// ---------------------------------------------------------------- planning
-static int plan_create(fg_index* ix, const fg_query_batch* q, uint32_t k, fg_plan** out, bool sync,
-                       hipStream_t up = hipStreamPerThread);
-static int plan_create_multi(fg_index* const* ixs, uint32_t n_segs, const fg_query_batch* q, uint32_t k,
-                             fg_plan** out, bool sync, hipStream_t up);
-
-int fg_plan_create(fg_index* ix, const fg_query_batch* q, uint32_t k, fg_plan** out) {
-  return plan_create(ix, q, k, out, true);
-}
-
-int fg_plan_create_multi(fg_index* const* ixs, uint32_t n_segs, const fg_query_batch* q, uint32_t k, fg_plan** out) {
-  return plan_create_multi(ixs, n_segs, q, k, out, true, hipStreamPerThread);
-}
-
-// sync = false (fg_search_batch): the upload stays in flight on the calling
-// thread's per-thread stream, where the plan's execute is queued behind it;
-// the pinned staging is returned when the plan is destroyed
-static int plan_create(fg_index* ix, const fg_query_batch* q, uint32_t k, fg_plan** out, bool sync,
-                       hipStream_t up) {
-  return plan_create_multi(&ix, 1, q, k, out, sync, up);
-}
-
-namespace {
-
-struct WItem { double key; uint32_t q, c, n; };
-
-// One snapshot's side of a planned batch, built on the host alone (no HIP
-// call): per-query tables, facet filters (ids local to the snapshot) and the
-// unsorted work items.  plan_create_multi joins one per snapshot.
-struct HostPlan {
-  std::vector<uint32_t> q_m, q_terms, lead, nchunk, q_filter;
-  std::vector<uint64_t> thr0;
-  std::vector<float> q_ub, q_wt, q_wn, q_rup;
-  uint32_t nf = 0;
-  std::vector<uint32_t> f_shift;
-  std::vector<uint64_t> f_woff;
-  std::vector<float> f_tab, f_max;
-  std::vector<uint32_t> ch_f, ch_c, ch_t, ch_s;
-  std::vector<WItem> citems, ditems, scan;
-  std::vector<uint32_t> ngroup, q_hlo, q_hhi, q_hsh;
-  // (a thread's plans reuse one set: assign / push_back into kept capacity, no
-  // page faults on fresh arrays -- ~0.2 ms of an 8-snapshot batch's planning)
-  void clear_lists() {
-    ch_f.clear(); ch_c.clear(); ch_t.clear(); ch_s.clear();
-    citems.clear(); ditems.clear(); scan.clear();
-  }
-};
-
-// n_segs: the snapshots the plan spans; a query's work items are spread over
-// all of them, so each snapshot gets its share of the per-query item counts.
-// nq_size: the batch size the item counts are sized for (q may be a slice of
-// that batch: plan_create_multi plans a snapshot's queries in pieces)
-int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t n_segs, HostPlan& h,
-              uint32_t nq_size) {
-  if (!ix || !q || (q->n_queries && !q->q_off)) return fail(FG_EINVAL, "bad arguments");
-  if (q->n_queries && q->q_off[q->n_queries] > q->q_off[0] && !q->terms) return fail(FG_EINVAL, "q_off without terms");
-  if (q->f_off && q->n_queries && q->f_off[q->n_queries] > q->f_off[0] && !q->f_terms)
-    return fail(FG_EINVAL, "f_off without f_terms");
-  if (k < 1) return fail(FG_EINVAL, "k must be >= 1 (TopDocs::with_limit asserts limit >= 1)");
-  if (k > FG_MAX_K) return fail(FG_EUNSUPPORTED, "k=%u > FG_MAX_K=%d", k, FG_MAX_K);
-  if (q->mode != FG_MODE_AND && q->mode != FG_MODE_OR) return fail(FG_EINVAL, "bad mode %d", q->mode);
-  const uint32_t nq = q->n_queries;
-  const uint64_t N = ix->n_docs;
-  const bool disj = q->mode == FG_MODE_OR;
-  h.clear_lists();
-  auto &q_m = h.q_m, &q_terms = h.q_terms, &lead = h.lead, &nchunk = h.nchunk;
-  auto& thr0 = h.thr0;
-  auto& q_ub = h.q_ub;
-  q_m.assign(nq, 0);
-  q_terms.assign((size_t)nq * fg::kMaxTerms, 0);
-  lead.assign(nq, 0);
-  nchunk.assign(nq, 0);
-  thr0.assign(nq, 0);
-  q_ub.assign((size_t)nq * fg::kMaxTerms, 0.0f);
-  h.q_wt.assign((size_t)nq * fg::kMaxTerms, 0.0f);
-  h.q_wn.assign((size_t)nq * fg::kMaxTerms, 0.0f);
-  h.q_rup.assign((size_t)nq * fg::kMaxTerms, 1.0f);
-
-  // ---- facet filters: one mask per distinct clause list (fg_internal.h DevFilters)
-  auto& q_filter = h.q_filter;
-  q_filter.assign(nq, 0xFFFFFFFFu);
-  std::vector<std::vector<uint32_t>> flist;
-  std::vector<uint8_t> q_nomatch(nq, 0);  // the filter matches no doc: no work items
-  if (q->f_off) {
-    std::map<std::vector<uint32_t>, uint32_t> fid;
-    for (uint32_t i = 0; i < nq; ++i) {
-      const uint32_t b = q->f_off[i], e = q->f_off[i + 1];
-      if (e < b) return fail(FG_EINVAL, "f_off not monotone at query %u", i);
-      if (e == b) continue;
-      if (e - b > fg::kMaxFacetClauses)
-        return fail(FG_EUNSUPPORTED, "query %u has %u facet clauses (> %u)", i, e - b, fg::kMaxFacetClauses);
-      std::vector<uint32_t> c(q->f_terms + b, q->f_terms + e);
-      bool any = false;
-      for (uint32_t t : c) any |= t < ix->n_fterms && ix->df_facet[t] > 0;
-      if (!any) { q_nomatch[i] = 1; continue; }
-      auto it = fid.find(c);
-      if (it == fid.end()) {
-        it = fid.emplace(c, (uint32_t)flist.size()).first;
-        flist.push_back(std::move(c));
-      }
-      q_filter[i] = it->second;
-    }
-  }
-  const uint32_t nf = h.nf = (uint32_t)flist.size();
-  auto& f_shift = h.f_shift;
-  auto& f_woff = h.f_woff;
-  auto& f_tab = h.f_tab;
-  auto& f_max = h.f_max;
-  auto &ch_f = h.ch_f, &ch_c = h.ch_c, &ch_t = h.ch_t, &ch_s = h.ch_s;
-  f_shift.assign(nf, 0);
-  f_woff.assign(nf + 1, 0);
-  f_tab.assign((size_t)nf * 256, 0.0f);
-  f_max.assign(nf, 0.0f);
-  std::vector<uint32_t> f_lo(nf, 0xFFFFFFFFu), f_hi(nf, 0);  // doc span of the filter's postings
-  for (uint32_t f = 0; f < nf; ++f) {
-    const std::vector<uint32_t>& c = flist[f];
-    const uint32_t n = (uint32_t)c.size();
-    const uint32_t sh = n <= 1 ? 0 : n <= 2 ? 1 : n <= 4 ? 2 : 3;
-    if ((N << sh) > (1ull << 32)) return fail(FG_EUNSUPPORTED, "facet mask of %u clauses too large for %llu docs", n,
-                                              (unsigned long long)N);
-    f_shift[f] = sh;
-    f_woff[f + 1] = f_woff[f] + ((((N << sh) + 31) / 32 + 63) & ~63ull);  // 256-B aligned masks
-    // union score of each set of matching clauses: 0.0 + s_i in clause order (SumCombiner)
-    for (uint32_t v = 0; v < (1u << n); ++v) {
-      float sc = 0.0f;
-      for (uint32_t i = 0; i < n; ++i)
-        if ((v >> i) & 1u) sc += c[i] < ix->n_fterms ? ix->fscore[c[i]] : 0.0f;
-      f_tab[(size_t)f * 256 + v] = sc;
-      f_max[f] = std::max(f_max[f], sc);
-    }
-    for (uint32_t i = 0; i < n; ++i) {
-      const uint32_t t = c[i];
-      if (t >= ix->n_fterms || ix->df_facet[t] == 0) continue;
-      f_lo[f] = std::min(f_lo[f], ix->ffirst[t]);
-      f_hi[f] = std::max(f_hi[f], ix->flast[t]);
-      const uint64_t df = ix->foff[t + 1] - ix->foff[t];
-      for (uint64_t st = 0; st < df; st += fg::kFmaskChunk) {
-        ch_f.push_back(f);
-        ch_c.push_back(i);
-        ch_t.push_back(t);
-        ch_s.push_back((uint32_t)st);
-      }
-    }
-  }
-
-  // work items: each query's chunks (Must-driven: k_conj) or doc tiles (Should
-  // only: k_disj) in ~kGroupsPerQuery groups, ordered as a doc sweep across the
-  // batch (a group centred at doc fraction x runs with the other queries'
-  // groups near x), ties by query.  Queries without text terms (facet-only /
-  // AllQuery) scan doc tiles (k_scan).  Per-term occurs (q->occur) make a
-  // query Must-driven when it has a Must clause (RequiredOptionalScorer over
-  // its Shoulds), a union of its Shoulds otherwise; MustNot clauses exclude.
-  using W = WItem;
-  // k_disj / k_scan groups per query, spread over the plan's snapshots; a small
-  // batch (the batch-of-one latency: the GPU holds nothing else) splits each
-  // query over up to 16x more, shorter items that run side by side
-  const uint32_t gpq_batch =
-      fg::kGroupsPerQuery * std::min<uint32_t>(fg::kDisjSmallSpread, std::max<uint32_t>(1, 256 / std::max(nq_size, 1u)));
-  const uint32_t gpq = std::max<uint32_t>(1, gpq_batch / n_segs);
-  // k_conj items per query per snapshot of a multi-snapshot plan: the single-
-  // snapshot count / n_segs, so a query keeps ~the single-snapshot item count
-  // over all its slots (C4, 8 x 1.25M namespaces: k_conj 1.300 -> 1.085 ms, /16
-  // 1.065 ms, identical hits: profiles/r05/ab/c4_ab_r05q.json; round 4 measured
-  // the opposite before the sparse rank words and the XCD split);
-  const uint32_t conj_gpq = fg::kConjGroupsPerQuery, conj_maxg = fg::kMaxGroup;
-  const uint32_t cdiv = n_segs <= 1 ? 1u : n_segs;
-  auto &citems = h.citems, &ditems = h.ditems, &scan = h.scan;
-  auto &ngroup = h.ngroup, &q_hlo = h.q_hlo, &q_hhi = h.q_hhi, &q_hsh = h.q_hsh;
-  ngroup.assign(nq, 0);
-  q_hlo.assign(nq, 0x3F800000u);
-  q_hhi.assign(nq, 0x3F800000u);
-  q_hsh.assign(nq, 31);
-  auto present = [&](uint32_t t) { return t < ix->n_terms && ix->off[t + 1] > ix->off[t]; };
-  // a clause's query-time weights and bound factor (DevPlan::q_wt / q_wn / q_rup),
-  // and its largest current score into cm[j] (the ratio computed once per clause)
-  float cm[fg::kMaxTerms];
-  auto set_clause = [&](uint32_t i, uint32_t j, uint32_t t) {
-    const size_t x = (size_t)i * fg::kMaxTerms + j;
-    h.q_wt[x] = ix->w_text[t];
-    h.q_wn[x] = ix->w_name[t];
-    float rdn, rup;
-    fgh::term_ratio(ix, t, &rdn, &rup);
-    h.q_rup[x] = rup;
-    cm[j] = fgh::term_max_scaled(ix, t, rup);
-  };
-  // histogram bins of query i: bin 0 at the starting threshold (or ub / 256), the
-  // top bin at the query's largest possible score ub; ~kQBins bins between
-  auto set_bins = [&](uint32_t i, float ub) {
-    const float lo = thr0[i] ? fg::key_score(thr0[i]) : ub / 256.0f;
-    uint32_t lb, hb;
-    std::memcpy(&lb, &lo, 4);
-    std::memcpy(&hb, &ub, 4);
-    lb = std::max<uint32_t>(lb, 1);
-    hb = std::max(hb, lb);
-    q_hlo[i] = lb;
-    q_hhi[i] = hb;
-    q_hsh[i] = bin_shift(lb, hb);
-  };
-  for (uint32_t i = 0; i < nq; ++i) {
-    const uint32_t b = q->q_off[i], e = q->q_off[i + 1];
-    if (e < b) return fail(FG_EINVAL, "q_off not monotone at query %u", i);
-    const uint32_t m = e - b;
-    if (m > fg::kMaxTerms) return fail(FG_EUNSUPPORTED, "query %u has %u terms (> %u)", i, m, fg::kMaxTerms);
-    if (q_nomatch[i]) continue;  // the facet clauses match nothing: no hits
-    const float fmx = q_filter[i] == 0xFFFFFFFFu ? 0.0f : f_max[q_filter[i]];
-    if (m == 0) {
-      // empty text query: the facet union alone, or AllQuery (src/db/search.rs:115-116, 131-137)
-      q_m[i] = 0;
-      const uint32_t f = q_filter[i];
-      const uint64_t dlo = f == 0xFFFFFFFFu ? 0 : f_lo[f], dhi = f == 0xFFFFFFFFu ? N - 1 : f_hi[f];
-      const uint32_t tlo = (uint32_t)(dlo >> fg::kDisjTileShift), thi = (uint32_t)(dhi >> fg::kDisjTileShift);
-      const uint32_t nt = thi - tlo + 1;
-      const uint32_t G = std::min<uint32_t>(fg::kScanMaxGroup,
-                                            std::max<uint32_t>(1, (nt + gpq - 1) / gpq));
-      const uint32_t ng = (nt + G - 1) / G;
-      ngroup[i] = ng;
-      // the groups of all queries in doc order: the first groups publish the
-      // thresholds that let the later ones stop early
-      for (uint32_t g = 0; g < ng; ++g) scan.push_back(W{(double)g, i, tlo + g * G, std::min(G, nt - g * G)});
-      continue;
-    }
-    // the query's clauses by occur; a Should or MustNot clause on a term the
-    // snapshot lacks matches nothing and is dropped; a missing Must empties it
-    uint32_t tm[fg::kMaxTerms], ts_[fg::kMaxTerms], tx[fg::kMaxTerms];
-    uint32_t nm = 0, ns = 0, nx = 0;
-    bool must_missing = false;
-    for (uint32_t j = 0; j < m; ++j) {
-      const uint32_t t = fgh::local_term(ix, q->terms[b + j]);  // (the snapshot's own ids from here on)
-      const uint8_t oc = q->occur ? q->occur[b + j] : (disj ? FG_OCCUR_SHOULD : FG_OCCUR_MUST);
-      if (oc > FG_OCCUR_MUST_NOT) return fail(FG_EINVAL, "query %u: bad occur %u", i, (unsigned)oc);
-      if (oc == FG_OCCUR_MUST) {
-        tm[nm++] = t;
-        must_missing |= !present(t);
-      } else if (present(t)) {
-        (oc == FG_OCCUR_SHOULD ? ts_[ns++] : tx[nx++]) = t;
-      }
-    }
-    // one positive clause: the union of one Should IS that clause, so it runs
-    // Must-driven (k_conj's single-list and exclusion paths); same docs, same score
-    if (nm == 0 && ns == 1) {
-      tm[nm++] = ts_[0];
-      ns = 0;
-    }
-    uint32_t* qt = q_terms.data() + (size_t)i * fg::kMaxTerms;
-    if (nm == 0) {
-      if (ns == 0) continue;  // no positive clause: EmptyScorer, no hits
-      // Should clauses in clause order (SumCombiner order), then the MustNots
-      uint32_t dlo = 0xFFFFFFFFu, dhi = 0;
-      for (uint32_t j = 0; j < ns; ++j) {
-        qt[j] = ts_[j];
-        dlo = std::min(dlo, ix->first_doc[ts_[j]]);
-        dhi = std::max(dhi, ix->last_doc[ts_[j]]);
-      }
-      for (uint32_t j = 0; j < nx; ++j) qt[ns + j] = tx[j];
-      for (uint32_t j = 0; j < ns + nx; ++j) set_clause(i, j, qt[j]);
-      q_m[i] = fg::qm_pack(ns + nx, 0, nx);
-      if (q_filter[i] != 0xFFFFFFFFu) {
-        dlo = std::max(dlo, f_lo[q_filter[i]]);
-        dhi = std::min(dhi, f_hi[q_filter[i]]);
-        if (dlo > dhi) continue;  // the text and facet doc spans do not meet
-      }
-      // starting threshold: the best per-clause K'-th score for the smallest stored
-      // K' >= k (unfiltered and unexcluded only: a filter or an exclusion may
-      // remove a term's best docs)
-      if (q_filter[i] == 0xFFFFFFFFu && nx == 0) {
-        float v = 0.0f;
-        for (uint32_t c = 0; c < ns; ++c) v = std::max(v, fgh::term_kth_now(ix, qt[c], k, true));
-        if (v > 0.0f) thr0[i] = fg::make_key(v, 0xFFFFFFFFu);  // lowest key with score v
-      }
-      float ub = fmx;
-      for (uint32_t c = 0; c < ns; ++c) ub += cm[c];
-      set_bins(i, ub);
-
-      const uint32_t tlo = dlo >> fg::kDisjTileShift, thi = dhi >> fg::kDisjTileShift;
-      const uint32_t nt = thi - tlo + 1;
-      // tiles per item: ~gpq items per query (capping an item's postings, or the
-      // items of heavy queries first, measured slower: ab_disj_itemcap_k*.log,
-      // ab_disj_heavy_k*.log)
-      const uint32_t G = std::min<uint32_t>(std::min(fg::kDisjMaxGroup, fg::kDisjMaxPairs / ns),
-                                            std::max<uint32_t>(1, (nt + gpq - 1) / gpq));
-      // (shorter first items -- G >> r, G >> (r-1), ... tiles -- so the items that
-      // start with no threshold publish one early: r = 2 / 3 / 5 / 8 slower at
-      // k = 1000 and 20, +0.4% to +7%: profiles/r05/ab/disj_ramp_r05t.log)
-      // (shorter items at the end of each query's range -- half-size in its last
-      // 1/8, 1/4, 1/2 -- measured +8.6 / +18 / +34% at top-20, +9 / +18 / +33% at
-      // top-1000; 64-tile items -0.5% / +1.8%: profiles/r06/ab/)
-      const uint32_t ng = (nt + G - 1) / G;
-      for (uint32_t g = 0; g < ng; ++g) {
-        const uint32_t t0 = tlo + g * G, n = std::min(G, nt - g * G);
-        const double mid = ((double)t0 + 0.5 * n) * (double)(1u << fg::kDisjTileShift) / (double)ix->n_docs;
-        ditems.push_back(W{mid, i, t0, n});
-      }
-      ngroup[i] = ng;
-      if (ditems.size() > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "batch too large (%zu work items)", ditems.size());
-      continue;
-    }
-    if (must_missing) continue;  // a Must clause matches nothing: no hits
-    // tantivy intersect_scorers: the Must children sorted by cost (union cost =
-    // df_text + df_name), stable; then the MustNots, then the Shoulds in clause order
-    struct T { uint64_t cost; uint32_t pos, term; };
-    T tc[fg::kMaxTerms];
-    for (uint32_t j = 0; j < nm; ++j) tc[j] = T{(uint64_t)ix->df_text[tm[j]] + ix->df_name[tm[j]], j, tm[j]};
-    std::stable_sort(tc, tc + nm, [](const T& x, const T& y) { return x.cost < y.cost; });
-    for (uint32_t j = 0; j < nm; ++j) qt[j] = tc[j].term;
-    for (uint32_t j = 0; j < nx; ++j) qt[nm + j] = tx[j];
-    for (uint32_t j = 0; j < ns; ++j) qt[nm + nx + j] = ts_[j];
-    const uint32_t mt = nm + nx + ns;
-    for (uint32_t j = 0; j < mt; ++j) set_clause(i, j, qt[j]);
-    q_m[i] = fg::qm_pack(mt, nm, nx);
-    // MaxScore suffix bounds of the probed lists (k_conj prunes a candidate once its
-    // partial score plus these cannot reach the query's threshold): the Must and
-    // Should maxima from position j on (MustNots add nothing)
-    {
-      float acc = 0.0f;
-      for (uint32_t j = mt; j-- > 1;) {
-        if (j < nm || j >= nm + nx) acc += cm[j];
-        q_ub[(size_t)i * fg::kMaxTerms + j] = acc;
-      }
-    }
-    // one list: its K'-th best alive score (the smallest stored K' >= k) bounds
-    // the query's k-th best from below, so k_conj starts from that threshold and
-    // skips the lead chunks whose block-max cannot reach it (the block-max
-    // pruning tantivy's TopDocs runs on a single TermScorer: block_wand_single_scorer)
-    if (mt == 1 && q_filter[i] == 0xFFFFFFFFu) {
-      const float v = fgh::term_kth_now(ix, qt[0], k, true);
-      if (v > 0.0f) thr0[i] = fg::make_key(v, 0xFFFFFFFFu);  // lowest key with score v
-    }
-    {
-      float ub = fmx + cm[0];
-      for (uint32_t j = 1; j < mt; ++j)
-        if (j < nm || j >= nm + nx) ub += cm[j];
-      set_bins(i, ub);
-    }
-    const uint64_t df0 = ix->off[qt[0] + 1] - ix->off[qt[0]];
-    lead[i] = (uint32_t)df0;
-    nchunk[i] = (uint32_t)((df0 + fg::kChunk - 1) / fg::kChunk);
-    if (citems.size() + nchunk[i] > 0x7FFFFFFFull)
-      return fail(FG_EUNSUPPORTED, "batch too large (%zu work items)", citems.size());
-    const uint32_t nch = nchunk[i];
-    // items per query: ~kConjGroupsPerQuery in a full batch; a small batch (a
-    // batch of one: the p50 latency) spreads a query over up to 64 items so its
-    // chunks run side by side instead of up to kMaxGroup in a row, while its
-    // k_final still reads at most 64 x k candidates
-    // (a multi-snapshot plan: divided by cdiv, above)
-    const uint32_t per_q =
-        std::max<uint32_t>(1, std::min<uint32_t>(64, std::max<uint32_t>(conj_gpq, 1024 / std::max(nq_size, 1u))) / cdiv);
-    const uint32_t G = std::min<uint32_t>(conj_maxg, std::max<uint32_t>(1, (nch + per_q - 1) / per_q));
-    const uint32_t ng = (nch + G - 1) / G;
-    ngroup[i] = ng;
-    for (uint32_t g = 0; g < ng; ++g)
-      citems.push_back(W{(g + 0.5) / ng, i, g * G, std::min(G, nch - g * G)});
-  }
-  return FG_OK;
-}
-
-}  // namespace
-
-// Plans of one batch on one or several snapshots of one device (a multi-
-// snapshot plan: DevPlan::segs, query slot v = s * nq + q): every snapshot is
-// planned on the host (in parallel for a large batch), then the slots are
-// joined into ONE set of work items, uploaded once and run by one launch per
-// kernel.  Several snapshots share each batch query's threshold and histogram
-// (score-only), and their bins span the union of the snapshots' score ranges.
-static void run_parallel(uint32_t n, const std::function<void(uint32_t)>& f);  // ShardWorkers, below
-
-static int plan_create_multi(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint32_t k,
-                             fg_plan** out, bool sync, hipStream_t up) {
-  if (!ixs || !q || !out || S == 0 || S > FG_MAX_SEGMENTS) return fail(FG_EINVAL, "bad arguments");
-  for (uint32_t s = 0; s < S; ++s) {
-    if (!ixs[s]) return fail(FG_EINVAL, "NULL snapshot");
-    if (ixs[s]->dev != ixs[0]->dev) return fail(FG_EINVAL, "the snapshots of one plan live on different devices");
-  }
-  fg_index* ix = ixs[0];
-  // FUGU_SHARD_TRACE: the planning phases of a multi-snapshot batch on stderr
-  static const bool ptrace = getenv("FUGU_SHARD_TRACE") != nullptr;
-  auto pnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double pt[5] = {ptrace ? pnow() : 0.0, 0, 0, 0, 0};
-  // (reused: HostPlan::clear_lists; a plain reference, so the planning workers'
-  // lambdas see THIS thread's copy, not their own thread_local one)
-  static thread_local std::vector<HostPlan> hs_tl;
-  std::vector<HostPlan>& hs = hs_tl;
-  const uint32_t nq1 = q->n_queries;  // batch queries
-  if ((uint64_t)S * nq1 > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "batch too large (%u x %u query slots)", S, nq1);
-  const uint32_t nq = S * nq1;  // query slots
-  // pieces: each snapshot's queries planned in P slices of >= 128 queries so
-  // the host's threads all plan (8 snapshots on 16 threads: 2 pieces each);
-  // piece p = s * P + r holds snapshot s's queries [pa(r), pa(r + 1)), and the
-  // pieces joined in order give the same tables and item lists as one plan per
-  // snapshot (plan_host sizes items by the whole batch)
-  const bool par = S > 1 && nq1 >= 64;
-  const uint32_t P =
-      par ? std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)fgh::hw_threads(0) / S, nq1 / 128)) : 1u;
-  auto pa = [&](uint32_t r) { return (uint32_t)((uint64_t)nq1 * r / P); };
-  if (hs.size() < (size_t)S * P) hs.resize((size_t)S * P);
-  // ---- the joined tables (this thread's buffers, reused like hs): several
-  // snapshots' per-query tables are copied into their slots by the planning
-  // workers themselves, the lists joined after
-  struct Join {
-    std::vector<uint32_t> q_m, q_terms, lead, q_filter, ngroup, q_hlo, q_hhi, q_hsh, f_shift, f_seg, ch_f, ch_c, ch_t, ch_s;
-    std::vector<uint64_t> thr0, f_woff;
-    std::vector<float> q_ub, q_wt, q_wn, q_rup, f_tab, f_max;
-    std::vector<WItem> citems, ditems, scan, items;
-  };
-  static thread_local Join J_tl;
-  Join& J = J_tl;
-  for (auto* v : {&J.q_m, &J.q_terms, &J.lead, &J.q_filter, &J.ngroup, &J.q_hlo, &J.q_hhi, &J.q_hsh, &J.f_shift, &J.f_seg,
-                  &J.ch_f, &J.ch_c, &J.ch_t, &J.ch_s})
-    v->clear();
-  for (auto* v : {&J.thr0, &J.f_woff}) v->clear();
-  for (auto* v : {&J.q_ub, &J.q_wt, &J.q_wn, &J.q_rup, &J.f_tab, &J.f_max}) v->clear();
-  for (auto* v : {&J.citems, &J.ditems, &J.scan, &J.items}) v->clear();
-  auto &q_m = J.q_m, &q_terms = J.q_terms, &lead = J.lead, &q_filter = J.q_filter, &ngroup = J.ngroup, &q_hlo = J.q_hlo,
-       &q_hhi = J.q_hhi, &q_hsh = J.q_hsh, &f_shift = J.f_shift, &f_seg = J.f_seg, &ch_f = J.ch_f, &ch_c = J.ch_c,
-       &ch_t = J.ch_t, &ch_s = J.ch_s;
-  auto &thr0 = J.thr0, &f_woff = J.f_woff;
-  auto &q_ub = J.q_ub, &q_wt = J.q_wt, &q_wn = J.q_wn, &q_rup = J.q_rup, &f_tab = J.f_tab, &f_max = J.f_max;
-  auto &citems = J.citems, &ditems = J.ditems, &scan = J.scan;
-  const size_t nqt = (size_t)nq1 * fg::kMaxTerms;
-  if (S > 1) {
-    q_m.resize(nq);
-    lead.resize(nq);
-    ngroup.resize(nq);
-    thr0.resize(nq);
-    q_terms.resize(nqt * S);
-    q_ub.resize(nqt * S);
-    q_wt.resize(nqt * S);
-    q_wn.resize(nqt * S);
-    q_rup.resize(nqt * S);
-  }
-  auto put_slot = [&](uint32_t pc) {  // piece pc's per-query tables into its slots
-    const HostPlan& h = hs[pc];
-    const size_t v0 = (size_t)(pc / P) * nq1 + pa(pc % P), t0 = v0 * fg::kMaxTerms;
-    auto cp = [](auto& dst, const auto& src, size_t at) { std::copy(src.begin(), src.end(), dst.begin() + at); };
-    cp(q_m, h.q_m, v0);
-    cp(lead, h.lead, v0);
-    cp(ngroup, h.ngroup, v0);
-    cp(thr0, h.thr0, v0);
-    cp(q_terms, h.q_terms, t0);
-    cp(q_ub, h.q_ub, t0);
-    cp(q_wt, h.q_wt, t0);
-    cp(q_wn, h.q_wn, t0);
-    cp(q_rup, h.q_rup, t0);
-  };
-  if (par) {
-    std::vector<int> rcs((size_t)S * P, FG_OK);
-    std::vector<std::string> errs((size_t)S * P);
-    run_parallel(S * P, [&](uint32_t pc) {
-      const uint32_t a = pa(pc % P), b = pa(pc % P + 1);
-      fg_query_batch qp = *q;  // the slice: q_off / f_off hold absolute offsets
-      qp.n_queries = b - a;
-      qp.q_off = q->q_off + a;
-      if (q->f_off) qp.f_off = q->f_off + a;
-      if ((rcs[pc] = plan_host(ixs[pc / P], &qp, k, S, hs[pc], nq1))) errs[pc] = fg_last_error();
-      else put_slot(pc);
-    });
-    for (uint32_t pc = 0; pc < S * P; ++pc)
-      if (rcs[pc]) return fail(rcs[pc], "snapshot %u: %s", pc / P, errs[pc].c_str());
-  } else {
-    for (uint32_t s = 0; s < S; ++s) {
-      if (int rc = plan_host(ixs[s], q, k, S, hs[s], nq1)) {
-        if (S == 1) return rc;
-        const std::string e = fg_last_error();
-        return fail(rc, "snapshot %u: %s", s, e.c_str());
-      }
-      if (S > 1) put_slot(s);
-    }
-  }
-  if (ptrace) pt[1] = pnow();
-  uint32_t nf = 0;
-  if (S == 1) {
-    HostPlan& h = hs[0];
-    q_m.swap(h.q_m); q_terms.swap(h.q_terms); lead.swap(h.lead); q_filter.swap(h.q_filter); ngroup.swap(h.ngroup);
-    q_hlo.swap(h.q_hlo); q_hhi.swap(h.q_hhi); q_hsh.swap(h.q_hsh); thr0.swap(h.thr0); q_ub.swap(h.q_ub);
-    q_wt.swap(h.q_wt); q_wn.swap(h.q_wn); q_rup.swap(h.q_rup);
-    f_shift.swap(h.f_shift); f_woff.swap(h.f_woff); f_tab.swap(h.f_tab); f_max.swap(h.f_max);
-    ch_f.swap(h.ch_f); ch_c.swap(h.ch_c); ch_t.swap(h.ch_t); ch_s.swap(h.ch_s);
-    citems.swap(h.citems); ditems.swap(h.ditems); scan.swap(h.scan);
-    nf = h.nf;
-  } else {
-    auto cat = [](auto& dst, const auto& src) { dst.insert(dst.end(), src.begin(), src.end()); };
-    f_woff.push_back(0);
-    for (uint32_t pc = 0; pc < S * P; ++pc) {
-      HostPlan& h = hs[pc];
-      const uint32_t s = pc / P, fb = nf, vb = s * nq1 + pa(pc % P);
-      for (uint32_t f : h.q_filter) q_filter.push_back(f == 0xFFFFFFFFu ? f : fb + f);
-      cat(f_shift, h.f_shift); cat(f_tab, h.f_tab); cat(f_max, h.f_max);
-      const uint64_t wb = f_woff.back();
-      for (uint32_t f = 0; f < h.nf; ++f) {
-        f_woff.push_back(wb + h.f_woff[f + 1]);
-        f_seg.push_back(s);
-      }
-      for (uint32_t f : h.ch_f) ch_f.push_back(fb + f);
-      cat(ch_c, h.ch_c); cat(ch_t, h.ch_t); cat(ch_s, h.ch_s);
-      for (WItem x : h.citems) { x.q += vb; citems.push_back(x); }
-      for (WItem x : h.ditems) { x.q += vb; ditems.push_back(x); }
-      for (WItem x : h.scan) { x.q += vb; scan.push_back(x); }
-      nf += h.nf;
-    }
-    // one bin geometry per batch query over the snapshots where it has work
-    // items (fg_plan_link's rule): a bin counts the same scores in every slot
-    q_hlo.assign(nq, 0x3F800000u);
-    q_hhi.assign(nq, 0x3F800000u);
-    q_hsh.assign(nq, 31);
-    for (uint32_t i = 0, r = 0; i < nq1; ++i) {
-      while (i >= pa(r + 1)) ++r;  // the piece of query i
-      const uint32_t li = i - pa(r);
-      uint32_t l = 0, hh = 0;
-      bool any = false;
-      for (uint32_t s = 0; s < S; ++s) {
-        const HostPlan& h = hs[s * P + r];
-        if (!h.ngroup[li]) continue;
-        l = std::max(l, h.q_hlo[li]);
-        hh = std::max(hh, h.q_hhi[li]);
-        any = true;
-      }
-      if (!any) continue;
-      hh = std::max(hh, l);
-      for (uint32_t s = 0; s < S; ++s) {
-        q_hlo[s * nq1 + i] = l;
-        q_hhi[s * nq1 + i] = hh;
-        q_hsh[s * nq1 + i] = bin_shift(l, hh);
-      }
-    }
-  }
-  if (ptrace) pt[2] = pnow();
-  if (f_woff[nf] * 4 > (8ull << 30)) return fail(FG_EUNSUPPORTED, "facet masks of this batch exceed 8 GiB");
-  if (ch_f.size() > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "facet postings of this batch too large");
-  if (citems.size() + ditems.size() + scan.size() > 0x7FFFFFFFull)
-    return fail(FG_EUNSUPPORTED, "batch too large (%zu work items)", citems.size() + ditems.size() + scan.size());
-  using W = WItem;
-  // k_conj: single-list queries' items first (their own k_conj launch), each part
-  // in sweep order; k_disj: sweep order.  A stable LSD radix sort on (not single,
-  // key quantized to 31 bits): the order is a scheduling choice only (every
-  // order gives the same hits), and it takes a fraction of a comparison sort's
-  // host time on a 20K-item batch.
-  auto single = [&](const W& x) { return q_m[x.q] == fg::qm_pack(1, 1, 0); };
-  // k_conj: the sweep split into 8 query groups, one per XCD (the kernel hands
-  // XCD x the x-th eighth of its items), the queries whose lead list is the
-  // same term in one group, groups balanced by items: headline k_conj 1.049 ->
-  // 1.001 ms, identical hits (profiles/r05/ab/ab_xcd_key_balanced.log; by the
-  // second list, ab_xcd_part.json: L2 hit rate 0.32 -> 0.23, DRAM 4.09 -> 4.57
-  // GB, each XCD walks the whole doc range for fewer queries).  The same split of k_disj by
-  // densest clause: OR top-20 2.78 -> 3.30 ms, top-1000 5.26 -> 6.86 ms -- its
-  // sweep stays doc-ordered.
-  constexpr bool xcd_part = true;
-  std::vector<uint8_t> q_grp;
-  auto groups = [&](const std::vector<W>& items) {
-    q_grp.assign(nq, 0);
-    // grouped by the lead list (ab_xcd_key_balanced.log: and3 1.001 ms, against 1.009
-    // by the second list; the last list, the query alone and the slot's snapshot
-    // measured no better)
-    auto probe_term = [&](uint32_t qv) { return q_terms[(size_t)qv * fg::kMaxTerms]; };
-    // the multi-list items only (single-list ones keep the sweep and run as a
-    // launch of their own, k_conj<true> over the first n_single items), counted
-    // per query slot (all of a slot's items share its lead term): the slots
-    // radix-sorted by term, the (term, items) counts, the terms by items
-    // (a comparison sort over every item's term cost ~0.4 ms of an 8-snapshot batch)
-    static thread_local std::vector<uint64_t> ka, kb;
-    ka.clear();
-    for (uint32_t v = 0; v < nq; ++v)
-      if (ngroup[v] && fg::qm_must(q_m[v]) && q_m[v] != fg::qm_pack(1, 1, 0))  // (k_conj slots only)
-        ka.push_back(((uint64_t)probe_term(v) << 32) | v);
-    kb.resize(ka.size());
-    for (int sh = 32; sh < 64; sh += 11) {
-      uint32_t cnt[2049] = {0};
-      for (uint64_t x : ka) cnt[((x >> sh) & 2047u) + 1]++;
-      for (int d = 0; d < 2048; ++d) cnt[d + 1] += cnt[d];
-      for (uint64_t x : ka) kb[cnt[(x >> sh) & 2047u]++] = x;
-      ka.swap(kb);
-    }
-    std::vector<std::pair<uint64_t, uint32_t>> by;  // (items, first index in ka)
-    for (size_t i = 0; i < ka.size();) {
-      size_t j = i;
-      uint64_t c = 0;
-      for (; j < ka.size() && (ka[j] >> 32) == (ka[i] >> 32); ++j) c += ngroup[(uint32_t)ka[j]];
-      by.emplace_back(c, (uint32_t)i);
-      i = j;
-    }
-    std::sort(by.begin(), by.end(), [&](auto& a, auto& b) {
-      return a.first > b.first || (a.first == b.first && (ka[a.second] >> 32) < (ka[b.second] >> 32));
-    });
-    uint64_t gl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (auto& [c, i0] : by) {
-      const uint32_t g = (uint32_t)(std::min_element(gl, gl + 8) - gl);
-      gl[g] += c;
-      for (size_t j = i0; j < ka.size() && (ka[j] >> 32) == (ka[i0] >> 32); ++j) q_grp[(uint32_t)ka[j]] = (uint8_t)g;
-    }
-    (void)items;
-  };
-  auto radix = [&](std::vector<W>& items, bool conj) {
-    const size_t n = items.size();
-    static thread_local std::vector<uint64_t> a, bb;  // (sort key << 32) | item index
-    a.resize(n);
-    bb.resize(n);
-    // (items of queries probing the same list next to each other within each
-    // 1/2048 of the sweep, so one XCD's L2 serves that list to all of them:
-    // measured slower, profiles/r04/ab/ab_sweep_*.log)
-    const bool part = conj && xcd_part;
-    if (part) groups(items);
-    for (size_t x = 0; x < n; ++x) {
-      const double kk = std::min(std::max(items[x].key, 0.0), 1.0);
-      // single-list items keep the plain sweep (grouped: C3's mix 1.07 -> 1.11 ms)
-      // (within a group, the sweep alone: also keying the items of one second / third /
-      // lead list together inside each 1/16 or 1/64 of the sweep ran 0.971 -> 1.004 /
-      // 0.999 / 0.982 ms, identical hits: profiles/r06/ab/conj_order.log)
-      const uint32_t sw = part && !single(items[x]) ? ((uint32_t)q_grp[items[x].q] << 28) | (uint32_t)(kk * 268435455.0)
-                                                    : (uint32_t)(kk * 2147483647.0);
-      const uint32_t rk = (conj && single(items[x]) ? 0u : 0x80000000u) | sw;
-      a[x] = ((uint64_t)rk << 32) | (uint64_t)x;
-    }
-    for (int sh = 32; sh < 64; sh += 11) {
-      uint32_t cnt[2049] = {0};
-      for (size_t x = 0; x < n; ++x) cnt[((a[x] >> sh) & 2047u) + 1]++;
-      for (int d = 0; d < 2048; ++d) cnt[d + 1] += cnt[d];
-      for (size_t x = 0; x < n; ++x) bb[cnt[(a[x] >> sh) & 2047u]++] = a[x];
-      a.swap(bb);
-    }
-    static thread_local std::vector<W> sorted;
-    sorted.resize(n);
-    for (size_t x = 0; x < n; ++x) sorted[x] = items[(uint32_t)a[x]];
-    items.swap(sorted);
-  };
-  radix(citems, true);
-  radix(ditems, false);
-  auto& items = J.items;
-  items.reserve(citems.size() + ditems.size() + scan.size());
-  items.insert(items.end(), citems.begin(), citems.end());
-  const uint64_t n_conj = citems.size();
-  items.insert(items.end(), ditems.begin(), ditems.end());
-  uint64_t n_single = 0;
-  for (const W& x : citems) n_single += single(x) ? 1 : 0;
-  std::stable_sort(scan.begin(), scan.end(), [](const W& a, const W& b) { return a.key < b.key; });
-  const uint64_t n_main = items.size(), n_scan = scan.size();
-  const uint64_t chunks = n_main + n_scan;  // from here on: work items (k_conj / k_disj, then k_scan)
-  if (chunks > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "batch too large (%llu work items)", (unsigned long long)chunks);
-  items.insert(items.end(), scan.begin(), scan.end());
-  static thread_local std::vector<uint32_t> work_q, work_c, work_n;
-  static thread_local std::vector<uint64_t> cand_off;
-  work_q.resize(chunks);
-  work_c.resize(chunks);
-  work_n.resize(chunks);
-  cand_off.assign(nq + 1, 0);
-  for (uint64_t w = 0; w < chunks; ++w) {
-    work_q[w] = items[w].q;
-    work_c[w] = items[w].c;
-    work_n[w] = items[w].n;
-  }
-  // each work item appends at most k keys to its query's candidate list
-  for (uint32_t i = 0; i < nq; ++i) cand_off[i + 1] = cand_off[i] + (uint64_t)ngroup[i] * k;
-
-  if (ptrace) pt[3] = pnow();
-  auto p = std::make_unique<fg_plan>();
-  p->nq = nq;
-  p->nq_batch = nq1;
-  p->n_segs = S;
-  p->k = k;
-  p->mode = q->mode;
-  p->total_chunks = (uint32_t)chunks;
-  p->n_scan = (uint32_t)n_scan;
-  p->mem.dev = ix->dev;
-  // one allocation: [inputs | zeroed (thresh, cand_cnt, facet masks) | candidates | outputs]
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t nch = ch_f.size();
-  const size_t s_qm = al(4ull * nq), s_qt = al(4ull * nq * fg::kMaxTerms), s_lead = al(4ull * nq),
-               s_wq = al(4ull * chunks), s_wc = al(4ull * chunks), s_wn = al(4ull * chunks),
-               s_co = al(8ull * (nq + 1)), s_t0 = al(8ull * nq), s_ub = al(4ull * nq * fg::kMaxTerms),
-               s_cache = al(4ull * 512 * S),
-               s_qf = al(4ull * nq), s_fs = al(4ull * nf),
-               s_fw = al(8ull * nf), s_ft = al(4ull * nf * 256), s_fm = al(4ull * nf), s_ch = al(4ull * nch),
-               s_hb = al(4ull * nq), s_fg = S > 1 ? al(4ull * nf) : 0,
-               s_sg = S > 1 ? al(sizeof(fg::DevIndex) * S) : 0, s_sb = S > 1 ? al(4ull * S) : 0;
-  // the snapshots' first docs in their concatenation (k_final's merged select)
-  std::vector<uint32_t> seg_base;
-  if (S > 1) {
-    uint64_t b = 0;
-    for (uint32_t x = 0; x < S; ++x) {
-      seg_base.push_back((uint32_t)std::min<uint64_t>(b, 0xFFFFFFFFull));
-      b += ixs[x]->n_docs;
-    }
-    if (b > 0xFFFFFFFFull) seg_base.clear();  // no merged select past 2^32 docs
-  }
-  // the snapshots' tf caches (query-time scoring, DevIndex::cache): one copy per
-  // distinct set of statistics (a namespace's segments share one)
-  std::vector<uint32_t> cache_of(S, 0);
-  for (uint32_t x = 0; x < S; ++x) {
-    uint32_t c = 0;
-    while (c < x && std::memcmp(ixs[cache_of[c]]->cache, ixs[x]->cache, sizeof ixs[x]->cache) != 0) ++c;
-    cache_of[x] = c < x ? cache_of[c] : x;  // x: the first snapshot with these statistics
-  }
-  const size_t s_in = s_qm + s_qt + s_lead + s_wq + s_wc + s_wn + s_co + s_t0 + 4 * s_ub + s_cache + s_qf + s_fs + s_fw +
-                      s_ft + s_fm + 4 * s_ch + 2 * s_hb + s_fg + s_sg + s_sb;
-  // one score histogram per query (DevPlan::hist: k_conj's and k_disj's running thresholds)
-  // (thresholds and histograms: one per batch query, shared by its slots)
-  const size_t s_thr = al(8ull * nq1), s_cc = al(4ull * nq), s_mask = al(4ull * f_woff[nf]),
-               s_hist = al(4ull * nq1 * fg::kQBins);
-  const size_t s_ck = al(8ull * cand_off[nq]);
-  const size_t s_os = al(4ull * nq * k), s_od = al(4ull * nq * k), s_on = al(4ull * nq);
-#ifdef FG_DIAG
-  const size_t s_dg = al(8ull * fg::kDiagPerWg * (chunks + nq));
-#else
-  const size_t s_dg = 0;
-#endif
-  const size_t total = s_in + s_thr + s_cc + s_mask + s_hist + s_ck + s_os + s_od + s_on + s_dg;
-  HIPCHK(hipSetDevice(ix->dev));
-  char* base = static_cast<char*>(ix->pool->get(std::max<size_t>(total, 256), &p->ws_got));
-  if (!base) return fail(FG_EOOM, "plan workspace hipMalloc(%zu) failed", total);
-  p->ws = base;
-  p->ix = ix;  // owns the workspace from here on (returned to ix->pool); retained below
-  fg_index_retain(ix);
-  for (uint32_t s = 1; s < S; ++s) {
-    fg_index_retain(ixs[s]);
-    p->segs.push_back(ixs[s]);
-  }
-  p->ws_bytes = total;
-  // a small zero region (thresholds, candidate counts, facet masks) travels
-  // zeroed with the upload, so the first execute needs no memset
-  const size_t s_zero = s_thr + s_cc + s_mask + s_hist;
-  const size_t s_up = s_in + (s_zero <= (64u << 10) ? s_zero : 0);
-  PinnedLease pin(*ix->pinned, s_up);
-  std::vector<char> staging_pageable;  // only if the pinned allocation failed
-  char* staging = static_cast<char*>(pin.p);
-  if (!staging) {
-    staging_pageable.assign(s_up, 0);
-    staging = staging_pageable.data();
-  } else if (s_up > s_in) {
-    std::memset(staging + s_in, 0, s_up - s_in);
-  }
-  size_t o = 0;
-  auto put = [&](const void* src, size_t bytes, size_t slot) {
-    if (bytes) std::memcpy(staging + o, src, bytes);
-    void* dptr = base + o;
-    o += slot;
-    return dptr;
-  };
-  p->d.q_m = (const uint32_t*)put(q_m.data(), 4ull * nq, s_qm);
-  p->d.q_terms = (const uint32_t*)put(q_terms.data(), 4ull * nq * fg::kMaxTerms, s_qt);
-  p->d.q_lead_df = (const uint32_t*)put(lead.data(), 4ull * nq, s_lead);
-  p->d.work_q = (const uint32_t*)put(work_q.data(), 4ull * chunks, s_wq);
-  p->d.work_c = (const uint32_t*)put(work_c.data(), 4ull * chunks, s_wc);
-  p->d.work_n = (const uint32_t*)put(work_n.data(), 4ull * chunks, s_wn);
-  p->d.cand_off = (const uint64_t*)put(cand_off.data(), 8ull * (nq + 1), s_co);
-  p->d.q_thr0 = (const uint64_t*)put(thr0.data(), 8ull * nq, s_t0);
-  p->d.q_ub = (const float*)put(q_ub.data(), 4ull * nq * fg::kMaxTerms, s_ub);
-  p->d.q_wt = (const float*)put(q_wt.data(), 4ull * nq * fg::kMaxTerms, s_ub);
-  p->d.q_wn = (const float*)put(q_wn.data(), 4ull * nq * fg::kMaxTerms, s_ub);
-  p->d.q_rup = (const float*)put(q_rup.data(), 4ull * nq * fg::kMaxTerms, s_ub);
-  std::vector<const float*> d_cache(S, nullptr);
-  {
-    const size_t o0 = o;
-    for (uint32_t x = 0; x < S; ++x) {
-      if (cache_of[x] != x) continue;
-      std::memcpy(staging + o, ixs[x]->cache, 4ull * 512);
-      d_cache[x] = (const float*)(base + o);
-      o += 4ull * 512;
-    }
-    for (uint32_t x = 0; x < S; ++x) d_cache[x] = d_cache[cache_of[x]];
-    o = o0 + s_cache;
-  }
-  p->d0 = ix->d;
-  p->d0.cache = d_cache[0];
-  p->d.f.q_filter = (const uint32_t*)put(q_filter.data(), 4ull * nq, s_qf);
-  p->d.f.f_shift = (const uint32_t*)put(f_shift.data(), 4ull * nf, s_fs);
-  p->d.f.f_woff = (const uint64_t*)put(f_woff.data(), 8ull * nf, s_fw);
-  p->d.f.f_tab = (const float*)put(f_tab.data(), 4ull * nf * 256, s_ft);
-  p->d.f.f_max = (const float*)put(f_max.data(), 4ull * nf, s_fm);
-  p->d.f.ch_filter = (const uint32_t*)put(ch_f.data(), 4ull * nch, s_ch);
-  p->d.f.ch_clause = (const uint32_t*)put(ch_c.data(), 4ull * nch, s_ch);
-  p->d.f.ch_term = (const uint32_t*)put(ch_t.data(), 4ull * nch, s_ch);
-  p->d.f.ch_start = (const uint32_t*)put(ch_s.data(), 4ull * nch, s_ch);
-  p->d.q_hlo = (const uint32_t*)put(q_hlo.data(), 4ull * nq, s_hb);
-  p->d.q_hsh = (const uint32_t*)put(q_hsh.data(), 4ull * nq, s_hb);
-  if (S > 1) {
-    std::vector<fg::DevIndex> segs(S);
-    for (uint32_t s = 0; s < S; ++s) {
-      segs[s] = ixs[s]->d;
-      segs[s].cache = d_cache[s];
-    }
-    p->d.f.f_seg = (const uint32_t*)put(f_seg.data(), 4ull * nf, s_fg);
-    p->d.segs = (const fg::DevIndex*)put(segs.data(), sizeof(fg::DevIndex) * S, s_sg);
-    const uint32_t* sb = (const uint32_t*)put(seg_base.data(), 4ull * seg_base.size(), s_sb);
-    p->d.seg_base = seg_base.empty() ? nullptr : sb;
-  }
-  // on the planning thread's own stream (or the caller's `up`): a plan built
-  // while another thread's batch runs does not serialise against it through the
-  // legacy null stream
-  HIPCHK(hipMemcpyAsync(base, staging, s_up, hipMemcpyHostToDevice, up));
-  p->up_stream = up;
-  p->zeroed = s_up > s_in;
-  if (sync || !pin.p) {
-    HIPCHK(hipStreamSynchronize(up));
-  } else {
-    p->pin = pin.p;  // the plan returns it (after a sync) when destroyed
-    p->pin_n = pin.n;
-    pin.p = nullptr;
-  }
-  char* cur = base + s_in;
-  p->zero_region = cur;
-  p->zero_bytes = s_zero;
-  p->d.thresh = (uint64_t*)cur;
-  cur += s_thr;
-  p->d.cand_cnt = (uint32_t*)cur;
-  cur += s_cc;
-  p->d.f.fmask = (uint32_t*)cur;
-  cur += s_mask;
-  p->d.hist = (uint32_t*)cur;
-  cur += s_hist;
-  p->d.cand_keys = (uint64_t*)cur;
-  cur += s_ck;
-  p->own_score = (float*)cur;
-  cur += s_os;
-  p->own_doc = (uint32_t*)cur;
-  cur += s_od;
-  p->own_n = (uint32_t*)cur;
-  cur += s_on;
-  p->d.diag = s_dg ? (uint64_t*)cur : nullptr;
-  p->diag_words = s_dg / 8;
-  p->d.n_queries = nq;
-  p->d.total_chunks = (uint32_t)n_main;
-  p->d.n_conj = (uint32_t)n_conj;
-  p->d.n_scan = (uint32_t)n_scan;
-  p->d.n_single = (uint32_t)n_single;
-  p->d.k = k;
-  p->d.seg_nq = S > 1 ? nq1 : 0;
-  p->d.n_segs = S;
-  // query-time scores when some snapshot's statistics changed since its build
-  // (a commit elsewhere in the namespace); else the build-time scores
-  p->d.feat = 0;
-  for (uint32_t x = 0; x < S; ++x)
-    if (!ixs[x]->same_stats) p->d.feat = 4u;
-  for (uint32_t x = 0; x < S && p->d.feat; ++x)
-    p->d.feat |= (ixs[x]->d.tfn_name ? 1u : 0u) | (ixs[x]->d.n_esc ? 2u : 0u);
-  // several snapshots: a batch query's slots share its threshold score-only, so a
-  // doc of another snapshot tied with the k-th score is never pruned (the merge
-  // breaks such ties by snapshot)
-  p->d.pub_mask = S > 1 ? 0xFFFFFFFF00000000ull : ~0ull;
-  p->h_any.assign(nq1, 0);
-  for (uint32_t v = 0; v < nq; ++v)
-    if (ngroup[v]) p->h_any[v % nq1] = 1;
-  p->h_lo.swap(q_hlo);
-  p->h_hi.swap(q_hhi);
-  p->d.f.n_filters = nf;
-  p->d.f.n_chunks = (uint32_t)nch;
-  if (ptrace && S > 1) {
-    pt[4] = pnow();
-    fprintf(stderr, "[fg plan] %u snapshots x %u queries: plan_host %.3f join %.3f items %.3f stage+upload %.3f ms\n", S,
-            nq1, pt[1] - pt[0], pt[2] - pt[1], pt[3] - pt[2], pt[4] - pt[3]);
-  }
-  *out = p.release();
-  return FG_OK;
-}
-
 // the kernels of a planned batch on stream s, or of one part of it: the k_disj
 // items [from, to) of its sweep (fractions of the k_disj range, in sweep order:
 // every query's first docs first).  The first part (from = 0) zeroes the plan's
@@ -3343,15 +2485,13 @@ int fg_plan_set_hist_span(fg_plan* p, const uint32_t* lo, const uint32_t* hi) {
   for (uint32_t s = 0; s < S; ++s)
     for (uint32_t i = 0; i < nb; ++i) {
       const size_t v = (size_t)s * nb + i;
-      uint32_t l = lo[i], h = std::max(hi[i], lo[i]);
-      if (l == 0 && h == 0) {  // no shard has work for the query: keep the plan's own bins
-        l = p->h_lo[v];
-        h = p->h_hi[v];
-      }
-      p->h_lo[v] = l;
-      p->h_hi[v] = h;
-      L[v] = l;
-      SH[v] = bin_shift(l, h);
+      // (both 0: no shard has work for the query, keep the plan's own bins)
+      const bool own = lo[i] == 0 && hi[i] == 0;
+      const fgh::Bins b = own ? fgh::union_bins(p->h_lo[v], p->h_hi[v]) : fgh::union_bins(lo[i], hi[i]);
+      p->h_lo[v] = b.lo;
+      p->h_hi[v] = b.hi;
+      L[v] = b.lo;
+      SH[v] = b.shift;
     }
   HIPCHK(hipSetDevice(p->ix->dev));
   if (p->pin) HIPCHK(hipStreamSynchronize(p->up_stream));  // an upload still in flight would overwrite them
@@ -3474,9 +2614,9 @@ int fg_plan_link(fg_plan* const* plans, uint32_t n) {
       l = std::max(l, plans[i]->h_lo[q]);
       h = std::max(h, plans[i]->h_hi[q]);
     }
-    h = std::max(h, l);
-    lo[q] = l;
-    sh[q] = bin_shift(l, h);
+    const fgh::Bins b = fgh::union_bins(l, h);
+    lo[q] = b.lo;
+    sh[q] = b.shift;
   }
   HIPCHK(hipSetDevice(o->ix->dev));
   for (uint32_t i = 0; i < n; ++i) {
@@ -3497,7 +2637,8 @@ int fg_plan_link(fg_plan* const* plans, uint32_t n) {
 int fg_search_batch(fg_index* ix, const fg_query_batch* q, uint32_t k, float* out_score, uint32_t* out_doc,
                     uint32_t* out_n) {
   fg_plan* p = nullptr;
-  int rc = plan_create(ix, q, k, &p, false);  // execute is queued behind the upload on the same stream
+  // execute is queued behind the upload on the same stream
+  int rc = plan_create_multi(&ix, 1, q, k, &p, false, hipStreamPerThread);
   if (rc) return rc;
   std::unique_ptr<fg_plan> guard(p);
   // the calling thread's own stream: concurrent callers (tokio workers sharing
@@ -3566,8 +2707,6 @@ class ShardWorkers {
   std::deque<std::function<void()>> q_;
 };
 
-static void run_parallel(uint32_t n, const std::function<void(uint32_t)>& f) { ShardWorkers::get().run(n, f); }
-
 // One batch over several shards / segments / namespaces of one logical index
 // (SURVEY.md §8b fg_search_sharded, §8e).  The shards of each device run as ONE
 // multi-snapshot plan (fg_plan_create_multi: one upload, one launch per kernel,
@@ -3579,6 +2718,7 @@ static void run_parallel(uint32_t n, const std::function<void(uint32_t)>& f) { S
 // per-thread streams.
 }  // extern "C"
 namespace fgh {
+void run_parallel(uint32_t n, const std::function<void(uint32_t)>& f) { ShardWorkers::get().run(n, f); }
 SearchTrace& search_trace() {
   static SearchTrace t;
   return t;
