@@ -202,6 +202,7 @@ class SharedVec {
 // them (fg_index_rescore_many)
 struct Weights {
   SharedVec<float> wt, wn;
+  SharedVec<float> it, in;  // the idf of each weight (w = idf * (1 + K1)): a phrase's weight sums them
 };
 
 
@@ -363,6 +364,7 @@ struct fg_index {
   uint64_t n_postings = 0, device_bytes = 0, dir_entries = 0, tile_entries = 0;
   uint32_t n_dense = 0, n_rank = 0;  // n_rank: rank-kind slots, plain (d.n_prank) and sparse
   uint64_t n_srank_words = 0;        // sparse rank words (d.srank_w)
+  bool has_positions = false;        // the forward index (d.fwd_off / d.fwd): phrase queries run on it
   // ---- statistics (this snapshot's own: the Searcher-wide ones of its commit).
   // Scores are formed at query time from them (DevIndex::tfn, DevPlan::q_wt /
   // q_wn, the plan's copy of `cache`), as tantivy's TermScorer does.
@@ -371,6 +373,8 @@ struct fg_index {
   float avgdl[2] = {0, 0};
   float cache[512];
   fgh::SharedVec<float> w_text, w_name;
+  // each weight's idf (w = idf * (1 + K1)): Bm25Weight::for_terms sums a phrase's idfs before the factor
+  fgh::SharedVec<float> idf_text, idf_name;
   fgh::SharedVec<uint32_t> h_alive;  // the alive bitset of this snapshot (empty: every doc)
   // ---- bounds: computed ONCE when the structure is built (k_score / k_bucket /
   // k_tsub / k_ktop under the build's statistics) and shared by every rescore of

@@ -115,6 +115,8 @@ constexpr uint32_t kLadderExtra[kNumLadderExtra] = {2, 3, 5, 13, 25, 50, 125, 25
 constexpr uint32_t kNumLadder = kNumTopK + kNumLadderExtra;  // FG_LADDER_LEVELS
 constexpr uint32_t kLadderKs[kNumLadder] = {1, 2, 3, 5, 10, 13, 20, 25, 50, 100, 125, 250, 500, 1000};
 
+constexpr uint32_t kPhraseMaxGroup = 4;   // k_phrase: at most this many lead chunks per work item (each item starts
+                                          // from the query's published threshold: shorter items prune sooner)
 constexpr uint32_t kMaxFacetClauses = 8;  // facet clauses per query (FG_MAX_FACET_CLAUSES)
 constexpr uint32_t kFmaskChunk = 8192;    // facet postings per k_fmask workgroup
 constexpr uint32_t kScanMaxGroup = 32;    // k_scan: at most this many 4096-doc tiles per work item
@@ -136,6 +138,9 @@ __host__ __device__ inline uint32_t qm_terms(uint32_t qm) { return qm & 0xFFu; }
 __host__ __device__ inline uint32_t qm_must(uint32_t qm) { return (qm >> 8) & 0xFFu; }
 __host__ __device__ inline uint32_t qm_not(uint32_t qm) { return (qm >> 16) & 0xFFu; }
 __host__ __device__ inline uint32_t qm_pack(uint32_t m, uint32_t nm, uint32_t nx) { return m | (nm << 8) | (nx << 16); }
+// a phrase query's slot (k_phrase): bits 0-7 its distinct terms, 24-31 the phrase's terms
+__host__ __device__ inline uint32_t qm_phrase(uint32_t distinct, uint32_t n) { return distinct | (n << 24); }
+__host__ __device__ inline uint32_t qm_phrase_terms(uint32_t qm) { return qm >> 24; }
 
 // Rank words (DevIndex::rank): one u64 per 32 docs, the low half the docs'
 // presence bits, the high half the number of the term's postings before the
@@ -278,7 +283,17 @@ struct DevIndex {
   uint32_t rank_words;       // words per plain rank-kind term: ceil(N / 32)
   uint32_t n_prank;          // plain rank-kind slots
   uint32_t srank_blocks;     // block entries per sparse rank-kind term: ceil(N / 1024)
+  // Forward index (fg_docs_input::keep_positions; nullptr without): per field the
+  // doc's tokens addressed by POSITION, fwd[fwd_off[d] + p] = the VOCABULARY id of
+  // the token at analyzer position p of doc d, kFwdNone where the analyzer dropped
+  // one (RemoveLongFilter).  k_phrase verifies its candidates against it.  Shared
+  // by a snapshot and its rescores (structure).
+  const uint64_t* fwd_off;   // [N+1]
+  const uint32_t* fwd;       // [fwd_off[N]]
+  const uint64_t* fwd_off_name;  // [N+1], or nullptr (no `name` values)
+  const uint32_t* fwd_name;
 };
+constexpr uint32_t kFwdNone = 0xFFFFFFFFu;  // a dropped position: equals no term id
 
 // The exact tf_text | tf_name << 16 of posting p whose tf byte escaped (binary
 // search of the snapshot's escape list; rare: tf >= 255)
@@ -367,6 +382,14 @@ struct DevPlan {
   uint32_t n_single;            // k_conj: the first n_single work items belong to single-list queries
   uint32_t n_scan;              // k_scan work items (queries with no text terms), after the total_chunks
                                 // k_conj / k_disj items in work_q / work_c / work_n
+  uint32_t n_phrase;            // k_phrase work items (phrase queries), after the k_scan items: (query slot,
+                                // group of kChunk-posting chunks of the phrase's lead list).  A phrase slot's
+                                // q_terms row holds its distinct terms (the snapshot's ids), the lead -- the
+                                // one with the shortest list -- first; q_m = qm_phrase(distinct, terms);
+                                // q_wt[row][0] / q_wn[row][0] are the phrase's two field weights
+  const uint32_t* q_pterm;      // [nq * kMaxTerms] a phrase's terms as VOCABULARY ids (DevIndex::fwd), the
+                                //     anchor -- the rarest term's first occurrence in the phrase -- first
+  const uint32_t* q_ppos;       // [nq * kMaxTerms] ... and their position offsets within the phrase
   // Multi-snapshot plans (several segments / doc shards / namespaces of one
   // device in ONE launch per kernel): query slot v = s * seg_nq + q is query q
   // of the batch on snapshot segs[s]; every per-query array above is indexed by
@@ -491,6 +514,7 @@ hipError_t launch_disj(const DevIndex& ix, const DevPlan& pl, hipStream_t s, uin
                        uint32_t count = 0xFFFFFFFFu);
 hipError_t launch_fmask(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 hipError_t launch_scan(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
+hipError_t launch_phrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 // out_shard != nullptr: the merged select of a multi-snapshot plan (one list per batch query)
 hipError_t launch_final(const DevPlan& pl, float* out_score, uint32_t* out_doc, uint32_t* out_n, hipStream_t s,
                         uint32_t* out_shard = nullptr);

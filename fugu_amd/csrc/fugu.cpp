@@ -83,10 +83,11 @@ uint8_t fieldnorm_id(uint64_t n) {
   uint32_t x = n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)n;
   return (uint8_t)(std::upper_bound(t, t + 256, x) - t - 1);
 }
-float bm25_weight(uint64_t df, uint64_t n_docs) {
+float bm25_idf(uint64_t df, uint64_t n_docs) {
   float x = ((float)(n_docs - df) + 0.5f) / ((float)df + 0.5f);
-  return logf(1.0f + x) * (1.0f + kK1);
+  return logf(1.0f + x);
 }
+float bm25_weight(uint64_t df, uint64_t n_docs) { return bm25_idf(df, n_docs) * (1.0f + kK1); }
 void bm25_cache(float avgdl, float* out) {
   const uint32_t* t = fn_table().v;
   for (int i = 0; i < 256; ++i) out[i] = kK1 * ((1.0f - kB) + (kB * (float)t[i]) / avgdl);
@@ -535,14 +536,19 @@ int check_device(int dev) {
 // doc frequencies (global for a doc-sharded namespace).
 
 // BM25 weights of terms [0, V) for statistics (Ns, df_t, df_n) (tantivy's f32 order)
+// and their idfs (it, in: a phrase's weight sums them before the (1 + K1) factor)
 void bm25_weights(uint64_t Ns, const uint32_t* df_t, const uint32_t* df_n, uint32_t V, std::vector<float>& wt,
-                  std::vector<float>& wn) {
+                  std::vector<float>& wn, std::vector<float>& it, std::vector<float>& in) {
   wt.resize(V);
   wn.resize(V);
+  it.resize(V);
+  in.resize(V);
   parallel_ranges(V, hw_threads(0), [&](int, uint32_t b, uint32_t e) {
     for (uint32_t t = b; t < e; ++t) {
-      wt[t] = bm25_weight(df_t[t], Ns);
-      wn[t] = bm25_weight(df_n ? df_n[t] : 0u, Ns);
+      it[t] = bm25_idf(df_t[t], Ns);
+      in[t] = bm25_idf(df_n ? df_n[t] : 0u, Ns);
+      wt[t] = it[t] * (1.0f + kK1);
+      wn[t] = in[t] * (1.0f + kK1);
     }
   });
 }
@@ -565,11 +571,15 @@ void set_stats(fg_index* ix, uint64_t Ns, const uint64_t tot2[2], const uint32_t
   if (wts) {  // shared: at least V terms
     ix->w_text = wts->wt;
     ix->w_name = wts->wn;
+    ix->idf_text = wts->it;
+    ix->idf_name = wts->in;
   } else {
-    std::vector<float> wt, wn;
-    bm25_weights(Ns, df_t, df_n, V, wt, wn);
+    std::vector<float> wt, wn, it, in;
+    bm25_weights(Ns, df_t, df_n, V, wt, wn, it, in);
     ix->w_text = std::move(wt);
     ix->w_name = std::move(wn);
+    ix->idf_text = std::move(it);
+    ix->idf_name = std::move(in);
   }
   // facet field: Bm25Weight of a facet TermQuery (tf 1, no fieldnorms ->
   // FieldNormReader::constant(max_doc, 1) -> id 1, avg = total_num_tokens / N)
@@ -1713,6 +1723,64 @@ extern "C" {
 
 static int build_from_docs(fg_ctx* ctx, int dev, const fg_docs_input* in, const fg_global_stats* g, fg_index** out);
 
+// The forward index of a snapshot built with fg_docs_input::keep_positions
+// (DevIndex::fwd_off / fwd): per field every doc's tokens laid out by analyzer
+// position -- a gap entry leaves a kFwdNone hole before its token -- and
+// uploaded on the build stream (the background stream of a commit or a merge).
+// Structure: shared with the snapshot's rescores, counted in device_bytes.
+static int fwd_field(uint32_t N, const uint64_t* off, const uint32_t* tok, const uint64_t* gap, uint64_t n_gap,
+                     std::vector<uint64_t>& foff, std::vector<uint32_t>& fwd) {
+  const uint64_t nt = off[N];
+  for (uint64_t i = 0; i < n_gap; ++i)
+    if (gap[i] >= nt || gap[i] < off[0] || (i && gap[i] < gap[i - 1]))
+      return fail(FG_EINVAL, "gap list not ascending indices into the tokens");
+  foff.resize((size_t)N + 1);
+  try {
+    fwd.resize(nt + n_gap);
+  } catch (...) {
+    return fail(FG_EOOM, "forward index (%llu positions) allocation failed", (unsigned long long)(nt + n_gap));
+  }
+  uint64_t g = 0, o = 0;
+  for (uint32_t d = 0; d < N; ++d) {
+    foff[d] = o;
+    for (uint64_t i = off[d]; i < off[d + 1]; ++i) {
+      for (; g < n_gap && gap[g] == i; ++g) fwd[o++] = fg::kFwdNone;
+      fwd[o++] = tok[i];
+    }
+  }
+  foff[N] = o;
+  return FG_OK;
+}
+
+static int attach_positions(fg_index* ix, const fg_docs_input* in) {
+  if ((in->n_text_gap && !in->text_gap) || (in->n_name_gap && !in->name_gap)) return fail(FG_EINVAL, "gap count without a gap list");
+  const uint32_t N = in->n_docs;
+  const bool has_name_in = in->name_off && in->name_tok;
+  HIPCHK(hipSetDevice(ix->dev));
+  uint64_t bytes = 0;
+  std::vector<uint64_t> foff;
+  std::vector<uint32_t> fwd;
+  uint64_t* d_off = nullptr;
+  uint32_t* d_fwd = nullptr;
+  if (int rc = fwd_field(N, in->text_off, in->text_tok, in->text_gap, in->n_text_gap, foff, fwd)) return rc;
+  if (int rc = dev_upload(*ix->smem, foff.data(), foff.size(), &d_off, &bytes)) return rc;
+  if (int rc = dev_upload(*ix->smem, fwd.data(), fwd.size(), &d_fwd, &bytes)) return rc;
+  ix->d.fwd_off = d_off;
+  ix->d.fwd = d_fwd;
+  if (has_name_in && ix->d.tfn_name) {  // (no name postings: no phrase matches there)
+    if (int rc = fwd_field(N, in->name_off, in->name_tok, in->name_gap, in->n_name_gap, foff, fwd)) return rc;
+    if (int rc = dev_upload(*ix->smem, foff.data(), foff.size(), &d_off, &bytes)) return rc;
+    if (int rc = dev_upload(*ix->smem, fwd.data(), fwd.size(), &d_fwd, &bytes)) return rc;
+    ix->d.fwd_off_name = d_off;
+    ix->d.fwd_name = d_fwd;
+  }
+  ix->struct_bytes += bytes;
+  ix->device_bytes += bytes;
+  ix->has_positions = true;
+  g_bt.mark("forward index");
+  return FG_OK;
+}
+
 int fg_index_build_from_docs_global(fg_ctx* ctx, int dev, const fg_docs_input* in, const fg_global_stats* g,
                                     fg_index** out) {
   if (!ctx || !in || !out || !in->text_off || (!in->text_tok && in->text_off[in->n_docs] > 0))
@@ -1724,13 +1792,22 @@ int fg_index_build_from_docs_global(fg_ctx* ctx, int dev, const fg_docs_input* i
   g_bt.start();
   LocalDict L;
   if (int rc = local_dict(in, g, L)) return rc;
-  if (L.tmap.empty()) return build_from_docs(ctx, dev, in, g, out);
-  g_bt.mark("local dictionary");
   const uint32_t V = in->n_terms;
   fg_index* ix = nullptr;
-  if (int rc = build_from_docs(ctx, dev, &L.in, g ? &L.g : nullptr, &ix)) return rc;
-  ix->tmap = std::move(L.tmap);
-  ix->n_vocab = V;
+  if (L.tmap.empty()) {
+    if (int rc = build_from_docs(ctx, dev, in, g, &ix)) return rc;
+  } else {
+    g_bt.mark("local dictionary");
+    if (int rc = build_from_docs(ctx, dev, &L.in, g ? &L.g : nullptr, &ix)) return rc;
+    ix->tmap = std::move(L.tmap);
+    ix->n_vocab = V;
+  }
+  // (from the caller's tokens: a snapshot with its own dictionary still keeps vocabulary ids here)
+  if (in->keep_positions)
+    if (int rc = attach_positions(ix, in)) {
+      fg_index_release(ix);
+      return rc;
+    }
   *out = ix;
   return FG_OK;
 }
@@ -1989,6 +2066,7 @@ static int rescore_one(const fg_index* base, const fg_global_stats* g, const uin
   ix->tile_entries = base->tile_entries;
   ix->n_rank = base->n_rank;
   ix->n_srank_words = base->n_srank_words;
+  ix->has_positions = base->has_positions;
   ix->off = base->off;
   ix->df_text = base->df_text;
   ix->df_name = base->df_name;
@@ -2101,10 +2179,12 @@ int fg_index_rescore_many(const fg_index* const* bases, uint32_t n, const fg_glo
   fgh::Weights wts;
   g_bt.start();
   if (V) {
-    std::vector<float> wt, wn;
-    bm25_weights(g->n_docs, g->df_text, g->df_name, V, wt, wn);
+    std::vector<float> wt, wn, it, in;
+    bm25_weights(g->n_docs, g->df_text, g->df_name, V, wt, wn, it, in);
     wts.wt = std::move(wt);
     wts.wn = std::move(wn);
+    wts.it = std::move(it);
+    wts.in = std::move(in);
   }
   g_bt.mark("rescore: shared weights");
   for (uint32_t i = 0; i < n; ++i) {
@@ -2158,7 +2238,7 @@ int fg_index_stats_get(const fg_index* ix, fg_index_stats* o) {
   o->n_dense_f32 = ix->n_dense;
   o->n_rank_terms = ix->n_rank;
   o->n_sparse_rank_terms = ix->n_rank - ix->d.n_prank;
-  o->reserved0 = 0;
+  o->has_positions = ix->has_positions ? 1u : 0u;
   o->rank_bytes = 8ull * ix->d.n_prank * ix->d.rank_words +
                   8ull * (ix->n_rank - ix->d.n_prank) * ix->d.srank_blocks + 8ull * ix->n_srank_words;
   return FG_OK;
@@ -2331,6 +2411,7 @@ static int execute_impl(fg_plan* p, hipStream_t s, float* os, uint32_t* od, uint
   const uint32_t b = last ? nd : (uint32_t)std::min<double>(nd, std::llround(to * nd));
   if (b > a) HIPCHK(fg::launch_disj(p->d0, p->d, s, a, b - a));
   if (last && p->d.n_scan) HIPCHK(fg::launch_scan(p->d0, p->d, s));
+  if (last && p->d.n_phrase) HIPCHK(fg::launch_phrase(p->d0, p->d, s));
   if (p->profile) HIPCHK(hipEventRecord(ev[1], s));
   if (last) HIPCHK(fg::launch_final(p->d, os, od, on, s, oshard));
   if (p->profile) {

@@ -117,9 +117,13 @@ void lower_put(std::string& out, uint32_t cp) {
 // The "default" analyzer of TEXT fields (src/db/schemas.rs:10,14):
 // SimpleTokenizer (runs of char::is_alphanumeric) -> RemoveLongFilter::limit(40)
 // (keeps tokens with < 40 UTF-8 bytes, measured before lowercasing) -> LowerCaser.
-void analyze(std::string_view s, std::vector<std::string>& out) {
+// pos (optional): each kept token's analyzer position -- a token RemoveLongFilter
+// drops still consumes one (tantivy's filter skips the token, its position stays)
+void analyze(std::string_view s, std::vector<std::string>& out, std::vector<uint32_t>* pos = nullptr) {
   out.clear();
+  if (pos) pos->clear();
   size_t i = 0;
+  uint32_t at = 0;
   while (i < s.size()) {
     size_t start = i;
     uint32_t cp = utf8_next(s, i);
@@ -132,7 +136,9 @@ void analyze(std::string_view s, std::vector<std::string>& out) {
       end = j;
     }
     i = end;
+    const uint32_t here = at++;
     if (end - start >= 40) continue;  // RemoveLongFilter
+    if (pos) pos->push_back(here);
     std::string tok;
     size_t k = start;
     while (k < end) lower_put(tok, utf8_next(s, k));
@@ -144,22 +150,38 @@ void analyze(std::string_view s, std::vector<std::string>& out) {
 // scratch buffer (valid until the next call).  Pure-ASCII text takes a byte
 // loop (runs of [0-9A-Za-z], < 40 bytes, lowercased): the same tokens as
 // analyze(), whose Unicode path handles everything else.
+// gaps: the index (among the kept tokens) of the token each dropped one came
+// immediately before, ascending, repeated for several in a row (Doc::gaps).
+void gaps_of(const std::vector<uint32_t>& pos, std::vector<uint32_t>& gaps) {
+  for (uint32_t i = 0, next = 0; i < pos.size(); next = pos[i++] + 1)
+    for (uint32_t p = next; p < pos[i]; ++p) gaps.push_back(i);
+}
 template <class F>
-void analyze_each(std::string_view s, std::string& scratch, std::vector<std::string>& toks, F&& f) {
+void analyze_each(std::string_view s, std::string& scratch, std::vector<std::string>& toks, std::vector<uint32_t>& gaps,
+                  F&& f) {
   bool ascii = true;
   for (unsigned char c : s) ascii = ascii && c < 0x80;
+  gaps.clear();
   if (!ascii) {
-    analyze(s, toks);
+    std::vector<uint32_t> pos;
+    analyze(s, toks, &pos);
+    gaps_of(pos, gaps);
     for (auto& t : toks) f(std::string_view(t));
     return;
   }
+  uint32_t kept = 0;
   auto alnum = [](unsigned char c) { return (c >= '0' && c <= '9') || (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z'); };
   size_t i = 0;
   while (i < s.size()) {
     while (i < s.size() && !alnum((unsigned char)s[i])) ++i;
     const size_t b = i;
     while (i < s.size() && alnum((unsigned char)s[i])) ++i;
-    if (i == b || i - b >= 40) continue;  // RemoveLongFilter
+    if (i == b) continue;
+    if (i - b >= 40) {  // RemoveLongFilter
+      gaps.push_back(kept);
+      continue;
+    }
+    ++kept;
     scratch.assign(s.data() + b, i - b);
     for (char& c : scratch)
       if (c >= 'A' && c <= 'Z') c = (char)(c + 32);
@@ -364,9 +386,10 @@ class DocStore {
 //   `t1 t2 -t3 +t4 ...`   each term's occur by its prefix (bare = Should)
 //   `t1 AND t2 AND ...`   every term Must
 //   `t1 OR t2 OR ...`     every term Should (the same query as `t1 t2 ...`)
-// Every term must analyze to exactly one token (more = PhraseQuery).  Anything
-// else (mixed AND / OR, parentheses, field:, phrases, boosts, ranges, a query
-// of MustNot clauses only) is FG_EUNSUPPORTED: the reference host runs tantivy.
+// A term that analyzes to several tokens (`e-mail`, `user@example.com`) and a
+// quoted literal ("new york") are PhraseQuery clauses at slop 0 (parse_clauses).
+// Anything else (mixed AND / OR, parentheses, field:, slop, boosts, ranges, a
+// query of MustNot clauses only) is FG_EUNSUPPORTED: the reference host runs tantivy.
 // An empty query is AllQuery (src/db/search.rs:115-116), handled by the caller.
 bool is_special(char c) {
   switch (c) {
@@ -379,59 +402,124 @@ bool is_special(char c) {
   }
 }
 
-int parse_query(std::string_view q, std::vector<std::string>& terms, std::vector<uint8_t>& occur, std::string& why) {
-  terms.clear();
-  occur.clear();
-  std::vector<std::string_view> words;
+// One clause of a parsed query: a term (one token) or a phrase (several, with
+// each token's position offset from the first: a token the analyzer drops in
+// between leaves a hole -- PhraseQuery::new_with_offset).
+struct Clause {
+  uint8_t occur = FG_OCCUR_SHOULD;
+  std::vector<std::string> terms;
+  std::vector<uint32_t> pos;
+};
+
+// The clauses of a query.  A literal is a word or a quoted "..." (no `\` or `"`
+// inside, nothing but white space after the closing quote: slop `~` and prefix
+// `*` suffixes are outside the subset); a word may hold `-` after its first
+// character (`e-mail`, `state-of-the-art`).  A literal that analyzes to several
+// tokens is a phrase, to one a term; to none: FG_EUNSUPPORTED, as before.
+int parse_clauses(std::string_view q, std::vector<Clause>& out, std::string& why) {
+  out.clear();
+  struct Item { std::string_view body; bool quoted; bool prefixed; uint8_t occur; };
+  std::vector<Item> items;
+  auto space = [](char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r'; };
   size_t i = 0;
   while (i < q.size()) {
-    while (i < q.size() && (q[i] == ' ' || q[i] == '\t' || q[i] == '\n' || q[i] == '\r')) ++i;
+    while (i < q.size() && space(q[i])) ++i;
+    if (i >= q.size()) break;
     size_t s = i;
-    while (i < q.size() && !(q[i] == ' ' || q[i] == '\t' || q[i] == '\n' || q[i] == '\r')) ++i;
-    if (i > s) words.push_back(q.substr(s, i - s));
-  }
-  if (words.empty()) { why = "empty query (AllQuery)"; return FG_EUNSUPPORTED; }
-  std::vector<std::pair<std::string_view, uint8_t>> raw;
-  auto binary_form = [&](std::string_view op) {
-    bool ok = words.size() >= 3 && words.size() % 2 == 1;
-    for (size_t w = 1; ok && w < words.size(); w += 2) ok = words[w] == op;
-    return ok;
-  };
-  if (binary_form("AND") || binary_form("OR")) {
-    const uint8_t oc = words[1] == "AND" ? FG_OCCUR_MUST : FG_OCCUR_SHOULD;
-    for (size_t w = 0; w < words.size(); w += 2) raw.emplace_back(words[w], oc);
-  } else {
-    for (auto w : words) {
-      if (w.size() > 1 && (w[0] == '+' || w[0] == '-'))
-        raw.emplace_back(w.substr(1), w[0] == '+' ? FG_OCCUR_MUST : FG_OCCUR_MUST_NOT);
-      else
-        raw.emplace_back(w, FG_OCCUR_SHOULD);
+    while (i < q.size() && !space(q[i])) {
+      if (q[i] == '"') {  // a quoted literal runs to its closing quote, white space included
+        const size_t close = q.find('"', i + 1);
+        if (close == std::string_view::npos) { why = "unterminated quoted literal"; return FG_EUNSUPPORTED; }
+        i = close + 1;
+      } else {
+        ++i;
+      }
     }
-  }
-  bool positive = false;
-  for (auto& [w, oc] : raw) {
-    if (w == "AND" || w == "OR" || w == "NOT" || w == "IN" || w == "TO") {
-      why = "operator outside the supported forms";
-      return FG_EUNSUPPORTED;
+    std::string_view w = q.substr(s, i - s);
+    Item it{w, false, false, FG_OCCUR_SHOULD};
+    if (w.size() > 1 && (w[0] == '+' || w[0] == '-')) {
+      it.occur = w[0] == '+' ? FG_OCCUR_MUST : FG_OCCUR_MUST_NOT;
+      it.prefixed = true;
+      w = w.substr(1);
     }
-    for (char c : w)
-      if (is_special(c)) {
-        why = "query syntax beyond bare/+/-/AND/OR terms";
+    if (w[0] == '"') {
+      const size_t close = w.find('"', 1);
+      if (close != w.size() - 1) {
+        why = "query syntax beyond bare/+/-/AND/OR terms and plain quoted phrases (slop, prefix, boost)";
         return FG_EUNSUPPORTED;
       }
-    std::vector<std::string> toks;
-    analyze(w, toks);
-    if (toks.size() != 1) {
-      why = toks.empty() ? "a term analyzes to no token" : "a term analyzes to several tokens (PhraseQuery)";
+      w = w.substr(1, w.size() - 2);
+      if (w.find('\\') != std::string_view::npos) { why = "escape inside a quoted literal"; return FG_EUNSUPPORTED; }
+      it.quoted = true;
+    }
+    it.body = w;
+    items.push_back(it);
+  }
+  if (items.empty()) { why = "empty query (AllQuery)"; return FG_EUNSUPPORTED; }
+  auto is_op = [&](const Item& it, std::string_view op) { return !it.quoted && !it.prefixed && it.body == op; };
+  auto binary_form = [&](std::string_view op) {
+    bool ok = items.size() >= 3 && items.size() % 2 == 1;
+    for (size_t w = 1; ok && w < items.size(); w += 2) ok = is_op(items[w], op);
+    return ok;
+  };
+  std::vector<Item> raw;
+  if (binary_form("AND") || binary_form("OR")) {
+    const uint8_t oc = items[1].body == "AND" ? FG_OCCUR_MUST : FG_OCCUR_SHOULD;
+    for (size_t w = 0; w < items.size(); w += 2) {
+      Item it = items[w];
+      if (it.prefixed) { why = "query syntax beyond bare/+/-/AND/OR terms"; return FG_EUNSUPPORTED; }
+      it.occur = oc;
+      raw.push_back(it);
+    }
+  } else {
+    raw = items;
+  }
+  bool positive = false;
+  for (const Item& it : raw) {
+    const std::string_view w = it.body;
+    if (!it.quoted) {
+      if (w == "AND" || w == "OR" || w == "NOT" || w == "IN" || w == "TO") {
+        why = "operator outside the supported forms";
+        return FG_EUNSUPPORTED;
+      }
+      for (size_t c = 0; c < w.size(); ++c)
+        if (is_special(w[c]) && !(w[c] == '-' && c >= 1)) {
+          why = "query syntax beyond bare/+/-/AND/OR terms";
+          return FG_EUNSUPPORTED;
+        }
+    }
+    Clause cl;
+    cl.occur = it.occur;
+    analyze(w, cl.terms, &cl.pos);
+    if (cl.terms.empty()) {
+      why = "a term analyzes to no token";
       return FG_EUNSUPPORTED;
     }
-    terms.push_back(std::move(toks[0]));
-    occur.push_back(oc);
-    positive |= oc != FG_OCCUR_MUST_NOT;
+    for (size_t j = cl.pos.size(); j-- > 0;) cl.pos[j] -= cl.pos[0];
+    positive |= cl.occur != FG_OCCUR_MUST_NOT;
+    out.push_back(std::move(cl));
   }
   if (!positive) {
     why = "MustNot clauses only";
     return FG_EUNSUPPORTED;
+  }
+  return FG_OK;
+}
+
+// The term-per-clause form (fg_parse_query, fg_parse_query_occur): their
+// outputs cannot express a phrase, so one is FG_EUNSUPPORTED here.
+int parse_query(std::string_view q, std::vector<std::string>& terms, std::vector<uint8_t>& occur, std::string& why) {
+  terms.clear();
+  occur.clear();
+  std::vector<Clause> cl;
+  if (int rc = parse_clauses(q, cl, why)) return rc;
+  for (auto& c : cl) {
+    if (c.terms.size() != 1) {
+      why = "a term analyzes to several tokens (PhraseQuery)";
+      return FG_EUNSUPPORTED;
+    }
+    terms.push_back(std::move(c.terms[0]));
+    occur.push_back(c.occur);
   }
   return FG_OK;
 }
@@ -809,6 +897,11 @@ struct Doc {
   bool has_name = false;
   bool deleted = false;
   std::vector<uint32_t> text_tok, name_tok;
+  // tokens RemoveLongFilter dropped (they still consume a position: phrase
+  // queries): per field the index in *_tok each came immediately before,
+  // ascending; null: none (nearly every doc)
+  struct Gaps { std::vector<uint32_t> text, name; };
+  std::unique_ptr<Gaps> gaps;
   std::vector<std::string> id_tokens;
   std::vector<std::string> facets;   // stored facet values, encoded (Facet), in document order
   std::vector<uint32_t> facet_tok;   // FacetTokenizer tokens of all of them (facet dictionary ids)
@@ -974,9 +1067,12 @@ bool valid_ns_name(std::string_view n) {
   return true;
 }
 
-std::vector<uint32_t> intern(Namespace& ns, std::string_view text) {
+std::vector<uint32_t> intern(Namespace& ns, std::string_view text, std::vector<uint32_t>& gaps) {
   std::vector<std::string> toks;
-  analyze(text, toks);
+  std::vector<uint32_t> pos;
+  analyze(text, toks, &pos);
+  gaps.clear();
+  gaps_of(pos, gaps);
   std::vector<uint32_t> ids;
   ids.reserve(toks.size());
   for (auto& t : toks) ids.push_back(ns.dict.get(t));
@@ -1046,11 +1142,23 @@ int search_hits(fg_db* db, Namespace& ns, const char* query, const std::vector<s
   const std::string_view qv = query ? query : "";
   std::vector<std::string> terms;
   std::vector<uint8_t> occur;
+  std::vector<uint32_t> plen, ppos;  // fg_query_batch::phrase_len / phrase_pos
+  bool any_phrase = false;
   std::string why;
   const bool empty_text = blank(qv);  // query.trim().is_empty() -> AllQuery (src/db/search.rs:115-116)
   if (!empty_text) {
-    int rc = parse_query(qv, terms, occur, why);
+    std::vector<Clause> cls;
+    int rc = parse_clauses(qv, cls, why);
     if (rc) return hfail(rc, "query outside the device subset: " + why);
+    for (Clause& c : cls) {
+      any_phrase |= c.terms.size() > 1;
+      for (size_t j = 0; j < c.terms.size(); ++j) {
+        terms.push_back(std::move(c.terms[j]));
+        occur.push_back(c.occur);
+        plen.push_back(j == 0 ? (uint32_t)c.terms.size() : 0u);
+        ppos.push_back(c.pos[j]);
+      }
+    }
   }
   std::vector<std::string> clauses;
   bool facet_all = false;
@@ -1087,6 +1195,10 @@ int search_hits(fg_db* db, Namespace& ns, const char* query, const std::vector<s
   const uint32_t q_off[2] = {0, (uint32_t)ids.size()};
   const uint32_t f_off[2] = {0, (uint32_t)fids.size()};
   fg_query_batch qb{1, q_off, ids.data(), FG_MODE_AND, fids.empty() ? nullptr : f_off, fids.data(), occur.data()};
+  if (any_phrase) {
+    qb.phrase_len = plen.data();
+    qb.phrase_pos = ppos.data();
+  }
   std::vector<float> sc(limit);
   std::vector<uint32_t> dc(limit), sh(limit);
   uint32_t n = 0;
@@ -1413,8 +1525,12 @@ int upsert_record(fg_db* db, const char* nsname, const fg_object_record* r, cons
       ns->docs[d].deleted = true;
       ns->del[d] = 1;
     }
-  doc.text_tok = intern(*ns, doc.text);
-  if (doc.has_name) doc.name_tok = intern(*ns, doc.name);
+  {
+    Doc::Gaps g;
+    doc.text_tok = intern(*ns, doc.text, g.text);
+    if (doc.has_name) doc.name_tok = intern(*ns, doc.name, g.name);
+    if (!g.text.empty() || !g.name.empty()) doc.gaps = std::make_unique<Doc::Gaps>(std::move(g));
+  }
   doc.facet_tok = intern_facet(*ns, doc.facets);
   analyze(doc.id, doc.id_tokens);
   const uint32_t d = (uint32_t)ns->docs.size();
@@ -1567,13 +1683,30 @@ struct Stats {
   }
 };
 
+// FUGU_POSITIONS=0: segments are built without the forward index (4 B per token
+// position of device memory saved); phrase queries are then FG_EUNSUPPORTED
+bool positions_on() {
+  static const bool on = [] {
+    const char* e = getenv("FUGU_POSITIONS");
+    return !(e && e[0] == '0' && e[1] == 0);
+  }();
+  return on;
+}
+
 // The docs `ids` (global, in order) as fg_docs_input arrays
 struct DocsBuf {
   std::vector<uint64_t> toff{0}, noff{0}, foff{0};
   std::vector<uint32_t> ttok, ntok, ftok;
+  std::vector<uint64_t> tgap, ngap;  // fg_docs_input::text_gap / name_gap
   std::vector<uint8_t> del;
   bool any_name = false, any_del = false;
   void add(const Doc& d, bool deleted) {
+    if (d.gaps) {  // (a token dropped after the doc's last kept one is not listed: no phrase reaches it)
+      for (uint32_t g : d.gaps->text)
+        if (g < d.text_tok.size()) tgap.push_back(ttok.size() + g);
+      for (uint32_t g : d.gaps->name)
+        if (g < d.name_tok.size()) ngap.push_back(ntok.size() + g);
+    }
     ttok.insert(ttok.end(), d.text_tok.begin(), d.text_tok.end());
     ntok.insert(ntok.end(), d.name_tok.begin(), d.name_tok.end());
     ftok.insert(ftok.end(), d.facet_tok.begin(), d.facet_tok.end());
@@ -1598,6 +1731,11 @@ struct DocsBuf {
     in.n_facet_terms = n_fterms;
     in.facet_off = n_fterms ? foff.data() : nullptr;
     in.facet_tok = n_fterms ? ftok.data() : nullptr;
+    in.keep_positions = positions_on() ? 1 : 0;
+    in.text_gap = tgap.empty() ? nullptr : tgap.data();
+    in.n_text_gap = tgap.size();
+    in.name_gap = with_name && !ngap.empty() ? ngap.data() : nullptr;
+    in.n_name_gap = with_name ? ngap.size() : 0;
     return in;
   }
 };
@@ -2239,13 +2377,18 @@ int fg_db_upsert_batch(fg_db* db, const char* nsname, uint32_t n, const char* id
   run_threads((size_t)T, (size_t)T, [&](size_t t) {
     const uint32_t b = (uint32_t)((uint64_t)n * t / T), e = (uint32_t)((uint64_t)n * (t + 1) / T);
     std::vector<std::string> toks;
+    std::vector<uint32_t> gaps;
     std::string scratch;
     for (uint32_t i = b; i < e; ++i) {
       Doc& d = docs[i];
       d.id = std::string(sv(ids, id_off, i));
       d.text = std::string(sv(texts, text_off, i));
       // thread-local term ids until the merge
-      analyze_each(d.text, scratch, toks, [&](std::string_view w) { d.text_tok.push_back(ldict[t].get(w)); });
+      analyze_each(d.text, scratch, toks, gaps, [&](std::string_view w) { d.text_tok.push_back(ldict[t].get(w)); });
+      if (!gaps.empty()) {
+        d.gaps = std::make_unique<Doc::Gaps>();
+        d.gaps->text = gaps;
+      }
       analyze(d.id, d.id_tokens);
     }
     const uint32_t ne = (uint32_t)ldict[t].ent.size();
@@ -2469,6 +2612,25 @@ int fg_parse_query(const char* query, int* mode, char* out, size_t cap, size_t* 
   for (size_t i = 0; i < terms.size(); ++i) {
     if (i) o.push_back('\n');
     o += terms[i];
+  }
+  return copy_out(o, out, cap, len);
+}
+
+int fg_parse_query_clauses(const char* query, char* out, size_t cap, size_t* len) {
+  if (!query) return hfail(FG_EINVAL, "bad arguments");
+  std::vector<Clause> cls;
+  std::string why;
+  int rc = parse_clauses(query, cls, why);
+  if (rc) return hfail(rc, why);
+  std::string o;
+  for (size_t i = 0; i < cls.size(); ++i) {
+    if (i) o.push_back('\n');
+    o.push_back((char)('0' + cls[i].occur));
+    o.push_back(':');
+    for (size_t j = 0; j < cls[i].terms.size(); ++j) {
+      if (j) o.push_back(' ');
+      o += cls[i].terms[j] + "@" + std::to_string(cls[i].pos[j]);
+    }
   }
   return copy_out(o, out, cap, len);
 }

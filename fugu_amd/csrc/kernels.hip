@@ -1963,6 +1963,153 @@ __global__ __launch_bounds__(kThreads) void k_scan(DevIndex ix0, DevPlan pl) {
   flush_candidates(pl, q, sh.buf, sh.n_buf, sh.thr, sh.scratch);
 }
 
+// ---------------------------------------------------------------- k_phrase
+// Phrase queries (tantivy PhraseQuery at slop 0): a work item is
+// a group of kChunk-posting chunks of the phrase's LEAD list (its distinct term
+// with the shortest list).  Per chunk:
+//  (a) every lane takes kItems lead docs, drops the deleted ones and those some
+//      other distinct term of the phrase lacks (term_has_doc: rank words, sparse
+//      rank words or the bucket directory), and queues the survivors -- doc and
+//      the lead posting's tf / fieldnorm payload -- in LDS;
+//  (b) one wave per survivor verifies it against the forward index: the lanes
+//      stride over the doc's positions (coalesced), test the anchor term first
+//      and the other offsets only on an anchor hit, never reading outside the
+//      doc's [fwd_off[d], fwd_off[d + 1]); the lanes' counts are summed over the
+//      wave, per field;
+//  (c) the score is field_score with the phrase count in place of tf, per field
+//      with a count, text then name from 0.0; keys go through k_scan's local
+//      top-k buffer, threshold word and flush (scan_truncate: pub_mask and the
+//      peers keep their contract; a key below the published k-th is dropped);
+//  (d) pruning: in (a) a survivor whose score bound -- field_score at the lead
+//      posting's own tf, which no phrase count exceeds -- is below the threshold
+//      read at the chunk's start is not queued.
+struct PhraseShared {
+  ScanShared s;
+  uint64_t queue[kChunk];      // survivors: (lead posting's tfn | tfn_name << 16) << 32 | doc
+  uint32_t n_q;
+  uint32_t pterm[kMaxTerms];   // DevPlan::q_pterm / q_ppos of the slot (anchor first)
+  uint32_t ppos[kMaxTerms];
+  uint32_t tmeta[kMaxTerms];   // the other distinct terms' probe tables
+  uint32_t tdir[kMaxTerms];
+  uint64_t toff[kMaxTerms];
+};
+
+// Occurrences of the phrase in positions [b0, b1) of one field's forward index
+// (one wave; the result is the same in every lane)
+__device__ inline uint32_t phrase_count(const uint32_t* __restrict__ fwd, uint64_t b0, uint64_t b1,
+                                        const PhraseShared& sh, uint32_t n, uint32_t span) {
+  const uint64_t len = b1 - b0;
+  uint32_t c = 0;
+  if (len > span) {
+    const uint64_t starts = len - span;  // phrase starts p with p + span inside the doc
+    const uint32_t a_pos = sh.ppos[0], a_term = sh.pterm[0];
+    for (uint64_t p = lane_id(); p < starts; p += 64) {
+      if (fwd[b0 + p + a_pos] != a_term) continue;
+      bool ok = true;
+      for (uint32_t j = 1; j < n && ok; ++j) ok = fwd[b0 + p + sh.ppos[j]] == sh.pterm[j];
+      c += ok ? 1u : 0u;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o, 64);
+  return c;
+}
+
+template <bool kMulti>
+__global__ __launch_bounds__(kThreads) void k_phrase(DevIndex ix0, DevPlan pl) {
+  __shared__ PhraseShared sh;
+  const uint32_t tid = threadIdx.x, lane = lane_id();
+  const uint32_t w = pl.total_chunks + pl.n_scan + blockIdx.x;  // phrase items follow the k_scan items
+  const uint32_t q = pl.work_q[w];
+  const DevIndex ix = kMulti ? seg_index(pl, __builtin_amdgcn_readfirstlane(q / pl.seg_nq)) : ix0;
+  const uint32_t ql = kMulti ? __builtin_amdgcn_readfirstlane(q % pl.seg_nq) : q;
+  const uint32_t chunk0 = pl.work_c[w], nchunk = pl.work_n[w];
+  const uint32_t K = pl.k;
+  uint64_t* gthr = &pl.thresh[ql];
+  const uint32_t qm = pl.q_m[q];
+  const uint32_t nd = min(qm_terms(qm), kMaxTerms), np = min(qm_phrase_terms(qm), kMaxTerms);
+  const size_t row = (size_t)q * kMaxTerms;
+  const uint32_t lead = pl.q_terms[row];
+  const uint64_t base = ix.off[lead];
+  const uint32_t df = pl.q_lead_df[q];
+  const float wt = pl.q_wt[row], wn = pl.q_wn[row];
+  if (tid < np) {
+    sh.pterm[tid] = pl.q_pterm[row + tid];
+    sh.ppos[tid] = pl.q_ppos[row + tid];
+  }
+  if (tid >= 1 && tid < nd) {
+    const uint32_t t = pl.q_terms[row + tid];
+    sh.tmeta[tid] = ix.tmeta[t];
+    sh.tdir[tid] = ix.dir_off[t];
+    sh.toff[tid] = ix.off[t];
+  }
+  if (tid == 0) {
+    sh.s.n_buf = 0;
+    sh.n_q = 0;
+    sh.s.thr = atomicMax(reinterpret_cast<unsigned long long*>(gthr), 0ull);
+  }
+  __syncthreads();
+  uint32_t span = 0;  // the phrase's largest offset
+  for (uint32_t j = 0; j < np; ++j) span = max(span, sh.ppos[j]);
+  const bool name = ix.tfn_name != nullptr && ix.fwd_off_name != nullptr;
+  for (uint32_t c = 0; c < nchunk; ++c) {
+    // (a) the chunk's lead docs that are alive and hold every other distinct term
+    const uint32_t i0 = (chunk0 + c) * kChunk;
+    const uint64_t thr_a = sh.s.thr;  // (uniform: written before the last barrier)
+    for (uint32_t j = 0; j < kItems; ++j) {
+      const uint32_t i = i0 + j * kThreads + tid;
+      bool keep = i < df;
+      uint32_t d = 0;
+      if (keep) {
+        d = ix.doc[base + i];
+        keep = doc_alive(ix, d);
+      }
+      for (uint32_t u = 1; u < nd; ++u)
+        if (keep) keep = term_has_doc(ix, sh.tmeta[u], sh.toff[u], sh.tdir[u], d);
+      uint32_t v = 0;
+      if (keep) {
+        v = ix.tfn[base + i];
+        if (name) v |= (uint32_t)ix.tfn_name[base + i] << 16;
+        // (d) a field's phrase count is at most the lead term's tf there, and field_score rises with
+        // the count (correctly rounded f32 operations are monotone; an escaped tf byte: the weight
+        // itself): a survivor whose bound is below the published k-th key is not verified
+        const uint32_t tt = v & 0xFFu, tn = (v >> 16) & 0xFFu;
+        float ub = 0.0f;
+        if (tt) ub += tt == kTfEsc ? wt : field_score(tt, (v >> 8) & 0xFFu, wt, ix.cache);
+        if (tn) ub += tn == kTfEsc ? wn : field_score(tn, v >> 24, wn, ix.cache + 256);
+        keep = make_key(ub, d) >= thr_a;
+      }
+      wave_append(keep, ((uint64_t)v << 32) | d, sh.queue, &sh.n_q, kChunk);
+    }
+    __syncthreads();
+    // (b), (c) one wave per survivor, kRound survivors between truncations
+    const uint32_t nsv = min(sh.n_q, kChunk);
+    for (uint32_t r0 = 0; r0 < nsv; r0 += kRound) {
+      const uint64_t thr = sh.s.thr;
+      const uint32_t r1 = min(nsv, r0 + kRound);
+      for (uint32_t x = r0 + wave_id(); x < r1; x += kThreads / 64) {
+        const uint64_t e = sh.queue[x];
+        const uint32_t d = __builtin_amdgcn_readfirstlane((uint32_t)e);
+        const uint32_t v = __builtin_amdgcn_readfirstlane((uint32_t)(e >> 32));
+        uint32_t ct = 0, cn = 0;
+        if (v & 0xFFu) ct = phrase_count(ix.fwd, ix.fwd_off[d], ix.fwd_off[d + 1], sh, np, span);
+        if (name && ((v >> 16) & 0xFFu))
+          cn = phrase_count(ix.fwd_name, ix.fwd_off_name[d], ix.fwd_off_name[d + 1], sh, np, span);
+        float sc = 0.0f;
+        if (ct) sc += field_score(ct, (v >> 8) & 0xFFu, wt, ix.cache);
+        if (cn) sc += field_score(cn, v >> 24, wn, ix.cache + 256);
+        const uint64_t key = make_key(sc, d);
+        wave_append(lane == 0 && (ct | cn) != 0 && key >= thr, key, sh.s.buf, &sh.s.n_buf, kBufD);
+      }
+      __syncthreads();
+      scan_truncate(sh.s, K, kTrunc, gthr, false, pl.pub_mask, pl, ql);
+    }
+    if (tid == 0) sh.n_q = 0;
+    scan_truncate(sh.s, K, K, gthr, true, pl.pub_mask, pl, ql);
+  }
+  flush_candidates(pl, q, sh.s.buf, sh.s.n_buf, sh.s.thr, sh.s.scratch);
+}
+
 // ---------------------------------------------------------------- k_final
 // Dynamic LDS (80 KB: 2 workgroups per CU): candidate keys, the k winners,
 // the radix histogram.  Keeps 16-B alignment of the dynamic base (no static
@@ -2282,6 +2429,13 @@ hipError_t launch_scan(const DevIndex& ix, const DevPlan& pl, hipStream_t s) {
   if (pl.n_scan == 0) return hipSuccess;
   if (pl.segs) k_scan<true><<<pl.n_scan, kThreads, 0, s>>>(ix, pl);
   else k_scan<false><<<pl.n_scan, kThreads, 0, s>>>(ix, pl);
+  return hipGetLastError();
+}
+
+hipError_t launch_phrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s) {
+  if (pl.n_phrase == 0) return hipSuccess;
+  if (pl.segs) k_phrase<true><<<pl.n_phrase, kThreads, 0, s>>>(ix, pl);
+  else k_phrase<false><<<pl.n_phrase, kThreads, 0, s>>>(ix, pl);
   return hipGetLastError();
 }
 

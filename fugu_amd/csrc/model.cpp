@@ -539,6 +539,10 @@ extern "C" {
 int fg_model_batch(const fg_index* ix, const fg_query_batch* q, uint32_t k, const float* thr_score, double* per_query,
                    fg_model_out* out) {
   if (!ix || !q || !out || (q->n_queries && !q->q_off) || k == 0) return fail(FG_EINVAL, "bad arguments");
+  // phrase clauses (k_phrase) are not modelled
+  if (q->phrase_len)
+    for (uint32_t j = q->n_queries ? q->q_off[0] : 0; q->n_queries && j < q->q_off[q->n_queries]; ++j)
+      if (q->phrase_len[j] != 1) return fail(FG_EINVAL, "bad query batch (the model does not cover phrase queries)");
   if (!ix->h_doc && ix->n_postings) return fail(FG_EINVAL, "index built without keep_host_postings");
   Snap S;
   if (int rc = S.load(ix)) return rc;
@@ -618,6 +622,10 @@ int fg_model_batch(const fg_index* ix, const fg_query_batch* q, uint32_t k, cons
 // per probed 128-posting block), per query
 int fg_bytes_model(const fg_index* ix, const fg_query_batch* q, uint32_t k, double* out) {
   if (!ix || !q || !out) return fail(FG_EINVAL, "bad arguments");
+  // phrase clauses (k_phrase) are not modelled
+  if (q->phrase_len)
+    for (uint32_t j = q->n_queries ? q->q_off[0] : 0; q->n_queries && j < q->q_off[q->n_queries]; ++j)
+      if (q->phrase_len[j] != 1) return fail(FG_EINVAL, "bad query batch (the model does not cover phrase queries)");
   if (!ix->h_doc && ix->n_postings) return fail(FG_EINVAL, "index built without keep_host_postings");
   const double F = ix->has_name ? 2.0 : 1.0;
   std::vector<uint32_t> S;

@@ -42,6 +42,7 @@ struct WItem { double key; uint32_t q, c, n; };
 struct PlanTables {
   // per query (slot); the q_terms .. q_rup rows hold kMaxTerms entries each
   std::vector<uint32_t> q_m, q_terms, lead, q_filter, ngroup, q_hlo, q_hhi, q_hsh;
+  std::vector<uint32_t> q_pterm, q_ppos;  // phrase queries' (term, offset) rows; empty without phrase_len
   std::vector<uint64_t> thr0;
   std::vector<float> q_ub, q_wt, q_wn, q_rup;
   // facet filters (fg_internal.h DevFilters) and the chunks of their postings
@@ -50,18 +51,97 @@ struct PlanTables {
   std::vector<uint64_t> f_woff;
   std::vector<float> f_tab, f_max;
   std::vector<uint32_t> ch_f, ch_c, ch_t, ch_s;
-  // work items: k_conj's, k_disj's, k_scan's; items: all of them as the kernels
-  // run them (order_items, joined tables only)
-  std::vector<WItem> citems, ditems, scan, items;
+  // work items: k_conj's, k_disj's, k_scan's, k_phrase's; items: all of them as
+  // the kernels run them (order_items, joined tables only)
+  std::vector<WItem> citems, ditems, scan, phrase, items;
   // (a thread's plans reuse one set: assign / push_back into kept capacity, no
   // page faults on fresh arrays -- ~0.2 ms of an 8-snapshot batch's planning)
   void clear() {
     auto all = [](auto&... v) { (v.clear(), ...); };
     all(q_m, q_terms, lead, q_filter, ngroup, q_hlo, q_hhi, q_hsh, thr0, q_ub, q_wt, q_wn, q_rup, f_shift, f_seg, f_woff,
-        f_tab, f_max, ch_f, ch_c, ch_t, ch_s, citems, ditems, scan, items);
+        f_tab, f_max, ch_f, ch_c, ch_t, ch_s, citems, ditems, scan, phrase, items, q_pterm, q_ppos);
     nf = 0;
   }
 };
+
+// Query i of the batch when it holds a phrase clause (fg_query_batch::phrase_len
+// >= 2; *phrase = 0 otherwise, after checking the clause table): the device
+// subset -- the phrase is the query's only clause, no facet clauses, a snapshot
+// with positions -- or FG_EUNSUPPORTED naming the reason.  The slot's rows:
+// q_terms the phrase's distinct terms (the snapshot's ids), the lead -- the
+// shortest merged list -- first; q_pterm / q_ppos the (vocabulary id, offset)
+// list, the anchor (the first occurrence of the term with the fewest postings)
+// first; q_wt[0] / q_wn[0] the field weights, Bm25Weight::for_terms: the terms'
+// idfs summed in phrase order from 0.0 (a repeated term each time), times
+// (1 + K1).  Work items (k_phrase): groups of the lead list's chunks, as k_conj's.
+int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t nq_size, uint32_t n_segs,
+                PlanTables& h, int* phrase) {
+  *phrase = 0;
+  const uint32_t b = q->q_off[i], e = q->q_off[i + 1], m = e - b;
+  uint32_t n_clauses = 0, n_phr = 0;
+  for (uint32_t j = b; j < e;) {
+    const uint32_t n = q->phrase_len[j];
+    if (n == 0 || n > e - j) return fail(FG_EINVAL, "query %u: bad phrase_len at term %u", i, j - b);
+    for (uint32_t x = 1; x < n; ++x)
+      if (q->phrase_len[j + x] != 0) return fail(FG_EINVAL, "query %u: phrase_len inside a phrase must be 0", i);
+    if (n >= 2) {
+      if (q->phrase_pos[j] != 0) return fail(FG_EINVAL, "query %u: a phrase's first offset must be 0", i);
+      for (uint32_t x = 1; x < n; ++x)
+        if (q->phrase_pos[j + x] <= q->phrase_pos[j + x - 1])
+          return fail(FG_EINVAL, "query %u: phrase offsets must increase", i);
+      ++n_phr;
+    }
+    ++n_clauses;
+    j += n;
+  }
+  if (!n_phr) return FG_OK;
+  *phrase = 1;
+  if (n_clauses > 1) return fail(FG_EUNSUPPORTED, "query %u: phrase clause beside other clauses", i);
+  if (q->f_off && q->f_off[i + 1] > q->f_off[i]) return fail(FG_EUNSUPPORTED, "query %u: phrase with facet filters", i);
+  if (!ix->has_positions) return fail(FG_EUNSUPPORTED, "query %u: snapshot built without positions", i);
+  if (q->phrase_pos[e - 1] >= (1u << 30)) return fail(FG_EINVAL, "query %u: phrase offset too large", i);
+  const uint8_t oc = q->occur ? q->occur[b] : (q->mode == FG_MODE_OR ? FG_OCCUR_SHOULD : FG_OCCUR_MUST);
+  if (oc > FG_OCCUR_MUST_NOT) return fail(FG_EINVAL, "query %u: bad occur %u", i, (unsigned)oc);
+  if (oc == FG_OCCUR_MUST_NOT) return FG_OK;  // no positive clause: no hits
+  // the terms in this snapshot; one it lacks: no hits here
+  uint32_t lt[fg::kMaxTerms], dist[fg::kMaxTerms], nd = 0;
+  float it = 0.0f, in = 0.0f;
+  for (uint32_t j = 0; j < m; ++j) {
+    const uint32_t t = lt[j] = fgh::local_term(ix, q->terms[b + j]);
+    if (!(t < ix->n_terms && ix->off[t + 1] > ix->off[t])) return FG_OK;
+    it += ix->idf_text[t];
+    in += ix->idf_name[t];
+    if (std::find(dist, dist + nd, t) == dist + nd) dist[nd++] = t;
+  }
+  auto len = [&](uint32_t t) { return ix->off[t + 1] - ix->off[t]; };
+  const uint32_t lead = *std::min_element(dist, dist + nd, [&](uint32_t x, uint32_t y) { return len(x) < len(y); });
+  const size_t row = (size_t)i * fg::kMaxTerms;
+  uint32_t* qt = h.q_terms.data() + row;
+  qt[0] = lead;
+  for (uint32_t j = 0, o = 1; j < nd; ++j)
+    if (dist[j] != lead) qt[o++] = dist[j];
+  const uint32_t anchor = (uint32_t)(std::find(lt, lt + m, lead) - lt);
+  for (uint32_t j = 0, o = 1; j < m; ++j) {
+    const uint32_t at = j == anchor ? 0 : o++;
+    h.q_pterm[row + at] = q->terms[b + j];
+    h.q_ppos[row + at] = q->phrase_pos[b + j];
+  }
+  h.q_m[i] = fg::qm_phrase(nd, m);
+  h.q_wt[row] = it * (1.0f + 1.2f);  // (1 + K1), as bm25_weight's
+  h.q_wn[row] = in * (1.0f + 1.2f);
+  const uint64_t df0 = len(lead);
+  h.lead[i] = (uint32_t)df0;
+  const uint32_t nch = (uint32_t)((df0 + fg::kChunk - 1) / fg::kChunk);
+  if (h.phrase.size() + nch > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "batch too large (%zu work items)", h.phrase.size());
+  const uint32_t cdiv = n_segs <= 1 ? 1u : n_segs;
+  const uint32_t per_q = std::max<uint32_t>(
+      1, std::min<uint32_t>(64, std::max<uint32_t>(fg::kConjGroupsPerQuery, 1024 / std::max(nq_size, 1u))) / cdiv);
+  const uint32_t G = std::min<uint32_t>(fg::kPhraseMaxGroup, std::max<uint32_t>(1, (nch + per_q - 1) / per_q));
+  const uint32_t ng = (nch + G - 1) / G;
+  h.ngroup[i] = ng;
+  for (uint32_t g = 0; g < ng; ++g) h.phrase.push_back(WItem{(g + 0.5) / ng, i, g * G, std::min(G, nch - g * G)});
+  return FG_OK;
+}
 
 // n_segs: the snapshots the plan spans; a query's work items are spread over
 // all of them, so each snapshot gets its share of the per-query item counts.
@@ -86,6 +166,11 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
   h.thr0.assign(nq, 0);
   for (auto* v : {&h.q_ub, &h.q_wt, &h.q_wn}) v->assign(nqt, 0.0f);
   h.q_rup.assign(nqt, 1.0f);
+  if (q->phrase_len) {
+    if (!q->phrase_pos) return fail(FG_EINVAL, "phrase_len without phrase_pos");
+    h.q_pterm.assign(nqt, 0);
+    h.q_ppos.assign(nqt, 0);
+  }
 
   // ---- facet filters: one mask per distinct clause list (fg_internal.h DevFilters)
   h.q_filter.assign(nq, 0xFFFFFFFFu);
@@ -201,6 +286,11 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
     if (e < b) return fail(FG_EINVAL, "q_off not monotone at query %u", i);
     const uint32_t m = e - b;
     if (m > fg::kMaxTerms) return fail(FG_EUNSUPPORTED, "query %u has %u terms (> %u)", i, m, fg::kMaxTerms);
+    if (q->phrase_len) {
+      int phrase = 0;
+      if (int rc = plan_phrase(ix, q, i, nq_size, n_segs, h, &phrase)) return rc;
+      if (phrase) continue;
+    }
     if (q_nomatch[i]) continue;  // the facet clauses match nothing: no hits
     const uint32_t flt = h.q_filter[i];
     const float fmx = flt == 0xFFFFFFFFu ? 0.0f : h.f_max[flt];
@@ -392,6 +482,8 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
   J.thr0.resize(nq);
   J.q_terms.resize(nqt);
   for (auto* v : {&J.q_ub, &J.q_wt, &J.q_wn, &J.q_rup}) v->resize(nqt);
+  if (q->phrase_len)
+    for (auto* v : {&J.q_pterm, &J.q_ppos}) v->resize(nqt);
   auto put_slot = [&](uint32_t p) {  // piece p's per-query tables into its slots
     const PlanTables& h = hs[p];
     const size_t v0 = pc.slot(p), t0 = v0 * fg::kMaxTerms;
@@ -399,6 +491,7 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
     cp(J.q_m, h.q_m, v0); cp(J.lead, h.lead, v0); cp(J.ngroup, h.ngroup, v0); cp(J.thr0, h.thr0, v0);
     cp(J.q_terms, h.q_terms, t0);
     cp(J.q_ub, h.q_ub, t0); cp(J.q_wt, h.q_wt, t0); cp(J.q_wn, h.q_wn, t0); cp(J.q_rup, h.q_rup, t0);
+    cp(J.q_pterm, h.q_pterm, t0); cp(J.q_ppos, h.q_ppos, t0);  // (empty without phrase_len)
   };
   if (par) {
     std::vector<int> rcs(n, FG_OK);
@@ -449,6 +542,7 @@ PlanTables& join_pieces(const Pieces& pc, std::vector<PlanTables>& hs, PlanTable
     for (WItem x : h.citems) { x.q += vb; J.citems.push_back(x); }
     for (WItem x : h.ditems) { x.q += vb; J.ditems.push_back(x); }
     for (WItem x : h.scan) { x.q += vb; J.scan.push_back(x); }
+    for (WItem x : h.phrase) { x.q += vb; J.phrase.push_back(x); }
     J.nf += h.nf;
   }
   // one bin geometry per batch query over the snapshots where it has work
@@ -564,19 +658,20 @@ void sort_sweep(std::vector<WItem>& items, bool conj, const PlanTables& t, uint3
 struct WorkList {
   std::vector<uint32_t> work_q, work_c, work_n;
   std::vector<uint64_t> cand_off;
-  uint64_t n_single = 0, n_conj = 0, n_main = 0, n_scan = 0;
-  uint64_t count() const { return n_main + n_scan; }
+  uint64_t n_single = 0, n_conj = 0, n_main = 0, n_scan = 0, n_phrase = 0;
+  uint64_t count() const { return n_main + n_scan + n_phrase; }
 };
 
 int order_items(PlanTables& t, uint32_t nq, uint32_t k, WorkList& w) {
   if (t.f_woff[t.nf] * 4 > (8ull << 30)) return fail(FG_EUNSUPPORTED, "facet masks of this batch exceed 8 GiB");
   if (t.ch_f.size() > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "facet postings of this batch too large");
-  if (t.citems.size() + t.ditems.size() + t.scan.size() > 0x7FFFFFFFull)
-    return fail(FG_EUNSUPPORTED, "batch too large (%zu work items)", t.citems.size() + t.ditems.size() + t.scan.size());
+  if (t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() > 0x7FFFFFFFull)
+    return fail(FG_EUNSUPPORTED, "batch too large (%zu work items)",
+                t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size());
   sort_sweep(t.citems, true, t, nq);
   sort_sweep(t.ditems, false, t, nq);
   auto& items = t.items;
-  items.reserve(t.citems.size() + t.ditems.size() + t.scan.size());
+  items.reserve(t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size());
   items.insert(items.end(), t.citems.begin(), t.citems.end());
   w.n_conj = t.citems.size();
   items.insert(items.end(), t.ditems.begin(), t.ditems.end());
@@ -585,9 +680,13 @@ int order_items(PlanTables& t, uint32_t nq, uint32_t k, WorkList& w) {
   std::stable_sort(t.scan.begin(), t.scan.end(), [](const WItem& a, const WItem& b) { return a.key < b.key; });
   w.n_main = items.size();
   w.n_scan = t.scan.size();
-  const uint64_t chunks = w.count();  // work items (k_conj / k_disj, then k_scan)
+  // k_phrase: each query's lead chunks in list order, the queries side by side (a sweep, as k_conj's)
+  std::stable_sort(t.phrase.begin(), t.phrase.end(), [](const WItem& a, const WItem& b) { return a.key < b.key; });
+  w.n_phrase = t.phrase.size();
+  const uint64_t chunks = w.count();  // work items (k_conj / k_disj, then k_scan, then k_phrase)
   if (chunks > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "batch too large (%llu work items)", (unsigned long long)chunks);
   items.insert(items.end(), t.scan.begin(), t.scan.end());
+  items.insert(items.end(), t.phrase.begin(), t.phrase.end());
   w.work_q.resize(chunks);
   w.work_c.resize(chunks);
   w.work_n.resize(chunks);
@@ -659,7 +758,7 @@ int stage_and_upload(fg_plan* p, fg_index* const* ixs, PlanTables& t, const Work
   }
   // one allocation: [inputs | zeroed (thresh, cand_cnt, facet masks, hist) | candidates | outputs | diagnostics]
   Layout L;
-  L.regions.reserve(40);
+  L.regions.reserve(48);
   fg::DevPlan& d = p->d;
   std::vector<fg::DevIndex> segs(S > 1 ? S : 0);  // (filled once the caches' addresses are known)
   L.in(d.q_m, t.q_m.data(), 4ull * nq);
@@ -674,6 +773,8 @@ int stage_and_upload(fg_plan* p, fg_index* const* ixs, PlanTables& t, const Work
   L.in(d.q_wt, t.q_wt.data(), 4 * nqt);
   L.in(d.q_wn, t.q_wn.data(), 4 * nqt);
   L.in(d.q_rup, t.q_rup.data(), 4 * nqt);
+  L.in(d.q_pterm, t.q_pterm.data(), 4 * t.q_pterm.size());
+  L.in(d.q_ppos, t.q_ppos.data(), 4 * t.q_ppos.size());
   const size_t o_cache = L.add(4ull * 512 * S);  // (room for S even when fewer distinct caches are stored)
   L.in(d.f.q_filter, t.q_filter.data(), 4ull * nq);
   L.in(d.f.f_shift, t.f_shift.data(), 4ull * nf);
@@ -775,6 +876,7 @@ void fill_view(fg_plan* p, fg_index* const* ixs, PlanTables& t, const WorkList& 
   p->d.total_chunks = (uint32_t)w.n_main;
   p->d.n_conj = (uint32_t)w.n_conj;
   p->d.n_scan = (uint32_t)w.n_scan;
+  p->d.n_phrase = (uint32_t)w.n_phrase;
   p->d.n_single = (uint32_t)w.n_single;
   p->d.k = p->k;
   p->d.seg_nq = S > 1 ? nq1 : 0;

@@ -28,7 +28,7 @@ HOST_EXPORTS = (
     "fg_db_search", "fg_db_search_json", "fg_analyze", "fg_parse_query", "fg_parse_query_occur",
     "fg_db_upsert_record", "fg_db_upsert_batch", "fg_db_search_ex", "fg_db_search_json_ex", "fg_db_doc_facets", "fg_facet_tokens",
     "fg_facet_clauses", "fg_db_search_json_post", "fg_db_merge_wait", "fg_db_merge_info_get", "fg_db_segment_docs",
-    "fg_search_trace", "fg_merge_policy_pick",
+    "fg_search_trace", "fg_merge_policy_pick", "fg_parse_query_clauses",
 )
 SEARCH_PHASES = ("parse_dict", "plan", "launch", "wait_kernels_d2h", "json_fetch", "total")  # FG_SEARCH_PHASES
 
@@ -91,6 +91,7 @@ _sig("fg_search_trace", C.c_int, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.
 _sig("fg_merge_policy_pick", C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
 _sig("fg_parse_query", _s, C.POINTER(C.c_int), _s, _sz, C.POINTER(_sz))
 _sig("fg_parse_query_occur", _s, _s, _sz, C.POINTER(_sz))
+_sig("fg_parse_query_clauses", _s, _s, _sz, C.POINTER(_sz))
 
 
 class NotFound(native.FuguError):
@@ -190,6 +191,17 @@ def parse_query_occur(query: str):
     """[(occur, term)] with occur native.OCCUR_MUST / OCCUR_SHOULD / OCCUR_MUST_NOT."""
     out = _string_call(_lib.fg_parse_query_occur, query.encode())
     return [(int(x[0]), x[2:]) for x in out.split("\n")]
+
+
+def parse_query_clauses(query: str):
+    """[(occur, [(term, pos), ...])]: the query's clauses, a term clause one (term, 0),
+    a phrase its tokens with their position offsets (fg_parse_query_clauses)."""
+    out = _string_call(_lib.fg_parse_query_clauses, query.encode())
+    clauses = []
+    for line in out.split("\n"):
+        pairs = [x.rsplit("@", 1) for x in line[2:].split(" ")]
+        clauses.append((int(line[0]), [(t, int(p)) for t, p in pairs]))
+    return clauses
 
 
 @dataclass

@@ -63,7 +63,7 @@ LADDER_KS = (1, 2, 3, 5, 10, 13, 20, 25, 50, 100, 125, 250, 500, 1000)  # FG_LAD
 KTH_KS = (1, 10, 20, 100, 1000)  # fg_index_term_kth / fg_index_set_kth_floor ranks
 HIST_BINS = 512  # fugu.h FG_HIST_BINS: score-histogram bins per query
 MAX_PEERS = 15  # fugu.h FG_MAX_PEERS
-ABI_VERSION = 5  # include/fugu.h FG_ABI_VERSION this binding's structs follow
+ABI_VERSION = 6  # include/fugu.h FG_ABI_VERSION this binding's structs follow
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
@@ -85,7 +85,8 @@ class DocsInput(C.Structure):
     _fields_ = [("n_docs", C.c_uint32), ("n_terms", C.c_uint32), ("text_off", _u64p), ("text_tok", _u32p),
                 ("name_off", _u64p), ("name_tok", _u32p), ("deleted", _u8p), ("threads", C.c_int),
                 ("keep_host_postings", C.c_int), ("n_facet_terms", C.c_uint32), ("facet_off", _u64p),
-                ("facet_tok", _u32p)]
+                ("facet_tok", _u32p), ("keep_positions", C.c_int), ("text_gap", _u64p), ("n_text_gap", C.c_uint64),
+                ("name_gap", _u64p), ("n_name_gap", C.c_uint64)]
 
 
 class IndexInput(C.Structure):
@@ -102,7 +103,7 @@ class GlobalStats(C.Structure):
 
 class QueryBatch(C.Structure):
     _fields_ = [("n_queries", C.c_uint32), ("q_off", _u32p), ("terms", _u32p), ("mode", C.c_int),
-                ("f_off", _u32p), ("f_terms", _u32p), ("occur", _u8p)]
+                ("f_off", _u32p), ("f_terms", _u32p), ("occur", _u8p), ("phrase_len", _u32p), ("phrase_pos", _u32p)]
 
 
 class IndexStats(C.Structure):
@@ -110,7 +111,7 @@ class IndexStats(C.Structure):
                 ("device_bytes", C.c_uint64), ("tot_tokens", C.c_uint64 * 2), ("avgdl", C.c_float * 2),
                 ("has_name", C.c_int), ("device", C.c_int), ("n_facet_terms", C.c_uint32),
                 ("tot_facet_tokens", C.c_uint64), ("n_dense_f32", C.c_uint32), ("n_rank_terms", C.c_uint32),
-                ("n_sparse_rank_terms", C.c_uint32), ("reserved0", C.c_uint32), ("rank_bytes", C.c_uint64)]
+                ("n_sparse_rank_terms", C.c_uint32), ("has_positions", C.c_uint32), ("rank_bytes", C.c_uint64)]
 
 
 class ModelOut(C.Structure):
@@ -276,6 +277,7 @@ class Stats:
     n_rank_terms: int = 0
     n_sparse_rank_terms: int = 0
     rank_bytes: int = 0
+    has_positions: bool = False
 
 
 def _u64(a):
@@ -286,8 +288,10 @@ def _u32(a):
     return np.ascontiguousarray(a, dtype=np.uint32)
 
 
-def _batch(q_off, terms, mode, f_off=None, f_terms=None, occur=None):
-    """(QueryBatch, arrays it points into); occur: per-term OCCUR_* or None."""
+def _batch(q_off, terms, mode, f_off=None, f_terms=None, occur=None, phrase_len=None, phrase_pos=None):
+    """(QueryBatch, arrays it points into); occur: per-term OCCUR_* or None;
+    phrase_len / phrase_pos: per-term clause lengths and position offsets
+    (fg_query_batch: a clause of n >= 2 terms is a phrase), or None."""
     q_off = _u32(q_off)
     terms = _u32(terms)
     f_off = None if f_off is None else _u32(f_off)
@@ -295,14 +299,24 @@ def _batch(q_off, terms, mode, f_off=None, f_terms=None, occur=None):
     occur = None if occur is None else np.ascontiguousarray(occur, np.uint8)
     if occur is not None and len(occur) != len(terms):
         raise ValueError("occur must parallel terms")
+    if (phrase_len is None) != (phrase_pos is None):
+        raise ValueError("phrase_len and phrase_pos go together")
+    phrase_len = None if phrase_len is None else _u32(phrase_len)
+    phrase_pos = None if phrase_pos is None else _u32(phrase_pos)
+    if phrase_len is not None and (len(phrase_len) != len(terms) or len(phrase_pos) != len(terms)):
+        raise ValueError("phrase_len / phrase_pos must parallel terms")
     qb = QueryBatch(len(q_off) - 1, _ptr(q_off, _u32p), _ptr(terms, _u32p), mode, _ptr(f_off, _u32p),
-                    _ptr(f_terms, _u32p), _ptr(occur, _u8p))
-    return qb, (q_off, terms, f_off, f_terms, occur)
+                    _ptr(f_terms, _u32p), _ptr(occur, _u8p), _ptr(phrase_len, _u32p), _ptr(phrase_pos, _u32p))
+    return qb, (q_off, terms, f_off, f_terms, occur, phrase_len, phrase_pos)
 
 
 def _docs_input(text_off, text_tok, n_terms, name_off=None, name_tok=None, deleted=None, threads=0,
-                keep_host=True, facets=None):
-    """facets: (facet_off, facet_tok, n_facet_terms) or None."""
+                keep_host=True, facets=None, positions=False, text_gaps=None, name_gaps=None):
+    """facets: (facet_off, facet_tok, n_facet_terms) or None; positions: keep the
+    forward index (phrase queries); text_gaps / name_gaps: ascending indices into
+    text_tok / name_tok before which the analyzer dropped a token, or None."""
+    tg = None if text_gaps is None or len(text_gaps) == 0 else _u64(text_gaps)
+    ng = None if name_gaps is None or len(name_gaps) == 0 else _u64(name_gaps)
     text_off = _u64(text_off)
     text_tok = _u32(text_tok)
     name_off = None if name_off is None else _u64(name_off)
@@ -315,8 +329,9 @@ def _docs_input(text_off, text_tok, n_terms, name_off=None, name_tok=None, delet
     n_docs = len(text_off) - 1
     inp = DocsInput(n_docs, n_terms, _ptr(text_off, _u64p), _ptr(text_tok, _u32p), _ptr(name_off, _u64p),
                     _ptr(name_tok, _u32p), _ptr(deleted, _u8p), threads, 1 if keep_host else 0, nft,
-                    _ptr(fo, _u64p), _ptr(ft, _u32p))
-    return (text_off, text_tok, name_off, name_tok, deleted, fo, ft), inp
+                    _ptr(fo, _u64p), _ptr(ft, _u32p), 1 if positions else 0, _ptr(tg, _u64p),
+                    0 if tg is None else len(tg), _ptr(ng, _u64p), 0 if ng is None else len(ng))
+    return (text_off, text_tok, name_off, name_tok, deleted, fo, ft, tg, ng), inp
 
 
 @dataclass
@@ -373,12 +388,17 @@ class Index:
     @classmethod
     def from_docs(cls, ctx: Context, text_off, text_tok, n_terms: int, name_off=None, name_tok=None,
                   deleted=None, device: int | None = None, threads: int = 0, keep_host: bool = True,
-                  global_stats: "ShardStats | None" = None, facets=None):
+                  global_stats: "ShardStats | None" = None, facets=None, positions: bool = False,
+                  text_gaps=None, name_gaps=None):
         """Build a snapshot; `global_stats` (a doc-sharded namespace's summed
         ShardStats) makes the BM25 statistics global while the postings stay local.
-        `facets` = (facet_off, facet_tok, n_facet_terms): FacetTokenizer tokens per doc."""
+        `facets` = (facet_off, facet_tok, n_facet_terms): FacetTokenizer tokens per doc.
+        `positions`: keep the position-addressed forward index, so phrase queries
+        run on the snapshot; `text_gaps` / `name_gaps`: ascending indices into
+        text_tok / name_tok before which the analyzer dropped one token (it still
+        consumes a position)."""
         keep, inp = _docs_input(text_off, text_tok, n_terms, name_off, name_tok, deleted, threads, keep_host,
-                                facets)
+                                facets, positions, text_gaps, name_gaps)
         h = _p()
         dev = ctx.devices[0] if device is None else device
         if global_stats is None:
@@ -465,7 +485,7 @@ class Index:
         _check(_lib.fg_index_stats_get(self._h, C.byref(s)))
         return Stats(s.n_docs, s.n_terms, s.n_postings, s.device_bytes, tuple(s.tot_tokens), tuple(s.avgdl),
                      bool(s.has_name), s.device, s.n_facet_terms, s.tot_facet_tokens, s.n_dense_f32, s.n_rank_terms,
-                     s.n_sparse_rank_terms, s.rank_bytes)
+                     s.n_sparse_rank_terms, s.rank_bytes, bool(s.has_positions))
 
     def df(self, term: int, field: int = -1) -> int:
         return int(_lib.fg_index_df(self._h, field, term))
@@ -499,13 +519,16 @@ class Index:
         _check(_lib.fg_index_bm25(self._h, term, C.byref(wt), C.byref(wn), _ptr(cache, _f32p)))
         return wt.value, wn.value, cache
 
-    def plan(self, q_off, terms, k: int, mode: int = MODE_AND, f_off=None, f_terms=None, occur=None) -> "Plan":
-        return Plan(self, q_off, terms, k, mode, f_off, f_terms, occur)
+    def plan(self, q_off, terms, k: int, mode: int = MODE_AND, f_off=None, f_terms=None, occur=None,
+             phrase_len=None, phrase_pos=None) -> "Plan":
+        return Plan(self, q_off, terms, k, mode, f_off, f_terms, occur, phrase_len, phrase_pos)
 
-    def search_batch(self, q_off, terms, k: int, mode: int = MODE_AND, f_off=None, f_terms=None, occur=None):
+    def search_batch(self, q_off, terms, k: int, mode: int = MODE_AND, f_off=None, f_terms=None, occur=None,
+                     phrase_len=None, phrase_pos=None):
         """f_off / f_terms: per-query facet clauses (facet term ids), or None;
-        occur: per-term OCCUR_MUST / SHOULD / MUST_NOT (None: `mode`)."""
-        qb, keep = _batch(q_off, terms, mode, f_off, f_terms, occur)
+        occur: per-term OCCUR_MUST / SHOULD / MUST_NOT (None: `mode`);
+        phrase_len / phrase_pos: per-term clause lengths and offsets (phrases)."""
+        qb, keep = _batch(q_off, terms, mode, f_off, f_terms, occur, phrase_len, phrase_pos)
         nq = qb.n_queries
         score = np.zeros(nq * k, np.float32)
         doc = np.zeros(nq * k, np.uint32)
@@ -532,12 +555,12 @@ class Index:
         _check(_lib.fg_bytes_model_or(self._h, C.byref(qb), k, _ptr(t, _f32p), _ptr(out, _f64p)))
         return out.reshape(qb.n_queries, 4)
 
-    def model(self, q_off, terms, k: int, thr=None, mode: int = MODE_AND):
+    def model(self, q_off, terms, k: int, thr=None, mode: int = MODE_AND, phrase_len=None, phrase_pos=None):
         """fg_model_batch: the loads k_conj / k_disj issue for the batch replayed on the
         host (thr: each query's final k-th best score, or None = k_conj's exhaustive
         cascade).  Returns (dict of the launch's bytes: algorithmic, 128-B line floor,
         per-query line sum, ...; per-query {stream, probe, output, total} array)."""
-        qb, keep = _batch(q_off, terms, mode)
+        qb, keep = _batch(q_off, terms, mode, phrase_len=phrase_len, phrase_pos=phrase_pos)
         t = None if thr is None else np.ascontiguousarray(thr, np.float32)
         per = np.zeros(4 * qb.n_queries, np.float64)
         o = ModelOut()
@@ -574,8 +597,8 @@ class Plan:
     s * nq + q ([n_segs * nq, k]), the input layout of merge_shards."""
 
     def __init__(self, index, q_off, terms, k: int, mode: int = MODE_AND, f_off=None, f_terms=None,
-                 occur=None):
-        qb, self._keep = _batch(q_off, terms, mode, f_off, f_terms, occur)
+                 occur=None, phrase_len=None, phrase_pos=None):
+        qb, self._keep = _batch(q_off, terms, mode, f_off, f_terms, occur, phrase_len, phrase_pos)
         self.k = k
         h = _p()
         if isinstance(index, (list, tuple)):
@@ -723,11 +746,11 @@ def link_plans(plans):
 
 
 def search_sharded(indexes, q_off, terms, k: int, mode: int = MODE_AND, f_off=None, f_terms=None, ctx=None,
-                   occur=None):
+                   occur=None, phrase_len=None, phrase_pos=None):
     """fg_search_sharded: one batch over several shard / segment / namespace
     indexes, merged on the first one's device by (score desc, shard asc, doc
     asc).  Returns (score [nq,k], doc [nq,k], shard [nq,k], n [nq])."""
-    qb, keep = _batch(q_off, terms, mode, f_off, f_terms, occur)
+    qb, keep = _batch(q_off, terms, mode, f_off, f_terms, occur, phrase_len, phrase_pos)
     nq = qb.n_queries
     hs = (_p * len(indexes))(*[ix._h for ix in indexes])
     score = np.zeros(nq * k, np.float32)

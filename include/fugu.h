@@ -32,9 +32,11 @@ extern "C" {
  * call's contract changes (4: fg_query_batch.occur; fg_model_out.  5:
  * fg_index_stats.n_sparse_rank_terms / reserved0 / rank_bytes (16 B more);
  * query-time scoring: fg_index_rescore[_many] do no device work, fg_index_term_kth
- * of a rescore is a lower bound).  A binding checks fg_abi_version() against the
- * value it was written for before passing any struct. */
-#define FG_ABI_VERSION 5
+ * of a rescore is a lower bound.  6: phrase queries -- fg_docs_input.keep_positions
+ * / text_gap / name_gap, fg_query_batch.phrase_len / phrase_pos, both appended;
+ * fg_index_stats.reserved0 is has_positions).  A binding checks fg_abi_version()
+ * against the value it was written for before passing any struct. */
+#define FG_ABI_VERSION 6
 
 #define FG_OK 0
 #define FG_EINVAL (-1)        /* bad argument (e.g. k == 0: tantivy asserts limit >= 1) */
@@ -104,6 +106,22 @@ typedef struct fg_docs_input {
   uint32_t n_facet_terms;
   const uint64_t* facet_off; /* [n_docs+1] or NULL */
   const uint32_t* facet_tok;
+  /* Positions (phrase queries).  keep_positions != 0: the snapshot also keeps a
+   * position-addressed forward index of both fields (4 B per token position +
+   * 8 B per doc and field of device memory), which k_phrase verifies phrase
+   * candidates against.  A gap list holds ascending indices i into text_tok
+   * (name_tok), 0 <= i < the array's length: the analyzer dropped one token
+   * (RemoveLongFilter) immediately before element i, inside element i's doc; the
+   * dropped token consumes a position.  An index may repeat (several dropped in
+   * a row); tokens dropped after a doc's last kept token are not listed (no
+   * phrase can reach them).  NULL = no gaps.  Gaps count nowhere else: field
+   * lengths, tf, df and the token totals are those of the kept tokens.  A
+   * zero-initialised tail is today's behaviour. */
+  int keep_positions;
+  const uint64_t* text_gap;
+  uint64_t n_text_gap;
+  const uint64_t* name_gap;
+  uint64_t n_name_gap;
 } fg_docs_input;
 
 /* Replaces: Index::open_or_create + IndexWriter commit + Searcher snapshot
@@ -159,6 +177,7 @@ int fg_docs_stats(const fg_docs_input* in, uint32_t* df_text, uint32_t* df_name,
 /* ... and of its facet field: df_facet [n_facet_terms], *tot_facet. */
 int fg_docs_facet_stats(const fg_docs_input* in, uint32_t* df_facet, uint64_t* tot_facet);
 /* fg_index_build_from_docs scored with global statistics (g may be NULL = local).
+ * (fg_index_build[_global] take pre-inverted postings and keep no positions.)
  * A build whose docs hold fewer than a quarter of the n_terms vocabulary's terms
  * (a commit's new docs) keeps its own term dictionary -- its work and device
  * arrays then scale with its own terms, as a tantivy segment's do -- and every
@@ -213,7 +232,7 @@ typedef struct fg_index_stats {
   uint32_t n_dense_f32;      /* terms with an f32 score table */
   uint32_t n_rank_terms;     /* terms with rank words */
   uint32_t n_sparse_rank_terms;  /* ... of which sparse rank words (block entries + the words holding docs) */
-  uint32_t reserved0;
+  uint32_t has_positions;    /* 1: built with fg_docs_input.keep_positions (phrase queries run on it) */
   uint64_t rank_bytes;       /* device bytes of the rank words, plain and sparse */
 } fg_index_stats;
 int fg_index_stats_get(const fg_index* ix, fg_index_stats* out);
@@ -283,6 +302,23 @@ typedef struct fg_query_batch {
    * (0.0 + must score) + Should union); without one the Shoulds' union; MustNot
    * clauses exclude; no Must and no Should: no hits.  A batch may mix shapes. */
   const uint8_t* occur;
+  /* Phrase clauses (tantivy PhraseQuery at slop 0: a word the analyzer splits
+   * into several tokens, or a quoted literal), or NULL (every term is a clause
+   * of its own).  phrase_len is parallel to `terms`: at a clause's first term
+   * the number of terms in the clause (1: a plain term clause, n >= 2: a phrase),
+   * then n-1 entries of 0; the clause's occur is its first term's.  phrase_pos,
+   * parallel too, holds each term's position offset within its phrase: 0 at the
+   * first, strictly increasing after (a token the analyzer dropped leaves a
+   * hole).  A doc matches a field when tok[p + pos_j] == term_j for every j at
+   * some position p; its score is Bm25Weight::for_terms' -- (sum of the terms'
+   * idf) * (1 + K1) * c / (c + cache[fieldnorm]) with c the number of such p --
+   * summed text then name.  Device subset: the phrase is the query's ONLY
+   * clause, the query has no facet clauses, and every snapshot of the plan was
+   * built with keep_positions; otherwise FG_EUNSUPPORTED ("phrase clause beside
+   * other clauses", "phrase with facet filters", "snapshot built without
+   * positions").  A batch may mix phrase queries with the other shapes. */
+  const uint32_t* phrase_len;
+  const uint32_t* phrase_pos;
 } fg_query_batch;
 
 /* Plan a batch: host-side query planning (tantivy Weight creation: terms
@@ -434,7 +470,7 @@ int fg_search_sharded(fg_ctx* ctx, fg_index* const* shards, uint32_t n_shards, c
  * threshold must at least (k_conj's bounds after each list and a single
  * list's block-max chunk skip; k_disj's tile split and both bounds); NULL =
  * k_conj's exhaustive cascade (k_disj at threshold 0).  Pure Must and pure
- * Should queries only (FG_EINVAL otherwise).  per_query[4*i..] (may be NULL) =
+ * Should queries only (FG_EINVAL otherwise, phrase clauses included).  per_query[4*i..] (may be NULL) =
  * {stream, probe, output, total} bytes of query i. */
 typedef struct fg_model_out {
   double stream_bytes;     /* lead / essential postings (doc + score); k_disj's per-(tile, clause) ranges + bounds */

@@ -26,12 +26,18 @@
  *   fg_analyze         the "default" analyzer (SimpleTokenizer ->
  *                      RemoveLongFilter(40) -> LowerCaser)
  *   fg_parse_query     the QueryParser subset the device runs
+ *   fg_parse_query_clauses  the same as clauses: terms, and phrases with offsets
  *
- * Queries outside the device subset (phrases, field:, -, boosts, a text
- * query with filters that parse to no facet term) return FG_EUNSUPPORTED: the
- * reference host then runs tantivy; this library never answers them on the CPU.
- * Empty queries (AllQuery), facet-only queries and text + facet filters run
- * on the device.
+ * Phrase queries run on the device (k_phrase, slop 0): a word the analyzer
+ * splits into several tokens (`e-mail`, `user@example.com`, `3.14`) or a quoted
+ * literal ("new york"), when the phrase is the query's only clause and no facet
+ * filter is given (segments built with FUGU_POSITIONS=0 keep no positions and
+ * refuse them).  Queries outside the device subset (a phrase beside other
+ * clauses or with filters, slop / prefix suffixes on a quoted literal, field:,
+ * boosts, a text query with filters that parse to no facet term) return
+ * FG_EUNSUPPORTED: the reference host then runs tantivy; this library never
+ * answers them on the CPU.  Empty queries (AllQuery), facet-only queries and
+ * text + facet filters run on the device.
  */
 #ifndef FUGU_HOST_H
 #define FUGU_HOST_H
@@ -172,6 +178,12 @@ int fg_parse_query(const char* query, int* mode, char* out, size_t cap, size_t* 
 /* The terms with their occurs: one line per term, "<o>:<term>", o = FG_OCCUR_*
  * ('0' Must, '1' Should, '2' MustNot). */
 int fg_parse_query_occur(const char* query, char* out, size_t cap, size_t* len);
+/* (Both return FG_EUNSUPPORTED for a query with a phrase clause: their outputs
+ * cannot express one.)  The clauses, one line each: "<o>:" followed by the
+ * clause's space-separated "term@pos" -- pos the token's position offset within
+ * its phrase (a token the analyzer dropped leaves a hole); a term clause is a
+ * single "term@0". */
+int fg_parse_query_clauses(const char* query, char* out, size_t cap, size_t* len);
 /* FacetTokenizer tokens of Facet::from_text(path), '\n'-separated; the
  * encoded facets keep their U+0000 separators, so read *len bytes. */
 int fg_facet_tokens(const char* path, char* out, size_t cap, size_t* len);

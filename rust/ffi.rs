@@ -22,7 +22,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct fg_db { _p: [u8; 0] }
 
 // ---- constants (fugu.h)
-pub const FG_ABI_VERSION: c_int = 5;  // checked against fg_abi_version() before any struct is passed
+pub const FG_ABI_VERSION: c_int = 6;  // checked against fg_abi_version() before any struct is passed
 pub const FG_OK: c_int = 0;
 pub const FG_EINVAL: c_int = -1;
 pub const FG_ENODEV: c_int = -2;
@@ -59,6 +59,11 @@ pub struct fg_docs_input {
     pub n_facet_terms: u32,
     pub facet_off: *const u64,
     pub facet_tok: *const u32,
+    pub keep_positions: c_int,      // != 0: keep the forward index (phrase queries run on the snapshot)
+    pub text_gap: *const u64,       // ascending indices into text_tok: one token dropped before each, or null
+    pub n_text_gap: u64,
+    pub name_gap: *const u64,
+    pub n_name_gap: u64,
 }
 
 #[repr(C)]
@@ -104,7 +109,7 @@ pub struct fg_index_stats {
     pub n_dense_f32: u32,
     pub n_rank_terms: u32,
     pub n_sparse_rank_terms: u32,
-    pub reserved0: u32,
+    pub has_positions: u32,         // built with keep_positions
     pub rank_bytes: u64,
 }
 
@@ -117,6 +122,8 @@ pub struct fg_query_batch {
     pub f_off: *const u32,          // [n_queries + 1] facet clauses per query, or null
     pub f_terms: *const u32,
     pub occur: *const u8,           // per term FG_OCCUR_*, parallel to `terms`, or null
+    pub phrase_len: *const u32,     // per term: a clause's length at its first term (>= 2: a phrase), then 0s; or null
+    pub phrase_pos: *const u32,     // per term: its position offset within its phrase
 }
 
 #[repr(C)]
@@ -305,6 +312,7 @@ extern "C" {
     pub fn fg_parse_query(query: *const c_char, mode: *mut c_int, out: *mut c_char, cap: usize, len: *mut usize)
                           -> c_int;
     pub fn fg_parse_query_occur(query: *const c_char, out: *mut c_char, cap: usize, len: *mut usize) -> c_int;
+    pub fn fg_parse_query_clauses(query: *const c_char, out: *mut c_char, cap: usize, len: *mut usize) -> c_int;
     pub fn fg_facet_tokens(path: *const c_char, out: *mut c_char, cap: usize, len: *mut usize) -> c_int;
     pub fn fg_facet_clauses(filters: *const *const c_char, n_filters: u32, applies: *mut c_int,
                             all_query: *mut c_int, out: *mut c_char, cap: usize, len: *mut usize) -> c_int;
