@@ -1,12 +1,13 @@
-// Host-side internals of libfugu shared by fugu.cpp (snapshot build, execution,
-// the C ABI), plan.cpp (batch planning) and model.cpp (the byte / line models of
-// the roofline):
+// Host-side internals of libfugu shared by fugu.cpp (streams, pools, statistics,
+// execution, the C ABI), build.cpp (snapshot build and rescore), plan.cpp (batch
+// planning) and model.cpp (the byte / line models of the roofline):
 // the opaque handles of include/fugu.h and their memory pools.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <functional>
 #include <cstdint>
@@ -356,15 +357,83 @@ namespace fgh {
 void device_pools(int dev, std::shared_ptr<WsPool>* ws, std::shared_ptr<PinnedPool>* pin);
 }  // namespace fgh
 
-struct fg_index {
-  std::atomic<int> refs{1};
-  int dev = 0;
+namespace fgh {
+// The chunk tables of the scoring kernels (k_score / k_bucket / k_tsub / k_ktop:
+// fg_internal.h ScoreJob::sc_* / bk_* / kt_* / kb_* / kc_*).  They depend on the
+// postings only, so they are structure; score_job_tables hands them to a ScoreJob.
+struct ChunkTables {
+  // packed chunk tables of k_score / k_bucket
+  const uint32_t *d_sc_tf = nullptr, *d_sc_tl = nullptr, *d_bk_tf = nullptr, *d_bk_tl = nullptr, *d_bk_e0 = nullptr,
+                 *d_bk_e1 = nullptr, *d_kt_terms = nullptr, *d_kt_tiny = nullptr;
+  const uint64_t *d_sc_e0 = nullptr, *d_sc_e1 = nullptr;
+  uint32_t n_scb = 0, n_ktiny = 0;  // k_score chunks; k_ktop_tiny terms
+  const uint32_t* d_tterm = nullptr;  // tile-table terms in toff order (k_tsub)
+  uint32_t n_tterm = 0, n_tiles = 0;
+  // k_ktop's tables: long terms, their first chunk, each chunk's term and first posting
+  const uint32_t *d_kb_terms = nullptr, *d_kb_chunk0 = nullptr, *d_kc_big = nullptr, *d_kc_start = nullptr;
+  uint32_t n_sc = 0, n_bk = 0, n_kt = 0, n_kbig = 0, n_kchunks = 0;
+};
+
+// ---- structure (independent of the statistics).  A rescored snapshot shares
+// its base's by ONE assignment of this struct (build.cpp rescore_one): a member
+// added here is shared with no further edit.
+struct IndexStructure : ChunkTables {
   uint32_t n_docs = 0, n_terms = 0;
   bool has_name = false;
-  uint64_t n_postings = 0, device_bytes = 0, dir_entries = 0, tile_entries = 0;
-  uint32_t n_dense = 0, n_rank = 0;  // n_rank: rank-kind slots, plain (d.n_prank) and sparse
-  uint64_t n_srank_words = 0;        // sparse rank words (d.srank_w)
-  bool has_positions = false;        // the forward index (d.fwd_off / d.fwd): phrase queries run on it
+  uint64_t n_postings = 0, dir_entries = 0, tile_entries = 0;
+  uint32_t n_rank = 0;         // rank-kind slots, plain (d.n_prank) and sparse
+  uint64_t n_srank_words = 0;  // sparse rank words (d.srank_w)
+  bool has_positions = false;  // the forward index (d.fwd_off / d.fwd): phrase queries run on it
+  // The snapshot's own term dictionary (tantivy keeps one per segment): a build
+  // over far fewer distinct terms than the vocabulary it was given (a commit's
+  // new docs) numbers its terms locally, tmap[l] = the vocabulary id of local
+  // term l (ascending); empty: local ids ARE vocabulary ids.  Every per-term
+  // array here and on the device is indexed by local id; the C ABI takes
+  // vocabulary ids (fgh::local_term).  n_terms counts local terms, n_vocab the
+  // vocabulary (fg_index_stats::n_terms).
+  SharedVec<uint32_t> tmap;
+  uint32_t n_vocab = 0;
+  SharedVec<uint64_t> off;
+  SharedVec<uint32_t> df_text, df_name;  // this snapshot's own postings (tantivy's per-segment cost order)
+  SharedVec<uint32_t> first_doc, last_doc;
+  std::shared_ptr<const std::vector<uint32_t>> h_doc;  // optional host copy for fg_bytes_model(_gpu)
+  SharedVec<uint32_t> tmeta;  // host copy of DevIndex::tmeta (probe kind of each term)
+  uint64_t tot_local[2] = {0, 0};
+  // facet field (FG_FIELD_FACET)
+  uint32_t n_fterms = 0;
+  uint64_t tot_f_local = 0;
+  SharedVec<uint64_t> foff;
+  SharedVec<uint32_t> df_facet_local, ffirst, flast;
+  // device: structure arrays (smem, shared) and the pool the scoring tables
+  // (IndexBounds::sblock) come from
+  std::shared_ptr<DevAllocs> smem;
+  std::shared_ptr<ScorePool> spool;
+  uint64_t struct_bytes = 0;
+  // the device's view; d.alive and the bound tables' pointers ride along (a
+  // rescore replaces d.alive when its deletions differ)
+  fg::DevIndex d{};
+};
+
+// ---- bounds: computed ONCE when the structure is built (k_score / k_bucket /
+// k_tsub / k_ktop under the build's statistics) and shared by every rescore of
+// it, again by one assignment; a plan scales them by the ratio of the current
+// to the build statistics (term_ratio).  sblock holds the device tables and the
+// host tmaxs / ktop.
+struct IndexBounds {
+  std::shared_ptr<ScoreBlock> sblock;
+  const float* ktop = nullptr;   // [V * kNumTopK] K-th best score per term at the build (alive docs then)
+  const float* tmaxs = nullptr;  // [V] largest posting score per term at the build
+  SharedVec<float> wb_text, wb_name;  // the build's BM25 weights
+  float cache_b[512];                 // the build's tf caches
+  SharedVec<uint32_t> h_alive_b;      // the alive bitset ktop was selected over (empty: every doc)
+  uint64_t device_bytes = 0;
+};
+}  // namespace fgh
+
+struct fg_index : fgh::IndexStructure, fgh::IndexBounds {
+  std::atomic<int> refs{1};
+  int dev = 0;
+  uint32_t n_dense = 0;
   // ---- statistics (this snapshot's own: the Searcher-wide ones of its commit).
   // Scores are formed at query time from them (DevIndex::tfn, DevPlan::q_wt /
   // q_wn, the plan's copy of `cache`), as tantivy's TermScorer does.
@@ -375,17 +444,13 @@ struct fg_index {
   fgh::SharedVec<float> w_text, w_name;
   // each weight's idf (w = idf * (1 + K1)): Bm25Weight::for_terms sums a phrase's idfs before the factor
   fgh::SharedVec<float> idf_text, idf_name;
+  // the facet field's
+  uint64_t tot_f = 0;
+  float avgdl_f = 0.0f, cache_f1 = 0.0f;
+  std::vector<uint32_t> df_facet;
+  std::vector<float> fscore;    // a facet clause's score in a doc holding the term (tf 1, fieldnorm id 1)
   fgh::SharedVec<uint32_t> h_alive;  // the alive bitset of this snapshot (empty: every doc)
-  // ---- bounds: computed ONCE when the structure is built (k_score / k_bucket /
-  // k_tsub / k_ktop under the build's statistics) and shared by every rescore of
-  // it; a plan scales them by the ratio of the current to the build statistics
-  // (term_ratio).  sblock holds the device tables and the host tmaxs / ktop.
-  std::shared_ptr<fgh::ScoreBlock> sblock;
-  const float* ktop = nullptr;   // [V * kNumTopK] K-th best score per term at the build (alive docs then)
-  const float* tmaxs = nullptr;  // [V] largest posting score per term at the build
-  fgh::SharedVec<float> wb_text, wb_name;  // the build's BM25 weights
-  float cache_b[512];                      // the build's tf caches
-  fgh::SharedVec<uint32_t> h_alive_b;      // the alive bitset ktop was selected over (empty: every doc)
+  // ---- how the statistics and deletions relate to the bounds' (IndexBounds)
   uint32_t n_dead = 0;     // docs dead now that were alive in h_alive_b (ktop's K-th then needs K + n_dead)
   bool same_stats = true;  // the current statistics are the build's (every ratio exactly 1)
   double cup[2] = {1, 1}, cdn[2] = {1, 1};  // per field: max / min over fieldnorms of the tf-factor ratio
@@ -393,47 +458,7 @@ struct fg_index {
   // [V * kNumTopK] namespace-wide floor of the current K-th scores (fg_index_set_kth_floor) or
   // null; read and replaced with std::atomic_load / atomic_store
   std::shared_ptr<const std::vector<float>> kth_floor;
-  // ---- structure (independent of the statistics; shared with rescored snapshots)
-  // The snapshot's own term dictionary (tantivy keeps one per segment): a build
-  // over far fewer distinct terms than the vocabulary it was given (a commit's
-  // new docs) numbers its terms locally, tmap[l] = the vocabulary id of local
-  // term l (ascending); empty: local ids ARE vocabulary ids.  Every per-term
-  // array here and on the device is indexed by local id; the C ABI takes
-  // vocabulary ids (fgh::local_term).  n_terms counts local terms, n_vocab the
-  // vocabulary (fg_index_stats::n_terms).
-  fgh::SharedVec<uint32_t> tmap;
-  uint32_t n_vocab = 0;
-  fgh::SharedVec<uint64_t> off;
-  fgh::SharedVec<uint32_t> df_text, df_name;  // this snapshot's own postings (tantivy's per-segment cost order)
-  fgh::SharedVec<uint32_t> first_doc, last_doc;
-  std::shared_ptr<const std::vector<uint32_t>> h_doc;  // optional host copy for fg_bytes_model(_gpu)
-  fgh::SharedVec<uint32_t> tmeta;  // host copy of DevIndex::tmeta (probe kind of each term)
-  uint64_t tot_local[2] = {0, 0};
-  // facet field (FG_FIELD_FACET)
-  uint32_t n_fterms = 0;
-  uint64_t tot_f = 0, tot_f_local = 0;
-  float avgdl_f = 0.0f, cache_f1 = 0.0f;
-  fgh::SharedVec<uint64_t> foff;
-  std::vector<uint32_t> df_facet;
-  fgh::SharedVec<uint32_t> df_facet_local, ffirst, flast;
-  std::vector<float> fscore;    // a facet clause's score in a doc holding the term (tf 1, fieldnorm id 1)
-  // device: structure arrays (smem, shared), the scoring tables (sblock, from the
-  // structure's spool) and other snapshot-own arrays (mem)
-  std::shared_ptr<DevAllocs> smem;
-  std::shared_ptr<fgh::ScorePool> spool;
-  uint64_t struct_bytes = 0;
-  // packed chunk tables of k_score / k_bucket (fg_internal.h ScoreJob::sc_* / bk_*)
-  const uint32_t *d_sc_tf = nullptr, *d_sc_tl = nullptr, *d_bk_tf = nullptr, *d_bk_tl = nullptr, *d_bk_e0 = nullptr,
-                 *d_bk_e1 = nullptr, *d_kt_terms = nullptr, *d_kt_tiny = nullptr;
-  const uint64_t *d_sc_e0 = nullptr, *d_sc_e1 = nullptr;
-  uint32_t n_scb = 0, n_ktiny = 0;  // k_score chunks; k_ktop_tiny terms
-  const uint32_t* d_tterm = nullptr;  // tile-table terms in toff order (k_tsub)
-  uint32_t n_tterm = 0, n_tiles = 0;
-  // k_ktop's tables (structure): long terms, their first chunk, each chunk's term and first posting
-  const uint32_t *d_kb_terms = nullptr, *d_kb_chunk0 = nullptr, *d_kc_big = nullptr, *d_kc_start = nullptr;
-  uint32_t n_sc = 0, n_bk = 0, n_kt = 0, n_kbig = 0, n_kchunks = 0;
-  fg::DevIndex d{};
-  DevAllocs mem;
+  DevAllocs mem;  // snapshot-own device arrays
   // plan workspaces and the pinned host staging of plan uploads and result
   // copies: the device's pools, shared by every snapshot on it (fgh::device_pools)
   std::shared_ptr<WsPool> pool;
@@ -529,4 +554,52 @@ int plan_create_multi(fg_index* const* ixs, uint32_t n_segs, const fg_query_batc
                       bool sync, hipStream_t up);
 // f(0 .. n-1) on fugu.cpp's persistent worker threads (ShardWorkers); returns when all have run
 void run_parallel(uint32_t n, const std::function<void(uint32_t)>& f);
+
+// ---- building (build.cpp): what fugu.cpp keeps for it
+// The calling thread's stream for snapshot builds and rescores (never the
+// legacy null stream), whether the thread works in the background, and the
+// workgroup cap of a background scoring's launches (0: none)
+hipStream_t build_stream();
+bool on_background();
+uint32_t bg_grid_cap(int dev);
+// FIELD_NORMS_TABLE.binary_search(n).unwrap_or_else(|i| i - 1)
+uint8_t fieldnorm_id(uint64_t n);
+// BM25 weights of terms [0, V) for statistics (Ns, df_t, df_n) (tantivy's f32
+// order) and their idfs (it, in)
+void bm25_weights(uint64_t Ns, const uint32_t* df_t, const uint32_t* df_n, uint32_t V, std::vector<float>& wt,
+                  std::vector<float>& wn, std::vector<float>& it, std::vector<float>& in);
+// The statistics of a snapshot (host only; wts: shared precomputed weights of
+// the same statistics, or nullptr), and how they relate to the build's
+// (fg_index::same_stats, cup / cdn)
+void set_stats(fg_index* ix, uint64_t Ns, const uint64_t tot2[2], const uint32_t* df_t, const uint32_t* df_n,
+               uint64_t tot_f, const uint32_t* df_f, const Weights* wts);
+void relate_stats(fg_index* ix);
+// n bytes of src into a fresh device allocation held by m (synchronous with the host)
+int dev_upload_bytes(DevAllocs& m, const void* src, size_t n, void** out, uint64_t* bytes);
+template <class T>
+int dev_upload(DevAllocs& m, const T* src, size_t n, T** out, uint64_t* bytes) {
+  return dev_upload_bytes(m, src, n * sizeof(T), reinterpret_cast<void**>(out), bytes);
+}
+// Several host arrays into ONE device allocation (one hipMalloc instead of one
+// per array: a small segment's build is otherwise dominated by allocation).
+struct UploadBatch {
+  struct E { const void* src; size_t bytes; void** out; };
+  std::vector<E> es;
+  size_t total = 0;
+  static size_t slot(size_t bytes) { return (std::max<size_t>(bytes, 16) + 16 + 255) & ~size_t(255); }  // >= 16 B of slack
+  template <class T>
+  void add(const T* src, size_t n, T** out) {
+    es.push_back(E{src, n * sizeof(T), reinterpret_cast<void**>(out)});
+    total += slot(n * sizeof(T));
+  }
+  int commit(DevAllocs& m, uint64_t* bytes);
+};
+// FUGU_BUILD_TRACE=1: per-phase wall time of a snapshot build on stderr
+struct BuildTrace {
+  bool on = false;
+  std::chrono::steady_clock::time_point t;
+  void start();
+  void mark(const char* what);
+};
+extern thread_local BuildTrace g_bt;
 }  // namespace fgh

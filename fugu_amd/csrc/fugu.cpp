@@ -1,5 +1,6 @@
-// libfugu host side: index snapshot build + HBM upload, plan execution and
-// the C ABI of include/fugu.h (batch planning: plan.cpp).
+// libfugu host side: streams, pools, a snapshot's statistics, plan execution
+// and the C ABI of include/fugu.h (snapshot build and rescore: build.cpp; batch
+// planning: plan.cpp).
 //
 // The BM25 statistics follow tantivy 0.24.1 as fugu uses it (SURVEY.md
 // Appendix A): N = max_doc (deleted docs included), avgdl = total tokens / N,
@@ -77,12 +78,6 @@ const FieldNormTable& fn_table() {
   static const FieldNormTable t;
   return t;
 }
-// FIELD_NORMS_TABLE.binary_search(n).unwrap_or_else(|i| i - 1)
-uint8_t fieldnorm_id(uint64_t n) {
-  const uint32_t* t = fn_table().v;
-  uint32_t x = n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)n;
-  return (uint8_t)(std::upper_bound(t, t + 256, x) - t - 1);
-}
 float bm25_idf(uint64_t df, uint64_t n_docs) {
   float x = ((float)(n_docs - df) + 0.5f) / ((float)df + 0.5f);
   return logf(1.0f + x);
@@ -107,27 +102,29 @@ float term_score_host(uint32_t tfp, uint32_t fn_t, uint32_t fn_n, float wt, floa
   return s;
 }
 
-// FUGU_BUILD_TRACE=1: per-phase wall time of a snapshot build on stderr
-struct BuildTrace {
-  bool on = false;
-  std::chrono::steady_clock::time_point t;
-  void start() {
-    on = getenv("FUGU_BUILD_TRACE") != nullptr;
-    t = std::chrono::steady_clock::now();
-  }
-  void mark(const char* what) {
-    if (!on) return;
-    const auto n = std::chrono::steady_clock::now();
-    // @: the phase's end on the steady clock (ms; Python's time.monotonic), to line
-    // phases up with other threads' events (tools/stall_trace.py)
-    fprintf(stderr, "[fg build] %-24s %9.1f ms @%.3f\n", what, std::chrono::duration<double, std::milli>(n - t).count(),
-            std::chrono::duration<double, std::milli>(n.time_since_epoch()).count());
-    t = n;
-  }
-};
-thread_local BuildTrace g_bt;
-
 }  // namespace
+
+uint8_t fgh::fieldnorm_id(uint64_t n) {
+  const uint32_t* t = fn_table().v;
+  uint32_t x = n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)n;
+  return (uint8_t)(std::upper_bound(t, t + 256, x) - t - 1);
+}
+
+thread_local fgh::BuildTrace fgh::g_bt;
+void fgh::BuildTrace::start() {
+  on = getenv("FUGU_BUILD_TRACE") != nullptr;
+  t = std::chrono::steady_clock::now();
+}
+void fgh::BuildTrace::mark(const char* what) {
+  if (!on) return;
+  const auto n = std::chrono::steady_clock::now();
+  // @: the phase's end on the steady clock (ms; Python's time.monotonic), to line
+  // phases up with other threads' events (tools/stall_trace.py)
+  fprintf(stderr, "[fg build] %-24s %9.1f ms @%.3f\n", what, std::chrono::duration<double, std::milli>(n - t).count(),
+          std::chrono::duration<double, std::milli>(n.time_since_epoch()).count());
+  t = n;
+}
+
 // Host threads for snapshot builds and planning: FUGU_THREADS when set; else
 // OMP_NUM_THREADS when it states a share above one (16 per GPU on the box; a
 // launcher's default of 1 -- torchrun sets it for every rank -- is not a CPU
@@ -300,28 +297,6 @@ hipError_t dev_malloc_async(void** p, size_t bytes, hipStream_t s) {
 }  // namespace fgh
 namespace {
 
-// Host-side postings before upload (merged text U name per term).
-struct HostPostings {
-  uint32_t n_docs = 0, n_terms = 0;
-  std::vector<uint64_t> off;      // [V+1]
-  std::vector<uint32_t> doc, tf;  // tf packed lo16 text / hi16 name
-  std::vector<uint32_t> df_text, df_name;
-  std::vector<uint8_t> fn_text, fn_name;
-  std::vector<uint32_t> alive;    // bitset, empty when no deletes
-  uint64_t tot[2] = {0, 0};
-  bool has_name = false;
-  // facet field: postings (docs only: IndexRecordOption::Basic) per facet term
-  uint32_t n_fterms = 0;
-  std::vector<uint64_t> foff{0};  // [VF+1]
-  std::vector<uint32_t> fdoc;
-  std::vector<uint32_t> df_facet;
-  uint64_t tot_f = 0;             // total_num_tokens(facet), duplicates included
-};
-
-}  // namespace
-
-namespace {
-
 // Snapshot builds and rescores run on the calling thread's own stream (never
 // the legacy null stream, which serialises with every other stream): a
 // commit's rescores of the older segments, its new segment's build and the
@@ -333,7 +308,8 @@ namespace {
 thread_local hipStream_t tl_build_stream = nullptr;
 thread_local int tl_background = 0;
 hipStream_t background_stream(int dev, uint32_t i);
-hipStream_t build_stream() {
+}  // namespace
+hipStream_t fgh::build_stream() {
   if (tl_build_stream) return tl_build_stream;
   if (tl_background) {
     thread_local const uint32_t mine = [] {
@@ -346,18 +322,18 @@ hipStream_t build_stream() {
   }
   return hipStreamPerThread;
 }
-#define kBuildStream build_stream()
+#define kBuildStream fgh::build_stream()
 
 // Does the calling thread work in the background (fg_thread_background, or a
 // rescore worker on a background stream)?
-bool on_background() { return tl_background || tl_build_stream; }
+bool fgh::on_background() { return tl_background || tl_build_stream; }
 // The workgroup cap of a background scoring's launches (fg::ScoreJob::grid_cap):
 // FUGU_BG_GRID workgroups per CU (default kBgGridPerCu; 0: no cap).  With the
 // K-th reuse (kth_reuse_bound) and one background stream, GET /search during
 // commits p99 0.37 -> 0.25 ms, 1.5x its idle p99 (profiles/r05/stall/bg_j2/);
 // before the reuse the cap had raised p99 (the capped k_ktop held its slots)
-constexpr uint32_t kBgGridPerCu = 2;
-uint32_t bg_grid_cap(int dev) {
+static constexpr uint32_t kBgGridPerCu = 2;
+uint32_t fgh::bg_grid_cap(int dev) {
   if (!on_background()) return 0;
   static const uint32_t per_cu = [] {
     const char* e = getenv("FUGU_BG_GRID");
@@ -371,6 +347,7 @@ uint32_t bg_grid_cap(int dev) {
   }
   return per_cu * (uint32_t)n_cu;
 }
+namespace {
 
 // A high-priority stream on device `dev` for the calling thread's searches (the
 // search path's own: its kernels are dispatched ahead of a commit's builds on
@@ -444,79 +421,65 @@ hipStream_t background_stream(int dev, uint32_t) {
   return st;
 }
 
-template <class T>
-int dev_upload(DevAllocs& m, const T* src, size_t n, T** out, uint64_t* bytes) {
-  size_t b = std::max<size_t>(n * sizeof(T), 16);
+}  // namespace
+
+int fgh::dev_upload_bytes(DevAllocs& m, const void* src, size_t n, void** out, uint64_t* bytes) {
+  size_t b = std::max<size_t>(n, 16);
   void* p = nullptr;
   if (fgh::dev_malloc(&p, b) != hipSuccess) return fail(FG_EOOM, "hipMalloc(%zu) failed", b);
   m.ptrs.push_back(p);
   if (n) {
-    HIPCHK(hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyHostToDevice, kBuildStream));
+    HIPCHK(hipMemcpyAsync(p, src, n, hipMemcpyHostToDevice, kBuildStream));
     HIPCHK(hipStreamSynchronize(kBuildStream));
   }
-  *out = static_cast<T*>(p);
+  *out = p;
   *bytes += b;
   return FG_OK;
 }
 
-// Several host arrays into ONE device allocation (one hipMalloc instead of one
-// per array: a small segment's build is otherwise dominated by allocation).
-struct UploadBatch {
-  struct E { const void* src; size_t bytes; void** out; };
-  std::vector<E> es;
-  size_t total = 0;
-  template <class T>
-  void add(const T* src, size_t n, T** out) {
-    es.push_back(E{src, n * sizeof(T), reinterpret_cast<void**>(out)});
-    total += (std::max<size_t>(n * sizeof(T), 16) + 16 + 255) & ~size_t(255);  // >= 16 B of slack after each array
-  }
-  int commit(DevAllocs& m, uint64_t* bytes) {
-    void* p = nullptr;
-    if (fgh::dev_malloc(&p, std::max<size_t>(total, 256)) != hipSuccess) return fail(FG_EOOM, "hipMalloc(%zu) failed", total);
-    m.ptrs.push_back(p);
-    // the arrays laid out in a pooled pinned staging buffer by all host threads,
-    // then ONE copy: a small segment's arrays are sized by the vocabulary (~40 MB
-    // for 2^20 terms), and pageable copies of them -- staged by the runtime,
-    // beside a commit's rescores -- took ~16 ms of a 1000-doc segment's build
-    // (a bulk build's arrays are larger than the pool keeps: pageable copies)
-    PinnedLease pin(stage_pool(), total <= kStageMax ? total : 0);
-    if (pin.p && total <= kStageMax) {
-      struct Piece { char* dst; const char* src; size_t n; };
-      std::vector<Piece> pieces;
-      size_t o = 0;
-      for (const E& e : es) {
-        for (size_t b = 0; b < e.bytes; b += kStagePiece)
-          pieces.push_back(Piece{static_cast<char*>(pin.p) + o + b, static_cast<const char*>(e.src) + b,
-                                 std::min(kStagePiece, e.bytes - b)});
-        o += (std::max<size_t>(e.bytes, 16) + 16 + 255) & ~size_t(255);
-      }
-      parallel_dynamic((uint32_t)pieces.size(), std::min<int>(hw_threads(0), (int)pieces.size()), 1,
-                       [&](int, uint32_t b, uint32_t e) {
-        for (uint32_t i = b; i < e; ++i) std::memcpy(pieces[i].dst, pieces[i].src, pieces[i].n);
-      });
-      HIPCHK(hipMemcpyAsync(p, pin.p, total, hipMemcpyHostToDevice, kBuildStream));
-    }
+int fgh::UploadBatch::commit(DevAllocs& m, uint64_t* bytes) {
+  constexpr size_t kStagePiece = 1u << 20, kStageMax = 128ull << 20;
+  // process-wide: builds run on many threads (a commit's builder, the merger)
+  static PinnedPool stage_pool(256ull << 20);
+  void* p = nullptr;
+  if (fgh::dev_malloc(&p, std::max<size_t>(total, 256)) != hipSuccess) return fail(FG_EOOM, "hipMalloc(%zu) failed", total);
+  m.ptrs.push_back(p);
+  // the arrays laid out in a pooled pinned staging buffer by all host threads,
+  // then ONE copy: a small segment's arrays are sized by the vocabulary (~40 MB
+  // for 2^20 terms), and pageable copies of them -- staged by the runtime,
+  // beside a commit's rescores -- took ~16 ms of a 1000-doc segment's build
+  // (a bulk build's arrays are larger than the pool keeps: pageable copies)
+  PinnedLease pin(stage_pool, total <= kStageMax ? total : 0);
+  const bool staged = pin.p && total <= kStageMax;
+  if (staged) {
+    struct Piece { char* dst; const char* src; size_t n; };
+    std::vector<Piece> pieces;
     size_t o = 0;
     for (const E& e : es) {
-      char* d = static_cast<char*>(p) + o;
-      if (!(pin.p && total <= kStageMax) && e.bytes) HIPCHK(hipMemcpyAsync(d, e.src, e.bytes, hipMemcpyHostToDevice, kBuildStream));
-      *e.out = d;
-      o += (std::max<size_t>(e.bytes, 16) + 16 + 255) & ~size_t(255);
+      for (size_t b = 0; b < e.bytes; b += kStagePiece)
+        pieces.push_back(Piece{static_cast<char*>(pin.p) + o + b, static_cast<const char*>(e.src) + b,
+                               std::min(kStagePiece, e.bytes - b)});
+      o += slot(e.bytes);
     }
-    HIPCHK(hipStreamSynchronize(kBuildStream));
-    *bytes += total;
-    return FG_OK;
+    parallel_dynamic((uint32_t)pieces.size(), std::min<int>(hw_threads(0), (int)pieces.size()), 1,
+                     [&](int, uint32_t b, uint32_t e) {
+      for (uint32_t i = b; i < e; ++i) std::memcpy(pieces[i].dst, pieces[i].src, pieces[i].n);
+    });
+    HIPCHK(hipMemcpyAsync(p, pin.p, total, hipMemcpyHostToDevice, kBuildStream));
   }
-  static constexpr size_t kStagePiece = 1u << 20;
-  static constexpr size_t kStageMax = 128ull << 20;
-  // process-wide: builds run on many threads (a commit's builder, the merger)
-  static PinnedPool& stage_pool() {
-    static PinnedPool pool(256ull << 20);
-    return pool;
+  size_t o = 0;
+  for (const E& e : es) {
+    char* d = static_cast<char*>(p) + o;
+    if (!staged && e.bytes) HIPCHK(hipMemcpyAsync(d, e.src, e.bytes, hipMemcpyHostToDevice, kBuildStream));
+    *e.out = d;
+    o += slot(e.bytes);
   }
-};
+  HIPCHK(hipStreamSynchronize(kBuildStream));
+  *bytes += total;
+  return FG_OK;
+}
 
-int check_device(int dev) {
+static int check_device(int dev) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return fail(FG_ENODEV, "no HIP device visible");
   if (dev < 0 || dev >= n) return fail(FG_ENODEV, "device %d out of range (%d visible)", dev, n);
@@ -537,7 +500,7 @@ int check_device(int dev) {
 
 // BM25 weights of terms [0, V) for statistics (Ns, df_t, df_n) (tantivy's f32 order)
 // and their idfs (it, in: a phrase's weight sums them before the (1 + K1) factor)
-void bm25_weights(uint64_t Ns, const uint32_t* df_t, const uint32_t* df_n, uint32_t V, std::vector<float>& wt,
+void fgh::bm25_weights(uint64_t Ns, const uint32_t* df_t, const uint32_t* df_n, uint32_t V, std::vector<float>& wt,
                   std::vector<float>& wn, std::vector<float>& it, std::vector<float>& in) {
   wt.resize(V);
   wn.resize(V);
@@ -558,7 +521,7 @@ void bm25_weights(uint64_t Ns, const uint32_t* df_t, const uint32_t* df_n, uint3
 // shared precomputed ones of the same statistics, or nullptr: computed here),
 // the facet clause scores.  The device sees them only through plans (query-time
 // scoring: DevPlan::q_wt / q_wn and the plan's copy of the caches).
-void set_stats(fg_index* ix, uint64_t Ns, const uint64_t tot2[2], const uint32_t* df_t, const uint32_t* df_n,
+void fgh::set_stats(fg_index* ix, uint64_t Ns, const uint64_t tot2[2], const uint32_t* df_t, const uint32_t* df_n,
                uint64_t tot_f, const uint32_t* df_f, const fgh::Weights* wts) {
   const uint32_t V = ix->n_terms;
   ix->n_stats = Ns;
@@ -601,7 +564,7 @@ void set_stats(fg_index* ix, uint64_t Ns, const uint64_t tot2[2], const uint32_t
 // (tf + c[fn]) / (tf + c'[fn]); over tf >= 1 the second factor lies between 1
 // and its value at tf = 1, so per field it is bounded by the extremes over the
 // fieldnorm ids of (1 + c) / (1 + c').
-void relate_stats(fg_index* ix) {
+void fgh::relate_stats(fg_index* ix) {
   ix->same_stats = std::memcmp(ix->cache, ix->cache_b, sizeof ix->cache) == 0 &&
                    (ix->w_text.data() == ix->wb_text.data() || ix->w_text.vec() == ix->wb_text.vec()) &&
                    (ix->w_name.data() == ix->wb_name.data() || ix->w_name.vec() == ix->wb_name.vec());
@@ -617,8 +580,6 @@ void relate_stats(fg_index* ix) {
     ix->cdn[f] = dn;
   }
 }
-
-}  // namespace
 
 // Per-term bounds under the CURRENT statistics from the build-time tables
 // (shared by the planner, fg_index_term_kth and the byte models).
@@ -690,829 +651,6 @@ float term_kth_now(const fg_index* ix, uint32_t t, uint32_t k, bool with_floor) 
   return v;
 }
 }  // namespace fgh
-namespace {
-
-// k_ktop over the build's scores (j.psc, j.alive -> j.ktop, and j.ladder when
-// set): terms of <= kKtopChunk postings one workgroup each; longer terms in
-// kKtopChunk-posting chunks (k_ktop_part), then one select per term over its
-// chunks' best keys (k_ktop_big).  The chunk tables are the structure's; the key
-// scratch is one stream-ordered temporary (freeing it does not synchronize the
-// device: searches on other streams keep running).
-static int ktop_pass(const fg_index* ix, fg::ScoreJob& j) {
-  const size_t n_small = ix->n_kt, n_big = ix->n_kbig, n_chunks = ix->n_kchunks;
-  const size_t kck_b = (8ull * n_chunks * fg::kTopKs[fg::kNumTopK - 1] + 255) & ~size_t(255);
-  const size_t kcc_b = (4ull * n_chunks + 255) & ~size_t(255), kbs_b = 4ull * 3 * n_big;
-  void* ktmp = nullptr;
-  if (fgh::dev_malloc_async(&ktmp, kck_b + kcc_b + kbs_b + 16, kBuildStream) != hipSuccess)
-    return fail(FG_EOOM, "hipMallocAsync(%zu) failed", kck_b + kcc_b + kbs_b);
-  struct KtmpBack {
-    void* p;
-    ~KtmpBack() { (void)hipFreeAsync(p, kBuildStream); }
-  } ktmp_back{ktmp};
-  char* kb = static_cast<char*>(ktmp);
-  uint32_t* d_kbs = reinterpret_cast<uint32_t*>(kb + kck_b + kcc_b);
-  // per long term: alive postings 0, min alive score bits ~0, max 0 ([3][n_big])
-  if (n_big) {
-    HIPCHK(hipMemsetAsync(d_kbs, 0, 4ull * 3 * n_big, kBuildStream));
-    HIPCHK(hipMemsetD32Async(d_kbs + n_big, (int)0xFFFFFFFFu, n_big, kBuildStream));
-  }
-  j.kt_tiny = ix->d_kt_tiny;
-  j.n_tiny = ix->n_ktiny;
-  j.kt_terms = ix->d_kt_terms;
-  j.kb_terms = ix->d_kb_terms;
-  j.kb_chunk0 = ix->d_kb_chunk0;
-  j.kc_big = ix->d_kc_big;
-  j.kc_start = ix->d_kc_start;
-  j.kc_keys = reinterpret_cast<uint64_t*>(kb);
-  j.kc_cnt = reinterpret_cast<uint32_t*>(kb + kck_b);
-  j.kb_stat = d_kbs;
-  j.n_big = (uint32_t)n_big;
-  HIPCHK(fg::launch_ktop(j, (uint32_t)n_small, (uint32_t)n_chunks, (uint32_t)n_big, kBuildStream));
-  return FG_OK;
-}
-
-// Every posting's score under the snapshot's CURRENT statistics (k_score) into
-// `psc` (a build's bound block) or a stream-ordered temporary, for the bound
-// kernels of a build and for fg_index_term_ladder.  `tmp` returns the temporary
-// (freed stream-ordered by the caller); j gets the postings inputs, the weights
-// and caches (inside tmp) and j.psc / j.cmax (cmax: the caller's, or a scratch
-// part of tmp).
-static int score_postings(const fg_index* ix, fg::ScoreJob& j, float* cmax, float* psc, void** tmp) {
-  const uint32_t V = ix->n_terms;
-  auto al = [](size_t x) { return (std::max<size_t>(x, 16) + 255) & ~size_t(255); };
-  const size_t b_psc = psc ? 0 : al(4ull * ix->n_postings + 16), b_w = al(4ull * V), b_c = al(4ull * 512),
-               b_cm = cmax ? 0 : al(4ull * ix->n_sc);
-  if (fgh::dev_malloc_async(tmp, b_psc + 2 * b_w + b_c + b_cm, kBuildStream) != hipSuccess)
-    return fail(FG_EOOM, "hipMallocAsync(%zu) failed", b_psc + 2 * b_w + b_c + b_cm);
-  char* t = static_cast<char*>(*tmp);
-  float* d_psc = psc ? psc : reinterpret_cast<float*>(t);
-  float* d_wt = reinterpret_cast<float*>(t + b_psc);
-  float* d_wn = reinterpret_cast<float*>(t + b_psc + b_w);
-  float* d_cache = reinterpret_cast<float*>(t + b_psc + 2 * b_w);
-  HIPCHK(hipMemcpyAsync(d_wt, ix->w_text.data(), 4ull * V, hipMemcpyHostToDevice, kBuildStream));
-  HIPCHK(hipMemcpyAsync(d_wn, ix->w_name.data(), 4ull * V, hipMemcpyHostToDevice, kBuildStream));
-  HIPCHK(hipMemcpyAsync(d_cache, ix->cache, 4ull * 512, hipMemcpyHostToDevice, kBuildStream));
-  j.doc = ix->d.doc;
-  j.tfn = ix->d.tfn;
-  j.tfn_name = ix->d.tfn_name;
-  j.esc_pos = ix->d.esc_pos;
-  j.esc_tf = ix->d.esc_tf;
-  j.n_esc = ix->d.n_esc;
-  j.off = ix->d.off;
-  j.dir = ix->d.dir;
-  j.dir_off = ix->d.dir_off;
-  j.tmeta = ix->d.tmeta;
-  j.toff = ix->d.toff;
-  j.w_text = d_wt;
-  j.w_name = d_wn;
-  j.cache = d_cache;
-  j.psc = d_psc;
-  j.cmax = cmax ? cmax : reinterpret_cast<float*>(t + b_psc + 2 * b_w + b_c);
-  j.coff = ix->d.coff;
-  j.sc_tf = ix->d_sc_tf;
-  j.sc_tl = ix->d_sc_tl;
-  j.sc_e0 = ix->d_sc_e0;
-  j.sc_e1 = ix->d_sc_e1;
-  j.n_terms = V;
-  j.grid_cap = bg_grid_cap(ix->dev);
-  HIPCHK(fg::launch_score(j, ix->n_scb, kBuildStream));
-  return FG_OK;
-}
-
-// The bounds of a freshly built structure under its build statistics (which
-// are its current ones): the posting scores into a temporary (k_score, with the
-// block-max per 2048 postings), bucket / term / tile maxima (k_bucket), sub-tile
-// maxima (k_tsub), per-term K-th best alive scores (k_ktop), and the read-back
-// of tmaxs / ktop for the planner.  Once per build or merge: a commit's
-// rescores of older segments share them (rescore_one).
-int build_bounds(fg_index* ix, const std::vector<uint32_t>& alive) {
-  const uint32_t V = ix->n_terms;
-  HIPCHK(hipSetDevice(ix->dev));
-  struct Part { size_t bytes; void** out; };
-  float *d_psc, *d_bmax, *d_ktop, *d_cmax;
-  uint64_t* d_tsub = nullptr;
-  uint32_t *d_alive = nullptr, *d_tmaxs, *d_tmax;
-  const Part parts[] = {
-      {4ull * ix->n_postings + 16, reinterpret_cast<void**>(&d_psc)},  // 16 B of slack after the scores
-      {alive.empty() ? 0 : 4ull * alive.size(), reinterpret_cast<void**>(&d_alive)},
-      {4ull * ix->dir_entries, reinterpret_cast<void**>(&d_bmax)},
-      {4ull * V, reinterpret_cast<void**>(&d_tmaxs)},
-      {4ull * ix->tile_entries, reinterpret_cast<void**>(&d_tmax)},
-      {4ull * V * fg::kNumTopK, reinterpret_cast<void**>(&d_ktop)},
-      {4ull * ix->n_sc, reinterpret_cast<void**>(&d_cmax)},
-      {8ull * ix->tile_entries, reinterpret_cast<void**>(&d_tsub)},
-  };
-  size_t total = 0;
-  for (const Part& pt : parts) total += (std::max<size_t>(pt.bytes, 16) + 255) & ~size_t(255);
-  if (!ix->spool) {
-    ix->spool = std::make_shared<fgh::ScorePool>();
-    ix->spool->dev = ix->dev;
-  }
-  auto sb = std::make_shared<fgh::ScoreBlock>();
-  char* blk = static_cast<char*>(ix->spool->get(total));
-  if (!blk) return fail(FG_EOOM, "bound tables: hipMalloc(%zu) failed", total);
-  sb->p = blk;
-  sb->bytes = total;
-  sb->pool = ix->spool;
-  ix->sblock = sb;
-  {
-    size_t o = 0;
-    for (const Part& pt : parts) {
-      *pt.out = pt.bytes ? blk + o : nullptr;
-      o += (std::max<size_t>(pt.bytes, 16) + 255) & ~size_t(255);
-    }
-  }
-  if (d_alive) HIPCHK(hipMemcpyAsync(d_alive, alive.data(), 4ull * alive.size(), hipMemcpyHostToDevice, kBuildStream));
-  HIPCHK(hipMemsetAsync(d_tmaxs, 0, 4ull * V, kBuildStream));
-  HIPCHK(hipMemsetAsync(d_tmax, 0, std::max<size_t>(4ull * ix->tile_entries, 16), kBuildStream));
-  HIPCHK(hipMemsetAsync(d_ktop, 0, 4ull * V * fg::kNumTopK, kBuildStream));
-  g_bt.mark("bound tables + uploads");
-  fg::ScoreJob j{};
-  void* tmp = nullptr;
-  if (int rc = score_postings(ix, j, d_cmax, d_psc, &tmp)) return rc;
-  struct TmpBack {
-    void* p;
-    ~TmpBack() { (void)hipFreeAsync(p, kBuildStream); }
-  } tmp_back{tmp};
-  j.alive = d_alive;
-  j.bmax = d_bmax;
-  j.tmaxs = d_tmaxs;
-  j.tmax = d_tmax;
-  j.ktop = d_ktop;
-  j.bk_tf = ix->d_bk_tf;
-  j.bk_tl = ix->d_bk_tl;
-  j.bk_e0 = ix->d_bk_e0;
-  j.bk_e1 = ix->d_bk_e1;
-  j.n_dir = ix->dir_entries;
-  HIPCHK(fg::launch_bucket(j, ix->n_bk, ix->n_docs, kBuildStream));
-  j.tsub = d_tsub;
-  j.tterm = ix->d_tterm;
-  j.n_tterm = ix->n_tterm;
-  j.n_tiles = ix->n_tiles;
-  HIPCHK(fg::launch_tsub(j, ix->n_docs, kBuildStream));
-  if (int rc = ktop_pass(ix, j)) return rc;
-  g_bt.mark("bound launches");
-  // tmaxs [V] then ktop [V * kNumTopK], read straight into a pooled pinned block
-  {
-    const size_t hb = 4ull * V * (1 + fg::kNumTopK);
-    float* h = static_cast<float*>(ix->spool->get_host(hb));
-    if (h) {
-      sb->hp = h;
-      sb->hbytes = hb;
-    } else {
-      sb->hown.resize((size_t)V * (1 + fg::kNumTopK));
-      h = sb->hown.data();
-    }
-    if (on_background() && sb->hp) {
-      // a background build: the read-back as a copy kernel of short workgroups
-      // on its low-priority stream (pinned host memory is device-visible), not a
-      // copy-engine transfer (those held searches up: tools/rescore_stall.py)
-      HIPCHK(fg::launch_copy32(reinterpret_cast<uint32_t*>(h), d_tmaxs, V, j.grid_cap, kBuildStream));
-      HIPCHK(fg::launch_copy32(reinterpret_cast<uint32_t*>(h + V), reinterpret_cast<const uint32_t*>(d_ktop),
-                               (uint64_t)V * fg::kNumTopK, j.grid_cap, kBuildStream));
-    } else {
-      HIPCHK(hipMemcpyAsync(h, d_tmaxs, 4ull * V, hipMemcpyDeviceToHost, kBuildStream));
-      HIPCHK(hipMemcpyAsync(h + V, d_ktop, 4ull * V * fg::kNumTopK, hipMemcpyDeviceToHost, kBuildStream));
-    }
-    HIPCHK(hipStreamSynchronize(kBuildStream));
-    ix->tmaxs = h;
-    ix->ktop = h + V;
-  }
-  g_bt.mark("device bounds");
-  // the build's statistics are the bounds' reference
-  ix->wb_text = ix->w_text;
-  ix->wb_name = ix->w_name;
-  std::memcpy(ix->cache_b, ix->cache, sizeof ix->cache);
-  ix->h_alive = alive;
-  ix->h_alive_b = ix->h_alive;
-  ix->n_dead = 0;
-  relate_stats(ix);
-  ix->d.psc = d_psc;
-  ix->d.bmax = d_bmax;
-  ix->d.tmaxs = reinterpret_cast<const float*>(d_tmaxs);
-  ix->d.tmax = reinterpret_cast<const float*>(d_tmax);
-  ix->d.tsub = d_tsub;
-  ix->d.cmax = d_cmax;
-  ix->d.alive = d_alive;
-  ix->device_bytes = ix->struct_bytes + total;
-  return FG_OK;
-}
-
-// The statistics-independent half of a snapshot (postings, tf, fieldnorm ids,
-// bucket directory, rank words, facet postings, chunk tables) is uploaded into
-// ix->smem, then score_index computes the rest.  Consumes hp.  g: global
-// statistics of a doc-sharded namespace (NULL: the shard's own).
-int finish_index(int dev, HostPostings& hp, bool keep_host, fg_index** out, const fg_global_stats* g = nullptr) {
-  auto ix = std::make_unique<fg_index>();
-  ix->dev = dev;
-  ix->mem.dev = dev;
-  fgh::device_pools(dev, &ix->pool, &ix->pinned);
-  ix->smem = std::make_shared<DevAllocs>();
-  ix->smem->dev = dev;
-  ix->n_docs = hp.n_docs;
-  ix->n_terms = hp.n_terms;
-  ix->n_vocab = hp.n_terms;
-  ix->has_name = hp.has_name;
-  ix->n_postings = hp.off[hp.n_terms];
-  ix->tot_local[0] = hp.tot[0];
-  ix->tot_local[1] = hp.tot[1];
-  const uint64_t N = hp.n_docs;  // docs of this shard (array sizes)
-  const uint32_t V = hp.n_terms;
-  if (g && g->df_name == nullptr && hp.has_name) return fail(FG_EINVAL, "global statistics lack df_name for a shard with names");
-  // doc -> position bucket directory (fg_internal.h DevIndex): bucket width
-  // 2^B_t docs with B_t the largest shift keeping ~kBucketTarget postings per bucket
-  std::vector<uint32_t> dir_off(V), tmeta(V);
-  uint64_t nd = 0;
-  for (uint32_t t = 0; t < V; ++t) {
-    const uint64_t n = hp.off[t + 1] - hp.off[t];
-    uint32_t B = 0;
-    if (n == 0) B = 31;
-    else while (B < 31 && (n << (B + 1)) <= (uint64_t)fg::kBucketTarget * N) ++B;
-    const uint64_t nbk = ((N - 1) >> B) + 1;
-    if (nd > 0xFFFFFFFFull) return fail(FG_EINVAL, "directory too large");
-    dir_off[t] = (uint32_t)nd;
-    tmeta[t] = B;
-    nd += nbk + 1;
-  }
-  std::vector<uint32_t> dir(nd);
-  // term ranges of about equal work (postings + a per-term constant): a million
-  // mostly empty terms of a small segment cost one range grab per range, not
-  // one per term, and the densest terms still spread over the threads
-  std::vector<uint32_t> cuts{0};
-  {
-    const int nth = hw_threads(0);
-    const uint64_t tot = hp.off[V] + 64ull * V, step = std::max<uint64_t>(1, tot / (uint64_t)(nth * 16));
-    uint64_t acc = 0;
-    for (uint32_t t = 0; t < V; ++t) {
-      acc += (hp.off[t + 1] - hp.off[t]) + 64;
-      if (acc >= step) { cuts.push_back(t + 1); acc = 0; }
-    }
-    if (cuts.back() != V) cuts.push_back(V);
-  }
-  parallel_dynamic((uint32_t)cuts.size() - 1, hw_threads(0), 1, [&](int, uint32_t rb, uint32_t re) {
-    for (uint32_t t = cuts[rb]; t < cuts[re]; ++t) {
-      const uint64_t b0 = hp.off[t], n = hp.off[t + 1] - b0;
-      const uint32_t B = tmeta[t];
-      const uint64_t nbk = ((N - 1) >> B) + 1;
-      uint32_t* dt = dir.data() + dir_off[t];
-      uint64_t p = 0;
-      uint32_t maxocc = 0;
-      for (uint64_t b = 0; b <= nbk; ++b) {
-        const uint64_t lo = b << B;
-        const uint64_t p0 = p;
-        while (p < n && hp.doc[b0 + p] < lo) ++p;
-        dt[b] = (uint32_t)p;
-        if (b) maxocc = std::max<uint32_t>(maxocc, (uint32_t)(p - p0));
-      }
-      uint32_t S = 0;
-      while ((1ull << S) <= maxocc) ++S;  // 2^S > largest bucket
-      tmeta[t] = B | (S << 8);
-    }
-  });
-  g_bt.mark("directory");
-  // per-term tile maxima (4096-doc tiles of k_disj) for terms whose buckets are
-  // no wider than a tile: one load gives a clause's bound over a tile; and the
-  // tile directory beside them: tdir[toff + i] = the first posting of tile i
-  // (n_tiles + 1 entries per term, the last = df), so a tile's posting range
-  // is two adjacent loads -- 32 tiles per line, where the bucket directory puts
-  // a dense term's consecutive tile boundaries 4096 >> B_t entries apart
-  std::vector<uint32_t> toff(V, 0xFFFFFFFFu);
-  const uint64_t n_tiles = ((uint64_t)N + (1u << fg::kDisjTileShift) - 1) >> fg::kDisjTileShift;
-  uint64_t ntm = 0;
-  for (uint32_t t = 0; t < V; ++t)
-    if ((tmeta[t] & 0xFFu) <= fg::kDisjTileShift && hp.off[t + 1] > hp.off[t]) {
-      if (ntm + n_tiles + 1 > 0xFFFFFFFFull) break;
-      toff[t] = (uint32_t)ntm;
-      ntm += n_tiles + 1;
-    }
-  std::vector<uint32_t> tdir(ntm);
-  std::vector<uint32_t> tterm;  // the tile-table terms in toff order (k_tsub)
-  tterm.reserve(ntm / (n_tiles + 1));
-  for (uint32_t t = 0; t < V; ++t)
-    if (toff[t] != 0xFFFFFFFFu) tterm.push_back(t);
-  parallel_dynamic(V, hw_threads(0), 64, [&](int, uint32_t tb, uint32_t te) {
-    for (uint32_t t = tb; t < te; ++t) {
-      if (toff[t] == 0xFFFFFFFFu) continue;
-      const uint32_t B = tmeta[t] & 0xFFu;
-      const uint64_t nbk = ((N - 1) >> B) + 1;
-      const uint32_t* dt = dir.data() + dir_off[t];
-      for (uint64_t i = 0; i <= n_tiles; ++i)
-        tdir[toff[t] + i] = dt[std::min<uint64_t>(i << (fg::kDisjTileShift - B), nbk)];
-    }
-  });
-  ix->dir_entries = nd;
-  ix->tile_entries = ntm;
-  // chunk tables of the scoring kernels: (term, first posting) per <= kScoreChunk
-  // postings, (term, first bucket) per <= kBucketChunk buckets, terms with postings
-  // and of k_ktop (they depend on the postings only, so every rescore reuses
-  // them): terms of <= kKtopChunk postings one workgroup each (kt); longer terms
-  // (kb_terms) in kKtopChunk-posting chunks (kc_big / kc_start, the chunks of
-  // long term x from kb_chunk0[x])
-  // k_score / k_bucket chunks are PACKED: a long term's slice of kScoreChunk
-  // postings (kBucketChunk directory entries), or several whole short terms
-  // (<= kPackTerms term ids, <= a slice's postings / entries together) -- the
-  // long tail of a vocabulary in a workgroup per term was most of a small
-  // segment's scoring time
-  std::vector<uint32_t> kt, kt_tiny, coff(V), kb_terms, kb_chunk0, kc_big, kc_start;
-  std::vector<uint32_t> sc_tf, sc_tl, bk_tf, bk_tl, bk_e0, bk_e1;
-  std::vector<uint64_t> sc_e0, sc_e1;
-  uint32_t n_cmax = 0;
-  {
-    // postings: pack [pt0, t) open while short terms fit
-    uint32_t pt0 = 0;
-    uint64_t pe0 = 0;
-    bool open = false;
-    auto flush_sc = [&](uint32_t t_end) {  // terms [pt0, t_end)
-      if (!open) return;
-      sc_tf.push_back(pt0);
-      sc_tl.push_back(t_end - 1);
-      sc_e0.push_back(pe0);
-      sc_e1.push_back(hp.off[t_end]);
-      open = false;
-    };
-    for (uint32_t t = 0; t < V; ++t) {
-      const uint64_t n = hp.off[t + 1] - hp.off[t];
-      coff[t] = n_cmax;  // the term's first block-max entry (DevIndex::cmax: kChunk postings each)
-      n_cmax += (uint32_t)((n + fg::kChunk - 1) / fg::kChunk);
-      if (n >= fg::kScoreChunk) {
-        flush_sc(t);
-        for (uint64_t f = 0; f < n; f += fg::kScoreChunk) {
-          sc_tf.push_back(t);
-          sc_tl.push_back(t);
-          sc_e0.push_back(hp.off[t] + f);
-          sc_e1.push_back(hp.off[t] + std::min<uint64_t>(n, f + fg::kScoreChunk));
-        }
-        continue;
-      }
-      if (open && (hp.off[t + 1] - pe0 > fg::kScoreChunk || t - pt0 >= fg::kPackTerms)) flush_sc(t);
-      if (!open) {
-        pt0 = t;
-        pe0 = hp.off[t];
-        open = true;
-      }
-    }
-    flush_sc(V);
-  }
-  {
-    // directory entries (each term: its nbk buckets + the end entry)
-    uint32_t pt0 = 0, pe0 = 0;
-    bool open = false;
-    auto flush_bk = [&](uint32_t t_end) {
-      if (!open) return;
-      bk_tf.push_back(pt0);
-      bk_tl.push_back(t_end - 1);
-      bk_e0.push_back(pe0);
-      bk_e1.push_back(t_end < V ? dir_off[t_end] : (uint32_t)nd);
-      open = false;
-    };
-    for (uint32_t t = 0; t < V; ++t) {
-      const uint32_t ne = (t + 1 < V ? dir_off[t + 1] : (uint32_t)nd) - dir_off[t];  // nbk + 1
-      if (ne > fg::kBucketChunk) {
-        flush_bk(t);
-        for (uint32_t f = 0; f < ne; f += fg::kBucketChunk) {
-          bk_tf.push_back(t);
-          bk_tl.push_back(t);
-          bk_e0.push_back(dir_off[t] + f);
-          bk_e1.push_back(dir_off[t] + std::min<uint32_t>(ne, f + fg::kBucketChunk));
-        }
-        continue;
-      }
-      if (open && (dir_off[t] + ne - pe0 > fg::kBucketChunk || t - pt0 >= fg::kPackTerms)) flush_bk(t);
-      if (!open) {
-        pt0 = t;
-        pe0 = dir_off[t];
-        open = true;
-      }
-    }
-    flush_bk(V);
-  }
-  for (uint32_t t = 0; t < V; ++t) {
-    const uint64_t n = hp.off[t + 1] - hp.off[t];
-    if (!n) continue;
-    if (n <= fg::kKtopTiny) {
-      kt_tiny.push_back(t);
-      continue;
-    }
-    if (n <= fg::kKtopChunk) {
-      kt.push_back(t);
-      continue;
-    }
-    kb_chunk0.push_back((uint32_t)kc_big.size());
-    for (uint64_t st = 0; st < n; st += fg::kKtopChunk) {
-      kc_big.push_back((uint32_t)kb_terms.size());
-      kc_start.push_back((uint32_t)st);
-    }
-    kb_terms.push_back(t);
-  }
-  kb_chunk0.push_back((uint32_t)kc_big.size());
-  if (sc_tf.size() > 0x7FFFFFFFull || bk_tf.size() > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "index too large");
-  HIPCHK(hipSetDevice(dev));
-  DevAllocs& sm = *ix->smem;
-  uint64_t& bytes = ix->struct_bytes;
-  int rc;
-  uint32_t *d_doc, *d_dir, *d_dir_off, *d_tmeta, *d_toff, *d_tdir, *d_fdoc, *d_tterm, *d_esc_tf = nullptr;
-  uint16_t *d_tfn = nullptr, *d_tfn_name = nullptr;
-  uint64_t* d_esc_pos = nullptr;
-  uint64_t *d_off, *d_foff;
-  uint32_t *d_sctf, *d_sctl, *d_bktf, *d_bktl, *d_bke0, *d_bke1, *d_kt, *d_ktt, *d_coff, *d_kbt, *d_kb0, *d_kcb, *d_kcs;
-  uint64_t *d_sce0, *d_sce1;
-  // the postings' payloads (DevIndex::tfn): per field (fieldnorm id of the doc
-  // << 8) | tf, 2 B per posting -- what a query-time score needs besides the
-  // clause's weight, beside the doc id -- and the postings whose tf does not fit
-  // the byte (>= 255) in a sorted escape list
-  std::vector<uint16_t> tfn(hp.tf.size()), tfn_name(hp.has_name ? hp.tf.size() : 0);
-  std::vector<uint64_t> esc_pos;
-  std::vector<uint32_t> esc_tf;
-  {
-    const size_t np = hp.tf.size(), piece = (np + 1023) / 1024;  // > 2^32 postings: 64-bit pieces
-    std::vector<std::vector<uint64_t>> ep(1024);
-    parallel_dynamic(1024, hw_threads(0), 8, [&](int, uint32_t b, uint32_t e) {
-      for (uint32_t pc = b; pc < e; ++pc)
-        for (size_t i = (size_t)pc * piece; i < std::min(np, (size_t)(pc + 1) * piece); ++i) {
-          const uint32_t d = hp.doc[i], tt = hp.tf[i] & 0xFFFFu, tn = hp.tf[i] >> 16;
-          tfn[i] = (uint16_t)fg::tfn_pack(tt, hp.fn_text[d]);
-          if (hp.has_name) tfn_name[i] = (uint16_t)(tn ? fg::tfn_pack(tn, hp.fn_name[d]) : 0u);
-          if (tt >= fg::kTfEsc || (hp.has_name && tn >= fg::kTfEsc)) ep[pc].push_back(i);
-        }
-    });
-    for (auto& v : ep)
-      for (uint64_t i : v) {
-        esc_pos.push_back(i);
-        esc_tf.push_back(hp.tf[i]);
-      }
-  }
-  {
-    UploadBatch ub;
-    ub.add(hp.doc.data(), hp.doc.size(), &d_doc);
-    ub.add(tfn.data(), tfn.size(), &d_tfn);
-    if (hp.has_name) ub.add(tfn_name.data(), tfn_name.size(), &d_tfn_name);
-    if (!esc_pos.empty()) {
-      ub.add(esc_pos.data(), esc_pos.size(), &d_esc_pos);
-      ub.add(esc_tf.data(), esc_tf.size(), &d_esc_tf);
-    }
-    ub.add(hp.off.data(), hp.off.size(), &d_off);
-    ub.add(dir.data(), dir.size(), &d_dir);
-    ub.add(dir_off.data(), dir_off.size(), &d_dir_off);
-    ub.add(toff.data(), toff.size(), &d_toff);
-    ub.add(tdir.data(), tdir.size(), &d_tdir);
-    ub.add(tterm.data(), tterm.size(), &d_tterm);
-    ub.add(hp.fdoc.data(), hp.fdoc.size(), &d_fdoc);
-    ub.add(hp.foff.data(), hp.foff.size(), &d_foff);
-    ub.add(sc_tf.data(), sc_tf.size(), &d_sctf);
-    ub.add(sc_tl.data(), sc_tl.size(), &d_sctl);
-    ub.add(sc_e0.data(), sc_e0.size(), &d_sce0);
-    ub.add(sc_e1.data(), sc_e1.size(), &d_sce1);
-    ub.add(bk_tf.data(), bk_tf.size(), &d_bktf);
-    ub.add(bk_tl.data(), bk_tl.size(), &d_bktl);
-    ub.add(bk_e0.data(), bk_e0.size(), &d_bke0);
-    ub.add(bk_e1.data(), bk_e1.size(), &d_bke1);
-    ub.add(kt.data(), kt.size(), &d_kt);
-    ub.add(kt_tiny.data(), kt_tiny.size(), &d_ktt);
-    ub.add(kb_terms.data(), kb_terms.size(), &d_kbt);
-    ub.add(kb_chunk0.data(), kb_chunk0.size(), &d_kb0);
-    ub.add(kc_big.data(), kc_big.size(), &d_kcb);
-    ub.add(kc_start.data(), kc_start.size(), &d_kcs);
-    ub.add(coff.data(), coff.size(), &d_coff);
-    if ((rc = ub.commit(sm, &bytes))) return rc;
-  }
-  std::vector<uint16_t>().swap(tfn);
-  std::vector<uint16_t>().swap(tfn_name);
-  std::vector<uint32_t>().swap(hp.tf);
-  std::vector<uint32_t>().swap(dir);
-  std::vector<uint32_t>().swap(tdir);
-  g_bt.mark("upload");
-  // rank words (fg_internal.h DevIndex) for the terms with df >= N / kRankDiv,
-  // densest first (ties by term id), within a budget of the snapshot's own:
-  // FUGU_RANK_FACTOR (default kRankFactor) times its postings' bytes (doc id +
-  // tf + score, 12 B each), at most FUGU_RANK_GIB -- so a namespace's share
-  // depends on its size, not on how many namespaces were built on the device
-  // before it.  A term with df >= N / kRankPlainDiv (FUGU_RANK_PLAIN_DIV) gets
-  // plain rank words (8 B per 32 docs), a sparser one sparse rank words (8 B per
-  // 1024-doc block + 8 B per word holding any of its docs) unless plain ones
-  // cost it less (small snapshots).  A quarter of the free memory caps them
-  // only when HBM is short, and a failed allocation is retried with half the
-  // terms (down to none), so a build never fails for want of them.  They hang
-  // on doc ids only, so rescored snapshots share them.
-  std::vector<uint32_t> by_df;
-  for (uint32_t t = 0; t < V; ++t)
-    if (hp.off[t + 1] > hp.off[t] && (hp.off[t + 1] - hp.off[t]) * fg::kRankDiv >= N) by_df.push_back(t);
-  std::stable_sort(by_df.begin(), by_df.end(), [&](uint32_t a, uint32_t b) {
-    return hp.off[a + 1] - hp.off[a] > hp.off[b + 1] - hp.off[b];
-  });
-  const uint32_t rank_words = (uint32_t)((N + 31) / 32), sblocks = (N + 1023) / 1024;
-  const uint32_t pdiv = [] {
-    const char* e = getenv("FUGU_RANK_PLAIN_DIV");
-    return e && *e ? (uint32_t)std::max(1l, atol(e)) : fg::kRankPlainDiv;
-  }();
-  auto plain_df = [&](uint32_t t) { return (hp.off[t + 1] - hp.off[t]) * pdiv >= N; };
-  // the words of each sparse candidate that hold any of its docs
-  std::vector<uint32_t> nwords(by_df.size(), 0);
-  parallel_dynamic((uint32_t)by_df.size(), hw_threads(0), 16, [&](int, uint32_t b, uint32_t e) {
-    for (uint32_t i = b; i < e; ++i) {
-      const uint32_t t = by_df[i];
-      if (plain_df(t)) continue;
-      uint32_t n = 0, last = 0xFFFFFFFFu;
-      for (uint64_t p = hp.off[t]; p < hp.off[t + 1]; ++p) {
-        const uint32_t w = hp.doc[p] >> 5;
-        n += w != last;
-        last = w;
-      }
-      nwords[i] = n;
-    }
-  });
-  std::vector<uint32_t> rank_terms, sparse_terms, sparse_nw;
-  uint64_t* d_rank = nullptr;
-  uint64_t* d_srank = nullptr;
-  uint64_t n_swords = 0;
-  {
-    const char* v = getenv("FUGU_RANK_GIB");
-    const uint64_t cap = v && *v ? (uint64_t)(atof(v) * (double)(1ull << 30)) : fg::kRankBudget;
-    const char* f = getenv("FUGU_RANK_FACTOR");
-    const double factor = f && *f ? atof(f) : fg::kRankFactor;
-    const uint64_t want = std::min<uint64_t>(cap, (uint64_t)(factor * 12.0 * (double)hp.off[V]));
-    size_t free_b = ~size_t(0), total_b = 0;
-    if (want > (256ull << 20)) HIPCHK(hipMemGetInfo(&free_b, &total_b));  // (~1 ms: not for a small segment's)
-    const uint64_t brk = std::min<uint64_t>(want, free_b / 4);
-    uint64_t used = 0;
-    for (size_t i = 0; i < by_df.size(); ++i) {
-      const uint64_t cp = rank_words * 8ull, cs = (sblocks + (uint64_t)nwords[i]) * 8ull;
-      const bool plain = plain_df(by_df[i]) || cp <= cs;
-      const uint64_t c = plain ? cp : cs;
-      if (used + c > brk || rank_terms.size() + sparse_terms.size() >= fg::kMaxDense) break;
-      if (!plain && n_swords + nwords[i] >= 0xFFFFFFFFull) break;  // srank_w indices are u32
-      used += c;
-      if (plain) {
-        rank_terms.push_back(by_df[i]);
-      } else {
-        sparse_terms.push_back(by_df[i]);
-        sparse_nw.push_back(nwords[i]);
-        n_swords += nwords[i];
-      }
-    }
-    while (!rank_terms.empty()) {
-      void* q = nullptr;
-      if (fgh::dev_malloc(&q, rank_words * 8ull * rank_terms.size()) == hipSuccess) {
-        sm.ptrs.push_back(q);
-        bytes += rank_words * 8ull * rank_terms.size();
-        d_rank = static_cast<uint64_t*>(q);
-        break;
-      }
-      (void)hipGetLastError();
-      rank_terms.resize(rank_terms.size() / 2);
-    }
-    while (!sparse_terms.empty()) {
-      const uint64_t sb = (sblocks * (uint64_t)sparse_terms.size() + 1 + n_swords) * 8ull;
-      void* q = nullptr;
-      if (fgh::dev_malloc(&q, sb) == hipSuccess) {
-        sm.ptrs.push_back(q);
-        bytes += sb;
-        d_srank = static_cast<uint64_t*>(q);
-        break;
-      }
-      (void)hipGetLastError();
-      sparse_terms.resize(sparse_terms.size() / 2);
-      sparse_nw.resize(sparse_terms.size());
-      n_swords = 0;
-      for (uint32_t n : sparse_nw) n_swords += n;
-    }
-  }
-  g_bt.mark("rank words: budget");
-  if (!sparse_terms.empty()) {
-    // built on the host from the postings: per term its block entries, then
-    // the zero word and all terms' words (term by term), one upload
-    const uint32_t ns = (uint32_t)sparse_terms.size();
-    const uint32_t first_slot = (uint32_t)rank_terms.size() + 1;
-    std::vector<uint64_t> wbase(ns + 1, 1);
-    for (uint32_t s2 = 0; s2 < ns; ++s2) wbase[s2 + 1] = wbase[s2] + sparse_nw[s2];
-    std::vector<uint64_t> hs(sblocks * (uint64_t)ns + 1 + n_swords);
-    hs[sblocks * (uint64_t)ns] = 0;
-    parallel_dynamic(ns, hw_threads(0), 16, [&](int, uint32_t b, uint32_t e) {
-      for (uint32_t s2 = b; s2 < e; ++s2) {
-        const uint32_t t = sparse_terms[s2];
-        uint64_t* blk = hs.data() + (uint64_t)s2 * sblocks;
-        uint64_t* wd = hs.data() + (uint64_t)ns * sblocks;
-        std::fill(blk, blk + sblocks, 0ull);
-        uint64_t cur = wbase[s2];
-        uint32_t last = 0xFFFFFFFFu;
-        for (uint64_t p = hp.off[t]; p < hp.off[t + 1]; ++p) {
-          const uint32_t d = hp.doc[p], w = d >> 5;
-          if (w != last) {
-            if (last != 0xFFFFFFFFu) ++cur;
-            last = w;
-            wd[cur] = (uint64_t)(p - hp.off[t]) << 32;  // postings before the word's first doc
-            uint64_t& be = blk[fg::srank_block(d)];
-            if (!(uint32_t)be) be = cur << 32;  // the block's first word
-            be |= 1ull << (w & 31u);
-          }
-          wd[cur] |= 1ull << (d & 31u);
-        }
-      }
-    });
-    HIPCHK(hipMemcpyAsync(d_srank, hs.data(), hs.size() * 8, hipMemcpyHostToDevice, kBuildStream));
-    HIPCHK(hipStreamSynchronize(kBuildStream));
-    for (uint32_t s2 = 0; s2 < ns; ++s2) tmeta[sparse_terms[s2]] |= ((first_slot + s2) << 16) | 0x80000000u;
-  }
-  g_bt.mark("rank words: sparse");
-  if (!rank_terms.empty()) {
-    // one k_rank launch for every rank term: per slot the term's posting range
-    std::vector<uint64_t> sb(rank_terms.size());
-    std::vector<uint32_t> sn(rank_terms.size());
-    for (uint32_t s2 = 0; s2 < rank_terms.size(); ++s2) {
-      const uint32_t t = rank_terms[s2];
-      sb[s2] = hp.off[t];
-      sn[s2] = (uint32_t)(hp.off[t + 1] - hp.off[t]);
-      tmeta[t] |= ((s2 + 1) << 16) | 0x80000000u;
-    }
-    // the slot tables are stream-ordered temporaries: freeing them does not
-    // synchronise the device (hipFree would wait for every stream's work)
-    void* d_tab = nullptr;
-    const size_t nb = sb.size() * 8, nn = sn.size() * 4;
-    if (fgh::dev_malloc_async(&d_tab, nb + nn + 16, kBuildStream) != hipSuccess) return fail(FG_EOOM, "hipMallocAsync failed");
-    uint64_t* d_sb = static_cast<uint64_t*>(d_tab);
-    uint32_t* d_sn = reinterpret_cast<uint32_t*>(static_cast<char*>(d_tab) + nb);
-    HIPCHK(hipMemcpyAsync(d_sb, sb.data(), nb, hipMemcpyHostToDevice, kBuildStream));
-    HIPCHK(hipMemcpyAsync(d_sn, sn.data(), nn, hipMemcpyHostToDevice, kBuildStream));
-    HIPCHK(fg::launch_rank(d_doc, d_sb, d_sn, (uint32_t)rank_terms.size(), rank_words, d_rank, kBuildStream));
-    HIPCHK(hipFreeAsync(d_tab, kBuildStream));
-    HIPCHK(hipStreamSynchronize(kBuildStream));
-  }
-  ix->n_rank = (uint32_t)(rank_terms.size() + sparse_terms.size());
-  ix->n_srank_words = sparse_terms.empty() ? 0 : 1 + n_swords;
-  if ((rc = dev_upload(sm, tmeta.data(), tmeta.size(), &d_tmeta, &bytes))) return rc;
-  ix->tmeta = tmeta;
-  g_bt.mark("rank words");
-  ix->d.tfn = d_tfn;
-  ix->d.tfn_name = d_tfn_name;
-  ix->d.esc_pos = d_esc_pos;
-  ix->d.esc_tf = d_esc_tf;
-  ix->d.n_esc = esc_pos.size();
-  ix->d_sc_tf = d_sctf;
-  ix->d_sc_tl = d_sctl;
-  ix->d_sc_e0 = d_sce0;
-  ix->d_sc_e1 = d_sce1;
-  ix->d_bk_tf = d_bktf;
-  ix->d_bk_tl = d_bktl;
-  ix->d_bk_e0 = d_bke0;
-  ix->d_bk_e1 = d_bke1;
-  ix->d_kt_tiny = d_ktt;
-  ix->n_ktiny = (uint32_t)kt_tiny.size();
-  ix->d_tterm = d_tterm;
-  ix->n_tterm = (uint32_t)tterm.size();
-  ix->n_tiles = (uint32_t)n_tiles;
-  ix->d_kt_terms = d_kt;
-  ix->d_kb_terms = d_kbt;
-  ix->d_kb_chunk0 = d_kb0;
-  ix->d_kc_big = d_kcb;
-  ix->d_kc_start = d_kcs;
-  ix->n_kbig = (uint32_t)kb_terms.size();
-  ix->n_kchunks = (uint32_t)kc_big.size();
-  ix->n_sc = n_cmax;
-  ix->n_scb = (uint32_t)sc_tf.size();
-  ix->n_bk = (uint32_t)bk_tf.size();
-  ix->n_kt = (uint32_t)kt.size();
-  ix->d.doc = d_doc;
-  ix->d.off = d_off;
-  ix->d.dir = d_dir;
-  ix->d.dir_off = d_dir_off;
-  ix->d.tmeta = d_tmeta;
-  ix->d.rank = d_rank;
-  ix->d.srank = d_srank;
-  ix->d.srank_w = d_srank ? d_srank + (uint64_t)sblocks * sparse_terms.size() : nullptr;
-  ix->d.n_prank = (uint32_t)rank_terms.size();
-  ix->d.srank_blocks = sblocks;
-  ix->d.toff = d_toff;
-  ix->d.tdir = d_tdir;
-  ix->d.coff = d_coff;
-  ix->d.fdoc = d_fdoc;
-  ix->d.foff = d_foff;
-  ix->d.n_docs = hp.n_docs;
-  ix->d.n_terms = hp.n_terms;
-  ix->d.has_name = hp.has_name ? 1u : 0u;
-  ix->d.n_fterms = hp.n_fterms;
-  ix->d.rank_words = rank_words;
-  // host bookkeeping of the structure
-  ix->off = std::move(hp.off);
-  ix->df_text = std::move(hp.df_text);
-  ix->df_name = std::move(hp.df_name);
-  {
-    std::vector<uint32_t> fd(V, 0), ld(V, 0);
-    for (uint32_t t = 0; t < V; ++t)
-      if (ix->off[t + 1] > ix->off[t]) {
-        fd[t] = hp.doc[ix->off[t]];
-        ld[t] = hp.doc[ix->off[t + 1] - 1];
-      }
-    ix->first_doc = std::move(fd);
-    ix->last_doc = std::move(ld);
-  }
-  if (keep_host) ix->h_doc = std::make_shared<const std::vector<uint32_t>>(std::move(hp.doc));
-  const uint32_t VF = hp.n_fterms;
-  ix->n_fterms = VF;
-  ix->df_facet_local = hp.df_facet;
-  ix->tot_f_local = hp.tot_f;
-  {
-    std::vector<uint32_t> ff(VF, 0), fl(VF, 0);
-    for (uint32_t t = 0; t < VF; ++t)
-      if (hp.foff[t + 1] > hp.foff[t]) {
-        ff[t] = hp.fdoc[hp.foff[t]];
-        fl[t] = hp.fdoc[hp.foff[t + 1] - 1];
-      }
-    ix->ffirst = std::move(ff);
-    ix->flast = std::move(fl);
-  }
-  ix->foff = std::move(hp.foff);
-  // statistics: the shard's own, or the namespace's global ones
-  if (g && VF && !g->df_facet) return fail(FG_EINVAL, "global statistics lack df_facet for a faceted shard");
-  if (g && VF)
-    for (uint32_t t = 0; t < VF; ++t)
-      if (g->df_facet[t] < ix->df_facet_local[t]) return fail(FG_EINVAL, "global facet df of term %u is below this shard's", t);
-  const uint64_t tot_local[2] = {ix->tot_local[0], ix->tot_local[1]};
-  set_stats(ix.get(), g ? g->n_docs : N, g ? g->tot_tokens : tot_local, g ? g->df_text : ix->df_text.data(),
-            g ? g->df_name : ix->df_name.data(), g ? g->tot_facet_tokens : ix->tot_f_local,
-            g && VF ? g->df_facet : ix->df_facet_local.data(), nullptr);
-  g_bt.mark("weights");
-  if ((rc = build_bounds(ix.get(), hp.alive))) return rc;
-  g_bt.mark("tail");
-  *out = ix.release();
-  return FG_OK;
-}
-
-// Sorted (term, tf) runs of one field of one doc into `runs` (term << 0, tf).
-inline void doc_runs(const uint32_t* tok, uint64_t len, std::vector<uint32_t>& scratch,
-                     std::vector<std::pair<uint32_t, uint32_t>>& runs) {
-  runs.clear();
-  if (!len) return;
-  scratch.assign(tok, tok + len);
-  std::sort(scratch.begin(), scratch.end());
-  for (size_t i = 0; i < scratch.size();) {
-    size_t j = i;
-    while (j < scratch.size() && scratch[j] == scratch[i]) ++j;
-    runs.emplace_back(scratch[i], (uint32_t)(j - i));
-    i = j;
-  }
-}
-
-// Facet postings from per-doc FacetTokenizer tokens (fg_docs_input): each doc
-// once per distinct token (df), every token counted in total_num_tokens.
-int build_facets(const fg_docs_input* in, HostPostings& hp, int T) {
-  hp.n_fterms = 0;
-  hp.foff.assign(1, 0);
-  hp.fdoc.clear();
-  hp.df_facet.clear();
-  hp.tot_f = 0;
-  if (!in->facet_off) return FG_OK;
-  const uint32_t N = in->n_docs, VF = in->n_facet_terms;
-  if (in->facet_off[0] != 0 || (!in->facet_tok && in->facet_off[N] > 0))
-    return fail(FG_EINVAL, "bad facet token arrays");
-  for (uint32_t d = 0; d < N; ++d)
-    if (in->facet_off[d + 1] < in->facet_off[d]) return fail(FG_EINVAL, "facet_off not monotone at doc %u", d);
-  hp.n_fterms = VF;
-  hp.tot_f = in->facet_off[N];
-  std::vector<std::vector<uint32_t>> cnt(T);
-  std::atomic<bool> bad{false};
-  auto runs = [&](uint32_t d, std::vector<uint32_t>& sc) {
-    sc.assign(in->facet_tok + in->facet_off[d], in->facet_tok + in->facet_off[d + 1]);
-    std::sort(sc.begin(), sc.end());
-    sc.erase(std::unique(sc.begin(), sc.end()), sc.end());
-  };
-  parallel_ranges(N, T, [&](int t, uint32_t b, uint32_t e) {
-    cnt[t].assign(VF, 0);
-    std::vector<uint32_t> sc;
-    for (uint32_t d = b; d < e; ++d) {
-      runs(d, sc);
-      for (uint32_t x : sc) {
-        if (x >= VF) { bad = true; return; }
-        cnt[t][x]++;
-      }
-    }
-  });
-  if (bad) return fail(FG_EINVAL, "facet token id >= n_facet_terms");
-  std::vector<std::vector<uint64_t>> cur(T);
-  hp.foff.assign(VF + 1, 0);
-  hp.df_facet.assign(VF, 0);
-  uint64_t acc = 0;
-  for (int t = 0; t < T; ++t) cur[t].assign(VF, 0);
-  for (uint32_t x = 0; x < VF; ++x) {
-    hp.foff[x] = acc;
-    for (int t = 0; t < T; ++t) {
-      if (cnt[t].empty()) continue;
-      cur[t][x] = acc;
-      acc += cnt[t][x];
-      hp.df_facet[x] += cnt[t][x];
-    }
-  }
-  hp.foff[VF] = acc;
-  hp.fdoc.resize(acc);
-  parallel_ranges(N, T, [&](int t, uint32_t b, uint32_t e) {
-    std::vector<uint32_t> sc;
-    for (uint32_t d = b; d < e; ++d) {
-      runs(d, sc);
-      for (uint32_t x : sc) hp.fdoc[cur[t][x]++] = d;
-    }
-  });
-  return FG_OK;
-}
-
-}  // namespace
 
 // ================================================================ C ABI
 extern "C" {
@@ -1581,628 +719,6 @@ int fg_ctx_peer_access(const fg_ctx* ctx, int a, int b, int* enabled) {
   return FG_OK;
 }
 
-int fg_index_build_from_docs(fg_ctx* ctx, int dev, const fg_docs_input* in, fg_index** out) {
-  return fg_index_build_from_docs_global(ctx, dev, in, nullptr, out);
-}
-
-int fg_docs_stats(const fg_docs_input* in, uint32_t* df_text, uint32_t* df_name, uint64_t* tot_tokens2) {
-  if (!in || !df_text || !df_name || !tot_tokens2 || !in->text_off || (!in->text_tok && in->text_off[in->n_docs] > 0))
-    return fail(FG_EINVAL, "bad arguments");
-  const uint32_t N = in->n_docs, V = in->n_terms;
-  const bool has_name_in = in->name_off && in->name_tok;
-  const int T = hw_threads(in->threads);
-  std::vector<std::vector<uint32_t>> dft(T), dfn(T);
-  std::vector<uint64_t> tt(T, 0), tn(T, 0);
-  std::atomic<bool> bad{false};
-  parallel_ranges(N, T, [&](int t, uint32_t b, uint32_t e) {
-    dft[t].assign(V, 0);
-    dfn[t].assign(V, 0);
-    std::vector<uint32_t> scratch;
-    std::vector<std::pair<uint32_t, uint32_t>> runs;
-    for (uint32_t d = b; d < e; ++d) {
-      const uint64_t lt = in->text_off[d + 1] - in->text_off[d];
-      tt[t] += lt;
-      doc_runs(in->text_tok + in->text_off[d], lt, scratch, runs);
-      for (auto& r : runs) {
-        if (r.first >= V) { bad = true; return; }
-        dft[t][r.first]++;
-      }
-      if (has_name_in) {
-        const uint64_t ln = in->name_off[d + 1] - in->name_off[d];
-        tn[t] += ln;
-        doc_runs(in->name_tok + in->name_off[d], ln, scratch, runs);
-        for (auto& r : runs) {
-          if (r.first >= V) { bad = true; return; }
-          dfn[t][r.first]++;
-        }
-      }
-    }
-  });
-  if (bad) return fail(FG_EINVAL, "token id >= n_terms");
-  std::fill(df_text, df_text + V, 0u);
-  std::fill(df_name, df_name + V, 0u);
-  tot_tokens2[0] = tot_tokens2[1] = 0;
-  for (int t = 0; t < T; ++t) {
-    if (dft[t].empty()) continue;
-    for (uint32_t v = 0; v < V; ++v) {
-      df_text[v] += dft[t][v];
-      df_name[v] += dfn[t][v];
-    }
-    tot_tokens2[0] += tt[t];
-    tot_tokens2[1] += tn[t];
-  }
-  return FG_OK;
-}
-
-int fg_docs_facet_stats(const fg_docs_input* in, uint32_t* df_facet, uint64_t* tot_facet) {
-  if (!in || !tot_facet || (in->facet_off && in->n_facet_terms && !df_facet)) return fail(FG_EINVAL, "bad arguments");
-  HostPostings hp;
-  if (int rc = build_facets(in, hp, hw_threads(in->threads))) return rc;
-  if (hp.n_fterms) std::copy(hp.df_facet.begin(), hp.df_facet.end(), df_facet);
-  *tot_facet = hp.tot_f;
-  return FG_OK;
-}
-
-}  // extern "C"
-
-// A build's own term dictionary (fg_index::tmap).  Its docs' distinct terms are
-// marked in a vocabulary bitset; when they are fewer than 1/kLocalDiv of the
-// vocabulary (a commit's 1000 new docs hold ~2% of a 10M-doc namespace's), the
-// build runs on local ids: the tokens renumbered in vocabulary order (a rank in
-// the bitset) and the statistics gathered to them, so its work and its device
-// arrays scale with its own terms, not the vocabulary's.  The marking stops as
-// soon as the count passes the limit (a large build decides within its first
-// docs).  L.tmap stays empty: vocabulary ids.
-namespace {
-constexpr uint32_t kLocalDiv = 4;
-struct LocalDict {
-  std::vector<uint32_t> tmap, ttok, ntok, df_t, df_n;
-  fg_docs_input in{};
-  fg_global_stats g{};
-};
-int local_dict(const fg_docs_input* in, const fg_global_stats* g, LocalDict& L) {
-  const uint32_t N = in->n_docs, V = in->n_terms;
-  const bool has_name = in->name_off && in->name_tok;
-  const uint64_t limit = V / kLocalDiv;
-  std::vector<uint64_t> bits(((uint64_t)V + 63) / 64, 0);
-  uint64_t n = 0;
-  auto mark = [&](const uint32_t* tok, uint64_t b, uint64_t e) {
-    for (uint64_t i = b; i < e; ++i) {
-      const uint32_t t = tok[i];
-      if (t >= V) return false;
-      uint64_t& w = bits[t >> 6];
-      const uint64_t m = 1ull << (t & 63);
-      n += (w & m) == 0;
-      w |= m;
-    }
-    return true;
-  };
-  for (uint32_t d = 0; d < N && n <= limit; ++d) {
-    if (!mark(in->text_tok, in->text_off[d], in->text_off[d + 1])) return fail(FG_EINVAL, "token id >= n_terms");
-    if (has_name && !mark(in->name_tok, in->name_off[d], in->name_off[d + 1]))
-      return fail(FG_EINVAL, "token id >= n_terms");
-  }
-  if (n > limit || n == 0) return FG_OK;
-  const uint32_t v = (uint32_t)n;
-  std::vector<uint32_t> rank(bits.size());
-  L.tmap.reserve(v);
-  for (size_t w = 0; w < bits.size(); ++w) {
-    rank[w] = (uint32_t)L.tmap.size();
-    for (uint64_t x = bits[w]; x; x &= x - 1) L.tmap.push_back((uint32_t)(w * 64 + __builtin_ctzll(x)));
-  }
-  auto local = [&](uint32_t t) {
-    return rank[t >> 6] + (uint32_t)__builtin_popcountll(bits[t >> 6] & ((1ull << (t & 63)) - 1));
-  };
-  const uint64_t nt = in->text_off[N], nn = has_name ? in->name_off[N] : 0;
-  L.ttok.resize(nt);
-  for (uint64_t i = in->text_off[0]; i < nt; ++i) L.ttok[i] = local(in->text_tok[i]);
-  if (has_name) {
-    L.ntok.resize(nn);
-    for (uint64_t i = in->name_off[0]; i < nn; ++i) L.ntok[i] = local(in->name_tok[i]);
-  }
-  L.in = *in;
-  L.in.n_terms = v;
-  L.in.text_tok = L.ttok.data();
-  if (has_name) L.in.name_tok = L.ntok.data();
-  if (g) {
-    L.df_t.resize(v);
-    L.df_n.resize(v);
-    for (uint32_t l = 0; l < v; ++l) {
-      L.df_t[l] = g->df_text[L.tmap[l]];
-      L.df_n[l] = g->df_name ? g->df_name[L.tmap[l]] : 0u;
-    }
-    L.g = *g;
-    L.g.df_text = L.df_t.data();
-    L.g.df_name = g->df_name ? L.df_n.data() : nullptr;
-  }
-  return FG_OK;
-}
-}  // namespace
-
-extern "C" {
-
-static int build_from_docs(fg_ctx* ctx, int dev, const fg_docs_input* in, const fg_global_stats* g, fg_index** out);
-
-// The forward index of a snapshot built with fg_docs_input::keep_positions
-// (DevIndex::fwd_off / fwd): per field every doc's tokens laid out by analyzer
-// position -- a gap entry leaves a kFwdNone hole before its token -- and
-// uploaded on the build stream (the background stream of a commit or a merge).
-// Structure: shared with the snapshot's rescores, counted in device_bytes.
-static int fwd_field(uint32_t N, const uint64_t* off, const uint32_t* tok, const uint64_t* gap, uint64_t n_gap,
-                     std::vector<uint64_t>& foff, std::vector<uint32_t>& fwd) {
-  const uint64_t nt = off[N];
-  for (uint64_t i = 0; i < n_gap; ++i)
-    if (gap[i] >= nt || gap[i] < off[0] || (i && gap[i] < gap[i - 1]))
-      return fail(FG_EINVAL, "gap list not ascending indices into the tokens");
-  foff.resize((size_t)N + 1);
-  try {
-    fwd.resize(nt + n_gap);
-  } catch (...) {
-    return fail(FG_EOOM, "forward index (%llu positions) allocation failed", (unsigned long long)(nt + n_gap));
-  }
-  uint64_t g = 0, o = 0;
-  for (uint32_t d = 0; d < N; ++d) {
-    foff[d] = o;
-    for (uint64_t i = off[d]; i < off[d + 1]; ++i) {
-      for (; g < n_gap && gap[g] == i; ++g) fwd[o++] = fg::kFwdNone;
-      fwd[o++] = tok[i];
-    }
-  }
-  foff[N] = o;
-  return FG_OK;
-}
-
-static int attach_positions(fg_index* ix, const fg_docs_input* in) {
-  if ((in->n_text_gap && !in->text_gap) || (in->n_name_gap && !in->name_gap)) return fail(FG_EINVAL, "gap count without a gap list");
-  const uint32_t N = in->n_docs;
-  const bool has_name_in = in->name_off && in->name_tok;
-  HIPCHK(hipSetDevice(ix->dev));
-  uint64_t bytes = 0;
-  std::vector<uint64_t> foff;
-  std::vector<uint32_t> fwd;
-  uint64_t* d_off = nullptr;
-  uint32_t* d_fwd = nullptr;
-  if (int rc = fwd_field(N, in->text_off, in->text_tok, in->text_gap, in->n_text_gap, foff, fwd)) return rc;
-  if (int rc = dev_upload(*ix->smem, foff.data(), foff.size(), &d_off, &bytes)) return rc;
-  if (int rc = dev_upload(*ix->smem, fwd.data(), fwd.size(), &d_fwd, &bytes)) return rc;
-  ix->d.fwd_off = d_off;
-  ix->d.fwd = d_fwd;
-  if (has_name_in && ix->d.tfn_name) {  // (no name postings: no phrase matches there)
-    if (int rc = fwd_field(N, in->name_off, in->name_tok, in->name_gap, in->n_name_gap, foff, fwd)) return rc;
-    if (int rc = dev_upload(*ix->smem, foff.data(), foff.size(), &d_off, &bytes)) return rc;
-    if (int rc = dev_upload(*ix->smem, fwd.data(), fwd.size(), &d_fwd, &bytes)) return rc;
-    ix->d.fwd_off_name = d_off;
-    ix->d.fwd_name = d_fwd;
-  }
-  ix->struct_bytes += bytes;
-  ix->device_bytes += bytes;
-  ix->has_positions = true;
-  g_bt.mark("forward index");
-  return FG_OK;
-}
-
-int fg_index_build_from_docs_global(fg_ctx* ctx, int dev, const fg_docs_input* in, const fg_global_stats* g,
-                                    fg_index** out) {
-  if (!ctx || !in || !out || !in->text_off || (!in->text_tok && in->text_off[in->n_docs] > 0))
-    return fail(FG_EINVAL, "bad arguments");
-  if (g && (!g->df_text || g->n_docs < in->n_docs || g->n_docs >= 0x7FFFFFFFull))
-    return fail(FG_EINVAL, "bad global statistics");
-  if (in->n_docs == 0) return fail(FG_EINVAL, "empty index (n_docs == 0)");
-  if (in->n_docs >= 0x7FFFFFFFu) return fail(FG_EINVAL, "n_docs must be < 2^31 (tantivy DocId)");
-  g_bt.start();
-  LocalDict L;
-  if (int rc = local_dict(in, g, L)) return rc;
-  const uint32_t V = in->n_terms;
-  fg_index* ix = nullptr;
-  if (L.tmap.empty()) {
-    if (int rc = build_from_docs(ctx, dev, in, g, &ix)) return rc;
-  } else {
-    g_bt.mark("local dictionary");
-    if (int rc = build_from_docs(ctx, dev, &L.in, g ? &L.g : nullptr, &ix)) return rc;
-    ix->tmap = std::move(L.tmap);
-    ix->n_vocab = V;
-  }
-  // (from the caller's tokens: a snapshot with its own dictionary still keeps vocabulary ids here)
-  if (in->keep_positions)
-    if (int rc = attach_positions(ix, in)) {
-      fg_index_release(ix);
-      return rc;
-    }
-  *out = ix;
-  return FG_OK;
-}
-
-static int build_from_docs(fg_ctx* ctx, int dev, const fg_docs_input* in, const fg_global_stats* g, fg_index** out) {
-  if (!ctx || !in || !out || !in->text_off || (!in->text_tok && in->text_off[in->n_docs] > 0))
-    return fail(FG_EINVAL, "bad arguments");
-  if (g && (!g->df_text || g->n_docs < in->n_docs || g->n_docs >= 0x7FFFFFFFull))
-    return fail(FG_EINVAL, "bad global statistics");
-  if (in->n_docs == 0) return fail(FG_EINVAL, "empty index (n_docs == 0)");
-  if (in->n_docs >= 0x7FFFFFFFu) return fail(FG_EINVAL, "n_docs must be < 2^31 (tantivy DocId)");
-  if (std::find(ctx->devs.begin(), ctx->devs.end(), dev) == ctx->devs.end())
-    return fail(FG_EINVAL, "device %d not in context", dev);
-  const uint32_t N = in->n_docs, V = in->n_terms;
-  const bool has_name_in = in->name_off && in->name_tok;
-  // every thread of pass 1 zeroes and merges three vocabulary-sized count
-  // arrays: a small build (a commit's new docs) uses few threads
-  const int T = std::max(1, std::min(hw_threads(in->threads), (int)(N / 4096)));
-  HostPostings hp;
-  hp.n_docs = N;
-  hp.n_terms = V;
-  hp.fn_text.resize(N);
-  hp.fn_name.assign(N, 0);
-  // pass 1: per-thread counts (merged df, df_text, df_name), fieldnorms
-  std::vector<std::vector<uint32_t>> cnt(T), dft(T), dfn(T);
-  std::vector<uint64_t> tot_t(T, 0), tot_n(T, 0);
-  std::atomic<bool> bad{false};
-  parallel_ranges(N, T, [&](int t, uint32_t b, uint32_t e) {
-    cnt[t].assign(V, 0);
-    dft[t].assign(V, 0);
-    dfn[t].assign(V, 0);
-    std::vector<uint32_t> scratch;
-    std::vector<std::pair<uint32_t, uint32_t>> rt, rn;
-    for (uint32_t d = b; d < e; ++d) {
-      uint64_t lt = in->text_off[d + 1] - in->text_off[d];
-      uint64_t ln = has_name_in ? in->name_off[d + 1] - in->name_off[d] : 0;
-      tot_t[t] += lt;
-      tot_n[t] += ln;
-      hp.fn_text[d] = fieldnorm_id(lt);
-      if (has_name_in) hp.fn_name[d] = fieldnorm_id(ln);
-      doc_runs(in->text_tok + in->text_off[d], lt, scratch, rt);
-      if (has_name_in) doc_runs(in->name_tok + in->name_off[d], ln, scratch, rn); else rn.clear();
-      size_t i = 0, j = 0;
-      while (i < rt.size() || j < rn.size()) {
-        uint32_t a = i < rt.size() ? rt[i].first : 0xFFFFFFFFu;
-        uint32_t c = j < rn.size() ? rn[j].first : 0xFFFFFFFFu;
-        uint32_t term = std::min(a, c);
-        if (term >= V) { bad = true; return; }
-        cnt[t][term]++;
-        if (a == term) { dft[t][term]++; ++i; }
-        if (c == term) { dfn[t][term]++; ++j; }
-      }
-    }
-  });
-  if (bad) return fail(FG_EINVAL, "token id >= n_terms");
-  const int used = (int)std::count_if(cnt.begin(), cnt.end(), [](auto& v) { return !v.empty(); });
-  hp.off.assign(V + 1, 0);
-  hp.df_text.assign(V, 0);
-  hp.df_name.assign(V, 0);
-  // per-thread write cursors (reuse cnt as u64 cursors via a separate array)
-  std::vector<std::vector<uint64_t>> cur(used);
-  for (int t = 0; t < used; ++t) cur[t].resize(V);
-  uint64_t acc = 0;
-  for (uint32_t term = 0; term < V; ++term) {
-    hp.off[term] = acc;
-    for (int t = 0; t < used; ++t) {
-      cur[t][term] = acc;
-      acc += cnt[t][term];
-      hp.df_text[term] += dft[t][term];
-      hp.df_name[term] += dfn[t][term];
-    }
-  }
-  hp.off[V] = acc;
-  cnt.clear();
-  dft.clear();
-  dfn.clear();
-  for (int t = 0; t < used; ++t) { hp.tot[0] += tot_t[t]; hp.tot[1] += tot_n[t]; }
-  hp.has_name = hp.tot[1] > 0;
-  try {
-    hp.doc.resize(acc);
-    hp.tf.resize(acc);
-  } catch (...) {
-    return fail(FG_EOOM, "host postings (%llu) allocation failed", (unsigned long long)acc);
-  }
-  g_bt.mark("pass 1 counts + offsets");
-  // pass 2: fill (thread t's docs land after threads < t within each term)
-  parallel_ranges(N, T, [&](int t, uint32_t b, uint32_t e) {
-    std::vector<uint32_t> scratch;
-    std::vector<std::pair<uint32_t, uint32_t>> rt, rn;
-    std::vector<uint64_t>& c = cur[t];
-    for (uint32_t d = b; d < e; ++d) {
-      uint64_t lt = in->text_off[d + 1] - in->text_off[d];
-      uint64_t ln = has_name_in ? in->name_off[d + 1] - in->name_off[d] : 0;
-      doc_runs(in->text_tok + in->text_off[d], lt, scratch, rt);
-      if (has_name_in) doc_runs(in->name_tok + in->name_off[d], ln, scratch, rn); else rn.clear();
-      size_t i = 0, j = 0;
-      while (i < rt.size() || j < rn.size()) {
-        uint32_t a = i < rt.size() ? rt[i].first : 0xFFFFFFFFu;
-        uint32_t cc = j < rn.size() ? rn[j].first : 0xFFFFFFFFu;
-        uint32_t term = std::min(a, cc);
-        uint32_t tt = 0, tn = 0;
-        if (a == term) { tt = std::min<uint32_t>(rt[i].second, 0xFFFF); ++i; }
-        if (cc == term) { tn = std::min<uint32_t>(rn[j].second, 0xFFFF); ++j; }
-        uint64_t p = c[term]++;
-        hp.doc[p] = d;
-        hp.tf[p] = tt | (tn << 16);
-      }
-    }
-  });
-  if (in->deleted) {
-    hp.alive.assign((N + 31) / 32, 0);
-    for (uint32_t d = 0; d < N; ++d)
-      if (!in->deleted[d]) hp.alive[d >> 5] |= 1u << (d & 31);
-  }
-  if (g)
-    for (uint32_t t = 0; t < V; ++t)
-      if (g->df_text[t] < hp.df_text[t] || (g->df_name ? g->df_name[t] : 0u) < hp.df_name[t])
-        return fail(FG_EINVAL, "global df of term %u is below this shard's", t);
-  g_bt.mark("pass 2 fill");
-  if (int rc = build_facets(in, hp, T)) return rc;
-  g_bt.mark("facets");
-  return finish_index(dev, hp, in->keep_host_postings != 0, out, g);
-}
-
-int fg_index_build(fg_ctx* ctx, int dev, const fg_index_input* in, fg_index** out) {
-  return fg_index_build_global(ctx, dev, in, nullptr, out);
-}
-
-int fg_index_build_global(fg_ctx* ctx, int dev, const fg_index_input* in, const fg_global_stats* g, fg_index** out) {
-  if (!ctx || !in || !out || !in->term_off || !in->fn_text) return fail(FG_EINVAL, "bad arguments");
-  if (g && (!g->df_text || g->n_docs < in->n_docs || g->n_docs >= 0x7FFFFFFFull))
-    return fail(FG_EINVAL, "bad global statistics");
-  g_bt.start();
-  if (in->n_docs == 0 || in->n_docs >= 0x7FFFFFFFu) return fail(FG_EINVAL, "n_docs out of range");
-  if (in->term_off[0] != 0) return fail(FG_EINVAL, "term_off[0] must be 0");
-  if (in->term_off[in->n_terms] > 0 && (!in->doc || (!in->tf_text && !in->tf_name)))
-    return fail(FG_EINVAL, "postings without doc ids or term frequencies");
-  if (std::find(ctx->devs.begin(), ctx->devs.end(), dev) == ctx->devs.end())
-    return fail(FG_EINVAL, "device %d not in context", dev);
-  HostPostings hp;
-  const uint32_t N = in->n_docs, V = in->n_terms;
-  hp.n_docs = N;
-  hp.n_terms = V;
-  for (uint32_t t = 0; t < V; ++t)
-    if (in->term_off[t + 1] < in->term_off[t]) return fail(FG_EINVAL, "term_off not monotone at %u", t);
-  hp.off.assign(in->term_off, in->term_off + V + 1);
-  const uint64_t P = hp.off[V];
-  hp.doc.assign(in->doc, in->doc + P);
-  hp.tf.resize(P);
-  hp.df_text.assign(V, 0);
-  hp.df_name.assign(V, 0);
-  for (uint32_t t = 0; t < V; ++t) {
-    for (uint64_t p = hp.off[t]; p < hp.off[t + 1]; ++p) {
-      uint32_t tt = in->tf_text ? in->tf_text[p] : 0, tn = in->tf_name ? in->tf_name[p] : 0;
-      if (!tt && !tn) return fail(FG_EINVAL, "posting %llu has tf 0 in both fields", (unsigned long long)p);
-      if (hp.doc[p] >= N || (p > hp.off[t] && hp.doc[p] <= hp.doc[p - 1]))
-        return fail(FG_EINVAL, "postings of term %u not strictly ascending / in range", t);
-      hp.tf[p] = tt | (tn << 16);
-      hp.df_text[t] += tt ? 1 : 0;
-      hp.df_name[t] += tn ? 1 : 0;
-    }
-  }
-  hp.fn_text.assign(in->fn_text, in->fn_text + N);
-  if (in->fn_name) hp.fn_name.assign(in->fn_name, in->fn_name + N); else hp.fn_name.assign(N, 0);
-  hp.tot[0] = in->tot_tokens[0];
-  hp.tot[1] = in->tot_tokens[1];
-  hp.has_name = hp.tot[1] > 0;
-  if (in->deleted) {
-    hp.alive.assign((N + 31) / 32, 0);
-    for (uint32_t d = 0; d < N; ++d)
-      if (!in->deleted[d]) hp.alive[d >> 5] |= 1u << (d & 31);
-  }
-  if (in->facet_term_off) {
-    const uint32_t VF = in->n_facet_terms;
-    hp.n_fterms = VF;
-    hp.foff.assign(in->facet_term_off, in->facet_term_off + VF + 1);
-    if (hp.foff[0] != 0 || (!in->facet_doc && hp.foff[VF] > 0)) return fail(FG_EINVAL, "bad facet postings");
-    hp.fdoc.assign(in->facet_doc, in->facet_doc + hp.foff[VF]);
-    hp.df_facet.assign(VF, 0);
-    for (uint32_t t = 0; t < VF; ++t) {
-      if (hp.foff[t + 1] < hp.foff[t]) return fail(FG_EINVAL, "facet_term_off not monotone at %u", t);
-      for (uint64_t p = hp.foff[t]; p < hp.foff[t + 1]; ++p)
-        if (hp.fdoc[p] >= N || (p > hp.foff[t] && hp.fdoc[p] <= hp.fdoc[p - 1]))
-          return fail(FG_EINVAL, "facet postings of term %u not strictly ascending / in range", t);
-      hp.df_facet[t] = (uint32_t)(hp.foff[t + 1] - hp.foff[t]);
-    }
-    hp.tot_f = in->tot_facet_tokens;
-  }
-  if (g)
-    for (uint32_t t = 0; t < V; ++t)
-      if (g->df_text[t] < hp.df_text[t] || (g->df_name ? g->df_name[t] : 0u) < hp.df_name[t])
-        return fail(FG_EINVAL, "global df of term %u is below this segment's", t);
-  return finish_index(dev, hp, true, out, g);
-}
-
-}  // extern "C"
-
-// one snapshot rescored (fg_index_rescore); wts: shared precomputed weights or
-// nullptr.  Host only: tantivy scores at query time (src/db/search.rs:162), so
-// a new Searcher's statistics need no device work -- the snapshot shares every
-// device array of its base (structure and bound tables) and gets the new
-// statistics (plans read them), a new alive bitset when docs were deleted, and
-// the ratios that scale the build-time bounds (relate_stats).
-static int rescore_one(const fg_index* base, const fg_global_stats* g, const uint8_t* deleted, fg_index** out,
-                       const fgh::Weights* wts) {
-  if (!base || !g || !out || !g->df_text) return fail(FG_EINVAL, "bad arguments");
-  const uint32_t N = base->n_docs, V = base->n_terms, VF = base->n_fterms;
-  if (g->n_docs < N || g->n_docs >= 0x7FFFFFFFull) return fail(FG_EINVAL, "bad global statistics");
-  if (base->has_name && !g->df_name) return fail(FG_EINVAL, "global statistics lack df_name for a snapshot with names");
-  if (VF && !g->df_facet) return fail(FG_EINVAL, "global statistics lack df_facet for a faceted snapshot");
-  // the statistics' doc frequencies of the snapshot's terms (gathered to local
-  // ids when it has its own dictionary: a commit's rescores then cost its terms)
-  const uint32_t* gt = g->df_text;
-  const uint32_t* gn = g->df_name;
-  std::vector<uint32_t> lt, ln;
-  if (!base->tmap.empty()) {
-    const uint32_t* tm = base->tmap.data();
-    lt.resize(V);
-    for (uint32_t t = 0; t < V; ++t) lt[t] = g->df_text[tm[t]];
-    gt = lt.data();
-    if (g->df_name) {
-      ln.resize(V);
-      for (uint32_t t = 0; t < V; ++t) ln[t] = g->df_name[tm[t]];
-      gn = ln.data();
-    }
-    wts = nullptr;  // (shared weights are vocabulary-indexed)
-  }
-  {  // (branch-free scans: every older segment of every commit runs them over its terms)
-    const uint32_t* bt = base->df_text.data();
-    bool bad = false;
-    for (uint32_t t = 0; t < V; ++t) bad |= gt[t] < bt[t];
-    if (gn) {
-      const uint32_t* bn = base->df_name.data();
-      for (uint32_t t = 0; t < V; ++t) bad |= gn[t] < bn[t];
-    } else if (base->has_name) {
-      bad = true;
-    }
-    for (uint32_t t = 0; t < VF; ++t) bad |= g->df_facet[t] < base->df_facet_local[t];
-    if (bad) return fail(FG_EINVAL, "global doc frequencies below this snapshot's own");
-  }
-  auto ix = std::make_unique<fg_index>();
-  ix->dev = base->dev;
-  ix->mem.dev = base->dev;
-  fgh::device_pools(base->dev, &ix->pool, &ix->pinned);
-  // the structure: shared device arrays and host bookkeeping (SharedVec)
-  ix->smem = base->smem;
-  ix->spool = base->spool;
-  ix->struct_bytes = base->struct_bytes;
-  ix->n_docs = N;
-  ix->n_terms = V;
-  ix->n_vocab = base->n_vocab;
-  ix->tmap = base->tmap;
-  ix->has_name = base->has_name;
-  ix->n_postings = base->n_postings;
-  ix->dir_entries = base->dir_entries;
-  ix->tile_entries = base->tile_entries;
-  ix->n_rank = base->n_rank;
-  ix->n_srank_words = base->n_srank_words;
-  ix->has_positions = base->has_positions;
-  ix->off = base->off;
-  ix->df_text = base->df_text;
-  ix->df_name = base->df_name;
-  ix->first_doc = base->first_doc;
-  ix->last_doc = base->last_doc;
-  ix->h_doc = base->h_doc;
-  ix->tot_local[0] = base->tot_local[0];
-  ix->tot_local[1] = base->tot_local[1];
-  ix->tmeta = base->tmeta;
-  ix->n_fterms = VF;
-  ix->tot_f_local = base->tot_f_local;
-  ix->foff = base->foff;
-  ix->df_facet_local = base->df_facet_local;
-  ix->ffirst = base->ffirst;
-  ix->flast = base->flast;
-  ix->d_sc_tf = base->d_sc_tf;
-  ix->d_sc_tl = base->d_sc_tl;
-  ix->d_sc_e0 = base->d_sc_e0;
-  ix->d_sc_e1 = base->d_sc_e1;
-  ix->d_bk_tf = base->d_bk_tf;
-  ix->d_bk_tl = base->d_bk_tl;
-  ix->d_bk_e0 = base->d_bk_e0;
-  ix->d_bk_e1 = base->d_bk_e1;
-  ix->d_kt_tiny = base->d_kt_tiny;
-  ix->n_ktiny = base->n_ktiny;
-  ix->d_tterm = base->d_tterm;
-  ix->n_tterm = base->n_tterm;
-  ix->n_tiles = base->n_tiles;
-  ix->d_kt_terms = base->d_kt_terms;
-  ix->d_kb_terms = base->d_kb_terms;
-  ix->d_kb_chunk0 = base->d_kb_chunk0;
-  ix->d_kc_big = base->d_kc_big;
-  ix->d_kc_start = base->d_kc_start;
-  ix->n_kbig = base->n_kbig;
-  ix->n_kchunks = base->n_kchunks;
-  ix->n_sc = base->n_sc;
-  ix->n_scb = base->n_scb;
-  ix->n_bk = base->n_bk;
-  ix->n_kt = base->n_kt;
-  ix->d = base->d;
-  // the bounds and the build statistics they are under
-  ix->sblock = base->sblock;
-  ix->ktop = base->ktop;
-  ix->tmaxs = base->tmaxs;
-  ix->wb_text = base->wb_text;
-  ix->wb_name = base->wb_name;
-  std::memcpy(ix->cache_b, base->cache_b, sizeof ix->cache_b);
-  ix->h_alive_b = base->h_alive_b;
-  ix->device_bytes = base->device_bytes;
-  set_stats(ix.get(), g->n_docs, g->tot_tokens, gt, gn, g->tot_facet_tokens, VF ? g->df_facet : nullptr, wts);
-  relate_stats(ix.get());
-  // deletions: the alive bitset (the base's device copy when unchanged), and
-  // the docs dead now that ktop's selection counted alive (term_kth)
-  std::vector<uint32_t> alive;
-  if (deleted) {
-    alive.assign((N + 31) / 32, 0);
-    for (uint32_t d = 0; d < N; ++d)
-      if (!deleted[d]) alive[d >> 5] |= 1u << (d & 31);
-  }
-  if (alive == base->h_alive.vec()) {
-    ix->h_alive = base->h_alive;
-    ix->alive_hold = base->alive_hold;
-  } else if (alive.empty()) {
-    ix->d.alive = nullptr;
-  } else {
-    HIPCHK(hipSetDevice(ix->dev));
-    auto m = std::make_shared<DevAllocs>();
-    m->dev = ix->dev;
-    uint32_t* d_alive = nullptr;
-    uint64_t b = 0;
-    if (int rc = dev_upload(*m, alive.data(), alive.size(), &d_alive, &b)) return rc;
-    ix->d.alive = d_alive;
-    ix->alive_hold = m;
-    ix->h_alive = std::move(alive);
-  }
-  {
-    uint64_t dead = 0;
-    const auto& now = ix->h_alive.vec();
-    const auto& then = ix->h_alive_b.vec();
-    for (uint32_t w = 0; w < (N + 31) / 32; ++w) {
-      const uint32_t valid = (w + 1) * 32 <= N ? 0xFFFFFFFFu : (1u << (N & 31)) - 1u;
-      const uint32_t a0 = then.empty() ? valid : then[w], a1 = now.empty() ? valid : now[w];
-      dead += (uint32_t)__builtin_popcount(a0 & ~a1 & valid);
-    }
-    ix->n_dead = (uint32_t)std::min<uint64_t>(dead, 0xFFFFFFFFu);
-  }
-  *out = ix.release();
-  return FG_OK;
-}
-
-extern "C" {
-
-int fg_index_rescore(const fg_index* base, const fg_global_stats* g, const uint8_t* deleted, fg_index** out) {
-  g_bt.start();
-  return rescore_one(base, g, deleted, out, nullptr);
-}
-
-int fg_index_rescore_many(const fg_index* const* bases, uint32_t n, const fg_global_stats* g,
-                          const uint8_t* const* deleted, fg_index** outs) {
-  if ((n && (!bases || !outs)) || !g || !g->df_text) return fail(FG_EINVAL, "bad arguments");
-  uint32_t V = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (!bases[i]) return fail(FG_EINVAL, "NULL snapshot %u", i);
-    if (bases[i]->tmap.empty()) V = std::max(V, bases[i]->n_terms);
-    outs[i] = nullptr;
-  }
-  if (n == 0) return FG_OK;
-  // the weights once for every snapshot on vocabulary ids (they depend on the
-  // statistics only; a snapshot with its own dictionary gathers its own)
-  fgh::Weights wts;
-  g_bt.start();
-  if (V) {
-    std::vector<float> wt, wn, it, in;
-    bm25_weights(g->n_docs, g->df_text, g->df_name, V, wt, wn, it, in);
-    wts.wt = std::move(wt);
-    wts.wn = std::move(wn);
-    wts.it = std::move(it);
-    wts.in = std::move(in);
-  }
-  g_bt.mark("rescore: shared weights");
-  for (uint32_t i = 0; i < n; ++i) {
-    const int rc = rescore_one(bases[i], g, deleted ? deleted[i] : nullptr, &outs[i], &wts);
-    g_bt.mark(bases[i]->tmap.empty() ? "rescore: a snapshot" : "rescore: a snapshot (own dictionary)");
-    if (rc) {
-      const std::string e = fg_last_error();
-      for (uint32_t j2 = 0; j2 < n; ++j2)
-        if (outs[j2]) {
-          fg_index_release(outs[j2]);
-          outs[j2] = nullptr;
-        }
-      return fail(rc, "snapshot %u: %s", i, e.c_str());
-    }
-  }
-  return FG_OK;
-}
-
 int fg_thread_background(int on) {
   const int prev = tl_background;
   tl_background = on ? 1 : 0;
@@ -2259,60 +775,6 @@ int fg_index_term_kth(const fg_index* ix, uint32_t term, float* out) {
   static_assert(fg::kNumTopK == 5, "fugu.h documents five K");
   term = fgh::local_term(ix, term);
   for (uint32_t k = 0; k < fg::kNumTopK; ++k) out[k] = fgh::term_kth_now(ix, term, fg::kTopKs[k], false);
-  return FG_OK;
-}
-
-int fg_index_term_ladder(const fg_index* ix, float* out) {
-  if (!ix || !out) return fail(FG_EINVAL, "bad arguments");
-  static_assert(fg::kNumLadder == FG_LADDER_LEVELS, "fugu.h FG_LADDER_LEVELS");
-  const uint32_t V = ix->n_terms;
-  if (V == 0) return FG_OK;
-  HIPCHK(hipSetDevice(ix->dev));
-  // one temporary: the main K-th scores [V * kNumTopK], then the extra levels
-  const size_t nm = (size_t)V * fg::kNumTopK, nx = (size_t)V * fg::kNumLadderExtra;
-  void* tmp = nullptr;
-  if (fgh::dev_malloc_async(&tmp, 4 * (nm + nx) + 16, kBuildStream) != hipSuccess)
-    return fail(FG_EOOM, "hipMallocAsync(%zu) failed", 4 * (nm + nx));
-  struct Back {
-    void* p;
-    ~Back() { (void)hipFreeAsync(p, kBuildStream); }
-  } back{tmp};
-  float* d = static_cast<float*>(tmp);
-  HIPCHK(hipMemsetAsync(d, 0, 4 * (nm + nx), kBuildStream));
-  // the posting scores under the snapshot's statistics (a temporary), then k_ktop with the extra levels
-  fg::ScoreJob j{};
-  void* ptmp = nullptr;
-  if (int rc = score_postings(ix, j, nullptr, nullptr, &ptmp)) return rc;
-  struct PBack {
-    void* p;
-    ~PBack() { (void)hipFreeAsync(p, kBuildStream); }
-  } pback{ptmp};
-  j.alive = ix->d.alive;
-  j.ktop = d;
-  j.ladder = d + nm;
-  if (int rc = ktop_pass(ix, j)) return rc;
-  std::vector<float> h(nm + nx);
-  HIPCHK(hipMemcpyAsync(h.data(), d, 4 * (nm + nx), hipMemcpyDeviceToHost, kBuildStream));
-  HIPCHK(hipStreamSynchronize(kBuildStream));
-  // interleave into ascending K per term
-  uint32_t src[fg::kNumLadder];  // level l: (main?, index)
-  for (uint32_t l = 0; l < fg::kNumLadder; ++l) {
-    src[l] = 0xFFFFFFFFu;
-    for (uint32_t i = 0; i < fg::kNumTopK; ++i)
-      if (fg::kTopKs[i] == fg::kLadderKs[l]) src[l] = i;
-    for (uint32_t i = 0; i < fg::kNumLadderExtra; ++i)
-      if (fg::kLadderExtra[i] == fg::kLadderKs[l]) src[l] = 0x10000u | i;
-    if (src[l] == 0xFFFFFFFFu) return fail(FG_EINVAL, "ladder level %u unmapped", l);
-  }
-  // (vocabulary ids: a snapshot with its own dictionary scatters its terms, zeros elsewhere)
-  const uint32_t* tm = ix->tmap.empty() ? nullptr : ix->tmap.data();
-  if (tm) std::fill(out, out + (size_t)ix->n_vocab * fg::kNumLadder, 0.0f);
-  for (uint32_t t = 0; t < V; ++t)
-    for (uint32_t l = 0; l < fg::kNumLadder; ++l) {
-      const uint32_t s = src[l];
-      out[(size_t)(tm ? tm[t] : t) * fg::kNumLadder + l] = (s & 0x10000u) ? h[nm + (size_t)t * fg::kNumLadderExtra + (s & 0xFFFFu)]
-                                                            : h[(size_t)t * fg::kNumTopK + s];
-    }
   return FG_OK;
 }
 

@@ -2,7 +2,7 @@
 posting's tf / fieldnorm payload (DevIndex::tfn) and the query's weights, as
 tantivy's TermScorer does at search time (reference src/db/search.rs:162); a
 rescore (a commit's new Searcher statistics) runs no device work and scales the
-build-time bounds instead (fugu.cpp rescore_one, term_ratio).
+build-time bounds instead (build.cpp rescore_one, fugu.cpp term_ratio).
 
 Checked against the oracle and against fresh builds under the same statistics:
   * `name` postings (the second payload array, DevPlan::feat bit 0) and tf >= 255

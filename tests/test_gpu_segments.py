@@ -198,3 +198,82 @@ def test_sharded_batch_in_halves_equals_quarters(native, ctx, parts):
                     assert np.array_equal(part[a][i, :m], whole[a][b + i, :m]), (k, mode, b + i, a)
     for x in segs:
         x.close()
+
+
+class _Filtered:
+    """search_batch of an index (device or oracle) with fixed facet filters"""
+
+    def __init__(self, ix, **kw):
+        self.ix, self.kw = ix, kw
+
+    def search_batch(self, q_off, qt, k, **more):
+        return self.ix.search_batch(q_off, qt, k, **self.kw, **more)
+
+
+def test_rescore_shares_every_structure_member(native, ctx):
+    """A rescore takes its base's structure and bounds whole (build.cpp
+    rescore_one assigns fgh::IndexStructure / IndexBounds), so a member added to
+    them later cannot go missing.  5000 docs (two 4096-doc tiles, five sparse-rank
+    blocks) with a name field, facets, the forward index, deletions and both
+    kinds of rank words; rescored to the statistics of a namespace of 6000 docs
+    with one more deletion: every structure field of stats() is the base's, and
+    AND, OR, facet-filtered and phrase queries answer like the oracle / the
+    phrase reference over the 6000 docs with the other 1000 deleted (deleted
+    docs count in the statistics, so those are the rescore's)."""
+    import os
+
+    import phrase_ref as pr
+    from fugu_amd import synth
+    from oracle import oracle as orc
+    from test_gpu_phrase import check
+    from test_gpu_qtscore import _vs_oracle
+    n, n_all, V, nf = 5000, 6000, 4096, 8
+    c = synth.corpus(n_all, V)
+    off, tok = c.off.astype(np.uint64), c.tok.astype(np.uint32)
+    rng = np.random.default_rng(71)
+    lens = np.where(np.arange(n_all) % 3 == 0, rng.integers(1, 4, n_all), 0)
+    no = np.cumsum(np.concatenate([[0], lens])).astype(np.uint64)
+    nt = (rng.zipf(1.3, int(no[-1])) % V).astype(np.uint32)
+    fo = np.cumsum(np.concatenate([[0], rng.integers(0, 3, n_all)])).astype(np.uint64)
+    ft = rng.integers(0, nf, int(fo[-1])).astype(np.uint32)
+    dl = (rng.random(n) < 0.05).astype(np.uint8)
+    dl2 = dl.copy()
+    dl2[int(np.flatnonzero(dl == 0)[17])] = 1  # one more deletion
+    head = dict(name_off=no[:n + 1], name_tok=nt[:no[n]], facets=(fo[:n + 1], ft[:fo[n]], nf))
+    old = os.environ.get("FUGU_RANK_PLAIN_DIV")
+    os.environ["FUGU_RANK_PLAIN_DIV"] = "16"
+    try:
+        base = native.Index.from_docs(ctx, off[:n + 1], tok[:off[n]], V, deleted=dl, positions=True, **head)
+    finally:
+        if old is None:
+            os.environ.pop("FUGU_RANK_PLAIN_DIV", None)
+        else:
+            os.environ["FUGU_RANK_PLAIN_DIV"] = old
+    g = native.docs_stats(off, tok, V, no, nt, facets=(fo, ft, nf))
+    re = base.rescore(g, deleted=dl2)
+    sb, sr = base.stats(), re.stats()
+    assert 0 < sb.n_sparse_rank_terms < sb.n_rank_terms, (sb.n_sparse_rank_terms, sb.n_rank_terms)
+    for f in ("n_docs", "n_terms", "n_postings", "has_name", "n_facet_terms", "n_rank_terms", "n_sparse_rank_terms",
+              "rank_bytes", "has_positions", "device_bytes"):
+        assert getattr(sb, f) == getattr(sr, f), (f, getattr(sb, f), getattr(sr, f))
+    assert sb.has_name and sb.has_positions and sb.n_facet_terms == nf and sr.tot_tokens != sb.tot_tokens
+    dl_all = np.concatenate([dl2, np.ones(n_all - n, np.uint8)])
+    oi = orc.OracleIndex(V, off, tok, name_off=no, name_tok=nt, deleted=dl_all, threads=16, facet_off=fo,
+                         facet_tok=ft, n_fterms=nf)
+    q_off, qt = synth.queries(32, 2, 3, max_rank=V, seed_q=41)
+    _vs_oracle(re, oi, q_off, qt, 100, native.MODE_AND, "and")
+    _vs_oracle(re, oi, q_off, qt, 100, native.MODE_OR, "or")
+    flt = dict(f_off=np.arange(33, dtype=np.uint32), f_terms=(np.arange(32) % nf).astype(np.uint32))
+    _vs_oracle(_Filtered(re, **flt), _Filtered(oi, **flt), q_off, qt, 100, native.MODE_AND, "facet")
+    # a phrase: two adjacent tokens of an alive doc, against the reference under the same statistics
+    docs = [tok[off[i]:off[i + 1]] for i in range(n)]
+    text, name = pr.Field(docs), pr.Field([nt[no[i]:no[i + 1]] for i in range(n)])
+    st = pr.Stats(g.n_docs, g.tot_tokens, g.df_text, g.df_name)
+    d0 = int(np.flatnonzero(dl2 == 0)[3])
+    phrase = [int(docs[d0][0]), int(docs[d0][1])]
+    want = [pr.search(text, name, st, phrase, [0, 1], 100, deleted=dl2)[:2]]
+    assert d0 in want[0][1] or len(want[0][1]) == 100
+    s, d, m = re.search_batch([0, 2], phrase, 100, phrase_len=[2, 0], phrase_pos=[0, 1])
+    check(s, d, m, want, 100, "phrase")
+    for x in (re, base, oi):
+        x.close()

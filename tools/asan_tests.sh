@@ -1,6 +1,6 @@
 #!/bin/bash
 # The CPU test suite (pytest -m "not gpu") against ASan + UBSan builds of the
-# host code: libfugu's host half (fugu.cpp, host.cpp; the device kernels are
+# host code: libfugu's host half (fugu.cpp, build.cpp, plan.cpp, host.cpp; the device kernels are
 # not instrumented) and the CPU oracle.
 # Python is not instrumented, so the ASan runtime is preloaded; leak checking
 # is off (the interpreter's own allocations are not ours to fix).

@@ -8,7 +8,7 @@ import hashlib
 import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ("kernels.hip", "fg_internal.h", "fugu.cpp", "Makefile")
+SOURCES = ("kernels.hip", "fg_internal.h", "fugu.cpp", "build.cpp", "plan.cpp", "Makefile")
 
 
 def lib_id(csrc=None):
