@@ -418,6 +418,58 @@ __host__ __device__ inline uint32_t slot_query(const DevPlan& pl, uint32_t v) {
   return pl.seg_nq ? v % pl.seg_nq : v;
 }
 
+// Device view of one (snapshot, query slice) pass of fg_count_batch (count.cpp;
+// DESIGN.md §12): hit totals and facet counts, no scores.  Query slot i of the
+// slice owns the bitmap match[i * words .. + words) (one bit per doc, zeroed
+// per pass); the kernels run back to back on one stream:
+//   k_cfilter  one bit per doc of each distinct facet clause list (the union
+//              of its lists) into fbits[f * words ..];
+//   k_cmatch   work items (slot, kCountChunk postings of a driver list): a
+//              Should-only query drives every Should list, a Must-driven one its
+//              shortest Must list, a textless filtered one the filter's facet
+//              lists; AllQuery's items fill its words with ones.  Each doc is
+//              probed in the slot's other Must lists and its MustNot lists
+//              (term_has_doc), tested in the filter's bitmap, then set in match;
+//   k_ccount   match &= alive, the bits at or past N cleared, popcount into
+//              total[q0 + i];
+//   k_cfacet   work items (count term j, kCountFacetChunk postings of its facet
+//              list): the docs are loaded once and tested in every slot's bitmap,
+//              count[(q0 + i) * n_count + j] += hits.
+// total / count are the whole batch's (zeroed once per call) and sum over the
+// snapshots of a namespace (disjoint docs).
+// (constants of their own, not the k_conj tuning macros: count.cpp is compiled once for every variant build)
+constexpr uint32_t kCountItems = 8;                  // k_cmatch: driver postings per lane
+constexpr uint32_t kCountChunk = kThreads * kCountItems;  // ... per work item (2048)
+constexpr uint32_t kCountFacetChunk = kFmaskChunk;   // facet postings per k_cfilter / k_cfacet item
+constexpr uint32_t kCountFacetItems = kCountFacetChunk / kThreads;  // ... per lane of k_cfacet (registers)
+constexpr uint32_t kCountWordChunk = 2048;           // bitmap words per k_ccount workgroup / k_cmatch fill item
+constexpr uint32_t kCountTile = 64;                  // k_cfacet: slots per LDS accumulation round
+constexpr uint32_t kCountText = 0, kCountFacet = 1, kCountFill = 2;  // DevCount::w_kind
+struct DevCount {
+  uint32_t nq;                  // slots of the slice
+  uint32_t q0;                  // batch query of slot 0
+  uint32_t words;               // ceil(N / 32)
+  uint32_t n_count;
+  uint32_t n_fchunks, n_items, n_cchunks;
+  uint32_t* match;              // [nq * words] workspace, zeroed per pass
+  uint32_t* fbits;              // [n_filters * words] workspace, zeroed per pass
+  unsigned long long* total;    // [batch queries]
+  unsigned long long* count;    // [batch queries * n_count]
+  const uint32_t* fc_filter;    // [n_fchunks] k_cfilter item -> filter
+  const uint32_t* fc_term;      // [n_fchunks] facet term
+  const uint32_t* fc_start;     // [n_fchunks] first posting within the term's list
+  const uint32_t* w_q;          // [n_items] k_cmatch item -> slot
+  const uint32_t* w_kind;       // [n_items] kCountText / kCountFacet / kCountFill
+  const uint32_t* w_term;       // [n_items] driver term (text or facet id of the snapshot); kCountFill: unused
+  const uint32_t* w_start;      // [n_items] first posting within the driver list; kCountFill: first word
+  const uint32_t* q_m;          // [nq] qm_pack(probed terms, of which Must, of which MustNot)
+  const uint32_t* q_terms;      // [nq * kMaxTerms] probed terms: [other Musts][MustNots]
+  const uint32_t* q_filter;     // [nq] the slot's filter (fbits row) or 0xFFFFFFFF
+  const uint32_t* cc_j;         // [n_cchunks] k_cfacet item -> index in count_terms
+  const uint32_t* cc_term;      // [n_cchunks] facet term
+  const uint32_t* cc_start;     // [n_cchunks] first posting within the term's list
+};
+
 constexpr uint32_t kDiagPerWg = 16;  // u64 stamps per workgroup in diagnostic builds
 
 // Key of a hit: larger is better.  (score bits << 32) | ~doc orders by
@@ -518,6 +570,9 @@ hipError_t launch_phrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 // out_shard != nullptr: the merged select of a multi-snapshot plan (one list per batch query)
 hipError_t launch_final(const DevPlan& pl, float* out_score, uint32_t* out_doc, uint32_t* out_n, hipStream_t s,
                         uint32_t* out_shard = nullptr);
+// fg_count_batch's four kernels of one pass, back to back on s (a kernel with no items is skipped);
+// ev: 5 events recorded around them, or nullptr
+hipError_t launch_count(const DevIndex& ix, const DevCount& c, hipStream_t s, hipEvent_t* ev = nullptr);
 hipError_t launch_rank(const uint32_t* doc, const uint64_t* slot_base, const uint32_t* slot_n, uint32_t n_slots,
                        uint32_t n_words, uint64_t* out, hipStream_t s);
 hipError_t launch_score(const ScoreJob& j, uint32_t n_chunks, hipStream_t s);

@@ -1217,6 +1217,100 @@ std::vector<std::string> filter_list(const char* const* filters, uint32_t n) {
   return v;
 }
 
+// searcher.search(&query, &(Count, FacetCollector)) over the namespace's current
+// segments (src/db/facet.rs): the query's hit total and, for every facet term of
+// `cterms` (facet dictionary ids), the matching docs under it -- ONE
+// fg_count_batch call.  query NULL / blank: AllQuery.  The query is parsed and
+// the filters built as search_hits does; a phrase clause is FG_EUNSUPPORTED.
+int count_query(Namespace& ns, const char* query, const std::vector<std::string>& filters,
+                const std::vector<uint32_t>& cterms, uint64_t* total, std::vector<uint64_t>& counts) {
+  *total = 0;
+  counts.assign(cterms.size(), 0);
+  const std::string_view qv = query ? query : "";
+  std::vector<std::string> terms;
+  std::vector<uint8_t> occur;
+  const bool empty_text = blank(qv);
+  if (!empty_text) {
+    std::vector<Clause> cls;
+    std::string why;
+    int rc = parse_clauses(qv, cls, why);
+    if (rc) return hfail(rc, "query outside the device subset: " + why);
+    for (Clause& c : cls) {
+      if (c.terms.size() > 1) return hfail(FG_EUNSUPPORTED, "query outside the device subset: phrase clause in a count query");
+      terms.push_back(std::move(c.terms[0]));
+      occur.push_back(c.occur);
+    }
+  }
+  std::vector<std::string> clauses;
+  bool facet_all = false;
+  const bool filtered = facet_clauses(filters, clauses, &facet_all);
+  if (filtered && facet_all && !empty_text)
+    return hfail(FG_EUNSUPPORTED, "query outside the device subset: text query AND an AllQuery facet filter");
+  std::shared_ptr<Snapshot> snap;
+  {
+    std::shared_lock<std::shared_mutex> l(ns.snap_mu);
+    snap = ns.snap;  // held until the counts are back, as a search holds its snapshot
+  }
+  if (!snap || snap->segs.empty()) return FG_OK;  // nothing committed yet
+  std::vector<uint32_t> ids, fids;
+  for (auto& t : terms) {
+    const uint32_t id = ns.dict.find(t);
+    ids.push_back(id == TermDict::kMissing ? FG_TERM_MISSING : id);
+  }
+  for (auto& c : clauses) {
+    const uint32_t id = ns.fdict.find(c);
+    fids.push_back(id == TermDict::kMissing ? FG_TERM_MISSING : id);
+  }
+  std::vector<fg_index*> segs;
+  for (const Segment& seg : snap->segs) segs.push_back(seg.ix);
+  const uint32_t q_off[2] = {0, (uint32_t)ids.size()};
+  const uint32_t f_off[2] = {0, (uint32_t)fids.size()};
+  fg_query_batch qb{1, q_off, ids.data(), FG_MODE_AND, fids.empty() ? nullptr : f_off, fids.data(), occur.data()};
+  int rc = fg_count_batch(segs.data(), (uint32_t)segs.size(), &qb, cterms.data(), (uint32_t)cterms.size(), total,
+                          cterms.empty() ? nullptr : counts.data());
+  if (rc) return hfail(rc, fg_last_error());
+  return FG_OK;
+}
+
+// The facet dictionary's terms under `root` (encoded), root excluded, at most
+// `depth` levels below it (depth < 0: all), in encoded byte order -- which is the
+// pre-order of the tree with every node's children in FacetCounts::get's order
+// (the U+0000 separator sorts below every other byte).
+struct FacetTerm { std::string enc; uint32_t id; };
+std::vector<FacetTerm> facet_terms_under(const Namespace& ns, const std::string& root, long depth) {
+  std::vector<FacetTerm> v;
+  const std::string pre = root.empty() ? std::string() : root + '\0';
+  const uint32_t n = ns.fdict.size();
+  for (uint32_t id = 0; id < n; ++id) {
+    const std::string_view k = ns.fdict.key(id);
+    if (k.empty() || k.size() <= pre.size() || k.compare(0, pre.size(), pre) != 0) continue;
+    const long levels = 1 + (long)std::count(k.begin() + pre.size(), k.end(), '\0');
+    if (depth >= 0 && levels > depth) continue;
+    v.push_back(FacetTerm{std::string(k), id});
+  }
+  std::sort(v.begin(), v.end(), [](const FacetTerm& a, const FacetTerm& b) { return a.enc < b.enc; });
+  return v;
+}
+
+// (facet, count) pairs as '\n'-separated Display strings + a count array
+int facets_out(const std::vector<FacetTerm>& ft, const std::vector<uint64_t>& counts, char* out_paths, size_t cap,
+               size_t* len, uint64_t* out_counts, uint32_t count_cap, uint32_t* n_out) {
+  std::string o;
+  uint32_t n = 0;
+  for (size_t i = 0; i < ft.size(); ++i) {
+    if (!counts[i]) continue;  // FacetCounts lists the facets some matching doc has
+    if (n) o.push_back('\n');
+    o += facet_display(ft[i].enc);
+    if (out_counts && n < count_cap) out_counts[n] = counts[i];
+    ++n;
+  }
+  // both sizes are reported before either buffer is judged: one retry fits both
+  if (n_out) *n_out = n;
+  if (len) *len = o.size();
+  if (out_counts && n > count_cap) return hfail(FG_EINVAL, "count buffer too small");
+  return copy_out(o, out_paths, cap, len);
+}
+
 // urlencoding::decode: %XX escapes become bytes (a malformed escape stays as
 // it is); the result must be UTF-8, else "Invalid URL encoding in query"
 bool url_decode(std::string& q) {
@@ -2546,6 +2640,71 @@ int fg_db_doc_facets(fg_db* db, const char* nsname, uint32_t doc, char* out, siz
     if (j) o.push_back('\n');
     o += facet_display(ns->docs[doc].facets[j]);
   }
+  return copy_out(o, out, cap, len);
+}
+
+int fg_db_facet_counts(fg_db* db, const char* nsname, const char* query, const char* const* filters,
+                       uint32_t n_filters, const char* root_path, char* out_paths, size_t cap, size_t* len,
+                       uint64_t* out_counts, uint32_t count_cap, uint32_t* n_out, uint64_t* total) {
+  if (!db || !root_path) return hfail(FG_EINVAL, "bad arguments");
+  auto ns = find_ns(db, nsname);
+  if (!ns) return hfail(FG_ENOTFOUND, std::string("Namespace '") + (nsname ? nsname : "") + "' not found");
+  std::string root;
+  if (!facet_from_text(root_path, root)) return hfail(FG_EINVAL, "Facet::from_text: path must start with '/'");
+  const std::vector<FacetTerm> ft = facet_terms_under(*ns, root, 1);  // FacetCounts::get(root): the direct children
+  std::vector<uint32_t> ids;
+  for (auto& t : ft) ids.push_back(t.id);
+  uint64_t tot = 0;
+  std::vector<uint64_t> counts;
+  if (int rc = count_query(*ns, query, filter_list(filters, n_filters), ids, &tot, counts)) return rc;
+  if (total) *total = tot;
+  return facets_out(ft, counts, out_paths, cap, len, out_counts, count_cap, n_out);
+}
+
+int fg_db_facet_tree(fg_db* db, const char* nsname, int max_depth, char* out_paths, size_t cap, size_t* len,
+                     uint64_t* out_counts, uint32_t count_cap, uint32_t* n_out) {
+  if (!db) return hfail(FG_EINVAL, "bad arguments");
+  auto ns = find_ns(db, nsname);
+  if (!ns) return hfail(FG_ENOTFOUND, std::string("Namespace '") + (nsname ? nsname : "") + "' not found");
+  // collect_facets_recursive (src/db/facet.rs:199-233) runs one AllQuery collector
+  // per node and stops below max_depth; here every dictionary term within the
+  // depth is a count term of ONE device call, and a node with no matching doc (so
+  // none below it either) drops out as it does from FacetCounts::get
+  const std::vector<FacetTerm> ft = facet_terms_under(*ns, std::string(), max_depth < 0 ? -1L : (long)max_depth);
+  std::vector<uint32_t> ids;
+  for (auto& t : ft) ids.push_back(t.id);
+  uint64_t tot = 0;
+  std::vector<uint64_t> counts;
+  if (int rc = count_query(*ns, nullptr, {}, ids, &tot, counts)) return rc;
+  return facets_out(ft, counts, out_paths, cap, len, out_counts, count_cap, n_out);
+}
+
+int fg_db_facets_json(fg_db* db, const char* nsname, char* out, size_t cap, size_t* len) {
+  if (!db) return hfail(FG_EINVAL, "bad arguments");
+  auto ns = find_ns(db, nsname);
+  if (!ns) return hfail(FG_ENOTFOUND, std::string("Namespace '") + (nsname ? nsname : "") + "' not found");
+  // the handler calls DatasetManager::get_namespace_facets(&namespace, "/") (src/db/config.rs:251-255), which is
+  // get_facets_at("/") on the namespace's dataset: the direct children of the root
+  const std::vector<FacetTerm> ft = facet_terms_under(*ns, std::string(), 1);
+  std::vector<uint32_t> ids;
+  for (auto& t : ft) ids.push_back(t.id);
+  uint64_t tot = 0;
+  std::vector<uint64_t> counts;
+  if (int rc = count_query(*ns, nullptr, {}, ids, &tot, counts)) return rc;
+  // json!({"status", "namespace", "facets": [{"path", "count"}]}): serde_json Values, keys in byte order
+  std::string o = "{\"facets\":[";
+  bool first = true;
+  for (size_t i = 0; i < ft.size(); ++i) {
+    if (!counts[i]) continue;
+    if (!first) o.push_back(',');
+    first = false;
+    o += "{\"count\":" + std::to_string(counts[i]) + ",\"path\":";
+    json_str(o, facet_display(ft[i].enc));
+    o.push_back('}');
+  }
+  o += "],\"namespace\":";
+  json_str(o, ns->name);
+  o += ",\"status\":\"success\"}";
   return copy_out(o, out, cap, len);
 }
 

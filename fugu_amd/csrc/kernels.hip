@@ -2993,4 +2993,187 @@ hipError_t launch_merge(uint32_t n_shards, uint32_t n_queries, uint32_t k, const
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- fg_count_batch
+// Count + FacetCollector (tantivy searcher.search(&query, &(Count,
+// FacetCollector)), the collectors of reference src/db/facet.rs): one pass of
+// DevCount over one snapshot and one slice of the batch.  No scores, no top-k,
+// no pruning: a query's match set is a doc bitmap, its total a popcount, a facet
+// count the popcount of the bitmap under the facet term's postings.  Kernel
+// boundaries order the four kernels; none waits for another workgroup.
+namespace {
+
+// The union of each distinct facet clause list as one bit per doc: a workgroup
+// per kCountFacetChunk postings of one (filter, facet term), as k_fmask streams
+// them.  Postings ascend, so a wave's atomics fall into a few words.
+__global__ __launch_bounds__(kThreads) void k_cfilter(DevIndex ix, DevCount c) {
+  const uint32_t i = blockIdx.x;
+  const uint32_t f = c.fc_filter[i], t = c.fc_term[i], st = c.fc_start[i];
+  const uint64_t b0 = ix.foff[t];
+  const uint32_t n = (uint32_t)(ix.foff[t + 1] - b0);
+  const uint32_t end = st + min(n - st, kCountFacetChunk);
+  uint32_t* bits = c.fbits + (size_t)f * c.words;
+  for (uint32_t p = st + threadIdx.x; p < end; p += kThreads) {
+    const uint32_t d = ix.fdoc[b0 + p];
+    atomicOr(&bits[d >> 5], 1u << (d & 31u));
+  }
+}
+
+// The match bitmap of every slot.  A work item is kCountChunk postings of one of
+// the slot's driver lists, kCountItems consecutive docs per lane in lockstep: the slot's other
+// Must lists must hold the doc and its MustNot lists must not (term_has_doc: rank
+// words, sparse rank words or the bucket directory, as the term has), then the
+// slot's filter-union bit, then one atomic OR.  Several drivers of a Should-only
+// slot set the same bit: OR is idempotent.  Deleted docs are cleared by k_ccount.
+__global__ __launch_bounds__(kThreads) void k_cmatch(DevIndex ix, DevCount c) {
+  const uint32_t item = blockIdx.x;
+  const uint32_t q = c.w_q[item], kind = c.w_kind[item], st = c.w_start[item];
+  uint32_t* __restrict__ m = c.match + (size_t)q * c.words;
+  if (kind == kCountFill) {  // AllQuery: every word ones (k_ccount masks the deleted docs and the tail)
+    const uint32_t end = st + min(c.words - st, kCountWordChunk);
+    for (uint32_t x = st + threadIdx.x; x < end; x += kThreads) m[x] = 0xFFFFFFFFu;
+    return;
+  }
+  const uint32_t t = c.w_term[item];
+  const uint32_t* __restrict__ list;
+  uint32_t n;
+  if (kind == kCountFacet) {
+    const uint64_t b0 = ix.foff[t];
+    list = ix.fdoc + b0;
+    n = (uint32_t)(ix.foff[t + 1] - b0);
+  } else {
+    const uint64_t b0 = ix.off[t];
+    list = ix.doc + b0;
+    n = (uint32_t)(ix.off[t + 1] - b0);
+  }
+  const uint32_t cnt = min(n - st, kCountChunk);
+  uint32_t d[kCountItems];
+  uint32_t live = 0;
+#pragma unroll
+  for (uint32_t r = 0; r < kCountItems; ++r) {
+    const uint32_t p = threadIdx.x * kCountItems + r;  // a lane's docs are consecutive postings: see the merge below
+    d[r] = 0;
+    if (p < cnt) {
+      d[r] = list[st + p];
+      live |= 1u << r;
+    }
+  }
+  const uint32_t qm = c.q_m[q], nt = qm_terms(qm), nmust = qm_must(qm);
+  const uint32_t* __restrict__ qt = c.q_terms + (size_t)q * kMaxTerms;
+  for (uint32_t j = 0; j < nt; ++j) {
+    const uint32_t u = qt[j];
+    const uint32_t meta = ix.tmeta[u], dir_off = ix.dir_off[u];
+    const uint64_t base = ix.off[u];
+    const bool want = j < nmust;
+#pragma unroll
+    for (uint32_t r = 0; r < kCountItems; ++r)
+      if ((live >> r) & 1u)
+        if (term_has_doc(ix, meta, base, dir_off, d[r]) != want) live &= ~(1u << r);
+  }
+  const uint32_t flt = c.q_filter[q];
+  if (flt != kInvalid) {
+    const uint32_t* __restrict__ fb = c.fbits + (size_t)flt * c.words;
+#pragma unroll
+    for (uint32_t r = 0; r < kCountItems; ++r)
+      if (((live >> r) & 1u) && !((fb[d[r] >> 5] >> (d[r] & 31u)) & 1u)) live &= ~(1u << r);
+  }
+  // the lane's docs ascend, so those of one bitmap word are neighbours: their bits
+  // go out in one atomic (a dense driver list puts all kCountItems in one or two words)
+  uint32_t cw = kInvalid, cb = 0;
+#pragma unroll
+  for (uint32_t r = 0; r < kCountItems; ++r)
+    if ((live >> r) & 1u) {
+      const uint32_t w = d[r] >> 5, b = 1u << (d[r] & 31u);
+      if (w != cw) {
+        if (cb) atomicOr(&m[cw], cb);
+        cw = w;
+        cb = 0;
+      }
+      cb |= b;
+    }
+  if (cb) atomicOr(&m[cw], cb);
+}
+
+// match &= alive, the bits at or past N cleared (k_cfacet then reads finished
+// bitmaps), and the slot's total: popcounts summed per wave, one atomic add per
+// workgroup.  Workgroup = (slot, kCountWordChunk words).
+__global__ __launch_bounds__(kThreads) void k_ccount(DevIndex ix, DevCount c, uint32_t wchunks) {
+  __shared__ uint32_t part[kThreads / 64];
+  const uint32_t q = blockIdx.x / wchunks, w0 = (blockIdx.x % wchunks) * kCountWordChunk;
+  uint32_t* __restrict__ m = c.match + (size_t)q * c.words;
+  const uint32_t end = w0 + min(c.words - w0, kCountWordChunk);
+  const uint32_t tail = ix.n_docs & 31u;
+  uint32_t cnt = 0;
+  for (uint32_t x = w0 + threadIdx.x; x < end; x += kThreads) {
+    uint32_t v = m[x];
+    if (ix.alive) v &= ix.alive[x];
+    if (tail && x == c.words - 1) v &= (1u << tail) - 1u;
+    m[x] = v;
+    cnt += (uint32_t)__popc(v);
+  }
+  for (uint32_t o = 32; o; o >>= 1) cnt += __shfl_down(cnt, o);
+  if (lane_id() == 0) part[wave_id()] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t s = 0;
+    for (uint32_t i = 0; i < kThreads / 64; ++i) s += part[i];
+    if (s) atomicAdd(&c.total[c.q0 + q], (unsigned long long)s);
+  }
+}
+
+// Facet counts.  Workgroup = (count term j, kCountFacetChunk postings of its
+// facet list): each lane loads its kCountFacetItems docs once into registers,
+// then every slot of the slice tests them in its finished bitmap; hits are
+// counted per wave by ballot + popcount, summed per workgroup in LDS
+// (kCountTile slots per round) and added with one atomic per (workgroup, slot).
+__global__ __launch_bounds__(kThreads) void k_cfacet(DevIndex ix, DevCount c) {
+  __shared__ uint32_t acc[kCountTile];
+  const uint32_t i = blockIdx.x;
+  const uint32_t j = c.cc_j[i], t = c.cc_term[i], st = c.cc_start[i];
+  const uint64_t b0 = ix.foff[t];
+  const uint32_t n = (uint32_t)(ix.foff[t + 1] - b0);
+  const uint32_t cnt = min(n - st, kCountFacetChunk);
+  uint32_t d[kCountFacetItems];
+#pragma unroll
+  for (uint32_t r = 0; r < kCountFacetItems; ++r) {
+    const uint32_t p = r * kThreads + threadIdx.x;
+    d[r] = p < cnt ? ix.fdoc[b0 + st + p] : kInvalid;
+  }
+  for (uint32_t s0 = 0; s0 < c.nq; s0 += kCountTile) {
+    const uint32_t ns = min(c.nq - s0, kCountTile);
+    if (threadIdx.x < kCountTile) acc[threadIdx.x] = 0;
+    __syncthreads();
+    for (uint32_t s = 0; s < ns; ++s) {
+      const uint32_t* __restrict__ m = c.match + (size_t)(s0 + s) * c.words;
+      uint32_t h = 0;  // wave-uniform
+#pragma unroll
+      for (uint32_t r = 0; r < kCountFacetItems; ++r) {
+        const bool hit = d[r] != kInvalid && ((m[d[r] >> 5] >> (d[r] & 31u)) & 1u);
+        h += (uint32_t)__popcll(__ballot(hit));
+      }
+      if (lane_id() == 0 && h) atomicAdd(&acc[s], h);
+    }
+    __syncthreads();
+    if (threadIdx.x < ns && acc[threadIdx.x])
+      atomicAdd(&c.count[(size_t)(c.q0 + s0 + threadIdx.x) * c.n_count + j], (unsigned long long)acc[threadIdx.x]);
+    __syncthreads();
+  }
+}
+
+}  // namespace
+
+// ev (or nullptr): 5 events recorded around the four kernels (fg_count_trace)
+hipError_t launch_count(const DevIndex& ix, const DevCount& c, hipStream_t s, hipEvent_t* ev) {
+  if (ev) (void)hipEventRecord(ev[0], s);
+  if (c.n_fchunks) k_cfilter<<<c.n_fchunks, kThreads, 0, s>>>(ix, c);
+  if (ev) (void)hipEventRecord(ev[1], s);
+  if (c.n_items) k_cmatch<<<c.n_items, kThreads, 0, s>>>(ix, c);
+  if (ev) (void)hipEventRecord(ev[2], s);
+  const uint32_t wchunks = (c.words + kCountWordChunk - 1) / kCountWordChunk;
+  if (c.nq && wchunks) k_ccount<<<c.nq * wchunks, kThreads, 0, s>>>(ix, c, wchunks);
+  if (ev) (void)hipEventRecord(ev[3], s);
+  if (c.n_cchunks && c.nq) k_cfacet<<<c.n_cchunks, kThreads, 0, s>>>(ix, c);
+  if (ev) (void)hipEventRecord(ev[4], s);
+  return hipGetLastError();
+}
+
 }  // namespace fg

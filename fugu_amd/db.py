@@ -29,6 +29,7 @@ HOST_EXPORTS = (
     "fg_db_upsert_record", "fg_db_upsert_batch", "fg_db_search_ex", "fg_db_search_json_ex", "fg_db_doc_facets", "fg_facet_tokens",
     "fg_facet_clauses", "fg_db_search_json_post", "fg_db_merge_wait", "fg_db_merge_info_get", "fg_db_segment_docs",
     "fg_search_trace", "fg_merge_policy_pick", "fg_parse_query_clauses",
+    "fg_db_facet_counts", "fg_db_facet_tree", "fg_db_facets_json",
 )
 SEARCH_PHASES = ("parse_dict", "plan", "launch", "wait_kernels_d2h", "json_fetch", "total")  # FG_SEARCH_PHASES
 
@@ -92,6 +93,11 @@ _sig("fg_merge_policy_pick", C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_ui
 _sig("fg_parse_query", _s, C.POINTER(C.c_int), _s, _sz, C.POINTER(_sz))
 _sig("fg_parse_query_occur", _s, _s, _sz, C.POINTER(_sz))
 _sig("fg_parse_query_clauses", _s, _s, _sz, C.POINTER(_sz))
+_sig("fg_db_facet_counts", _p, _s, _s, C.POINTER(_s), C.c_uint32, _s, _s, _sz, C.POINTER(_sz), C.POINTER(C.c_uint64),
+     C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64))
+_sig("fg_db_facet_tree", _p, _s, C.c_int, _s, _sz, C.POINTER(_sz), C.POINTER(C.c_uint64), C.c_uint32,
+     C.POINTER(C.c_uint32))
+_sig("fg_db_facets_json", _p, _s, _s, _sz, C.POINTER(_sz))
 
 
 class NotFound(native.FuguError):
@@ -136,6 +142,22 @@ def _strs(items):
     items = list(items or [])
     arr = (_s * max(1, len(items)))(*[x.encode() for x in items])
     return arr, len(items)
+
+
+def _facets_call(call, cap: int = 1 << 16, ncap: int = 1 << 12) -> list:
+    """call(buf, cap, len*, counts, ncap, n*) -> [(path, count)]; called again with
+    the reported sizes when a buffer was too small."""
+    while True:
+        buf = C.create_string_buffer(cap)
+        cnt = (C.c_uint64 * ncap)()
+        ln, n = _sz(0), C.c_uint32(0)
+        rc = call(buf, cap, C.byref(ln), cnt, ncap, C.byref(n))
+        if rc == native.FG_EINVAL and (ln.value + 1 > cap or n.value > ncap):
+            cap, ncap = max(cap, ln.value + 1), max(ncap, n.value)
+            continue
+        _check(rc)
+        paths = buf.raw[:ln.value].decode().split("\n") if n.value else []
+        return list(zip(paths, [int(cnt[i]) for i in range(n.value)]))
 
 
 def facet_tokens(path: str) -> list:
@@ -326,6 +348,28 @@ class Database:
         t, a = C.c_uint64(0), C.c_uint64(0)
         _check(_lib.fg_db_doc_count(self._h, _b(namespace), C.byref(t), C.byref(a)))
         return t.value, a.value
+
+    # -- facet counts (src/db/facet.rs; fg_count_batch on the device) --
+    def facet_counts(self, namespace: Optional[str], root: str = "/", query: Optional[str] = None, filters=None):
+        """([(facet path, count)], total): the direct children of `root` with a
+        nonzero count among the docs matching `query` (None / blank: AllQuery) and
+        `filters`, in encoded-facet order, and the number of matching docs."""
+        farr, nf = _strs(filters)
+        total = C.c_uint64(0)
+        pairs = _facets_call(lambda buf, cap, ln, cnt, ncap, n: _lib.fg_db_facet_counts(
+            self._h, _b(namespace), _b(query), farr, nf, root.encode(), buf, cap, ln, cnt, ncap, n, C.byref(total)))
+        return pairs, total.value
+
+    def facet_tree(self, namespace: Optional[str] = None, max_depth: Optional[int] = None) -> list:
+        """[(facet path, count)] of the whole tree under "/" in pre-order, at most
+        max_depth levels deep (None: no limit), from one device call."""
+        d = -1 if max_depth is None else int(max_depth)
+        return _facets_call(lambda buf, cap, ln, cnt, ncap, n: _lib.fg_db_facet_tree(
+            self._h, _b(namespace), d, buf, cap, ln, cnt, ncap, n))
+
+    def facets_json(self, namespace: Optional[str] = None) -> str:
+        """The GET /namespaces/{ns}/facets body."""
+        return _string_call(_lib.fg_db_facets_json, self._h, _b(namespace))
 
     # -- search (Dataset::search / perform_search) --
     def search(self, namespace: Optional[str], query: str, page: int = 0, per_page: int = 20, filters=None):

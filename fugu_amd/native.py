@@ -33,6 +33,8 @@ FG_MAX_TERMS = 16
 FG_MAX_FACET_CLAUSES = 8
 FG_MAX_K = 1024
 FG_TERM_MISSING = 0xFFFFFFFF
+FG_MAX_COUNT_TERMS = 1 << 20  # count terms per fg_count_batch call
+FG_MAX_COUNT_CELLS = 1 << 25  # n_queries * n_count per call
 MODE_AND = 0
 MODE_OR = 1
 OCCUR_MUST = 0
@@ -58,6 +60,7 @@ EXPORTS = (
     "fg_ctx_peer_access", "fg_plan_link", "fg_bytes_model_or", "fg_plan_create_multi", "fg_plan_execute_merged", "fg_index_term_kth",
     "fg_model_batch", "fg_abi_version", "fg_index_term_ladder", "fg_kth_floor_combine", "fg_index_set_kth_floor",
     "fg_plan_set_peers", "fg_plan_ipc_export", "fg_plan_set_ipc_peers", "fg_plan_reset",
+    "fg_count_batch", "fg_count_trace",
 )
 LADDER_KS = (1, 2, 3, 5, 10, 13, 20, 25, 50, 100, 125, 250, 500, 1000)  # FG_LADDER_LEVELS ranks
 KTH_KS = (1, 10, 20, 100, 1000)  # fg_index_term_kth / fg_index_set_kth_floor ranks
@@ -190,6 +193,8 @@ _sig("fg_merge_shards", C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, _p, _p, _p,
 _sig("fg_bytes_model", C.c_int, _p, C.POINTER(QueryBatch), C.c_uint32, _f64p)
 _sig("fg_bytes_model_gpu", C.c_int, _p, C.POINTER(QueryBatch), C.c_uint32, _f64p)
 _sig("fg_model_batch", C.c_int, _p, C.POINTER(QueryBatch), C.c_uint32, _f32p, _f64p, C.POINTER(ModelOut))
+_sig("fg_count_batch", C.c_int, C.POINTER(_p), C.c_uint32, C.POINTER(QueryBatch), _u32p, C.c_uint32, _u64p, _u64p)
+_sig("fg_count_trace", C.c_int, C.c_int, _f64p, _u32p)
 _sig("fg_abi_version", C.c_int)
 if _lib.fg_abi_version() != ABI_VERSION:
     raise ImportError(f"{LIB_PATH} has ABI {_lib.fg_abi_version()}, this binding follows {ABI_VERSION}: rebuild")
@@ -760,6 +765,35 @@ def search_sharded(indexes, q_off, terms, k: int, mode: int = MODE_AND, f_off=No
     _check(_lib.fg_search_sharded(ctx._h if ctx is not None else None, hs, len(indexes), C.byref(qb), k,
                                   _ptr(score, _f32p), _ptr(doc, _u32p), _ptr(shard, _u32p), _ptr(n, _u32p)))
     return score.reshape(nq, k), doc.reshape(nq, k), shard.reshape(nq, k), n
+
+
+def count_batch(indexes, q_off, terms, count_terms=(), mode: int = MODE_AND, f_off=None, f_terms=None, occur=None,
+                phrase_len=None, phrase_pos=None):
+    """fg_count_batch: tantivy's (Count, FacetCollector) for every query of the
+    batch over the snapshots `indexes` of one namespace (one device), summed.
+    count_terms: facet term ids, given once per batch.  Returns (total [nq] u64,
+    count [nq, n_count] u64); no scores, no top-k."""
+    qb, keep = _batch(q_off, terms, mode, f_off, f_terms, occur, phrase_len, phrase_pos)
+    nq = qb.n_queries
+    ct = _u32(count_terms)
+    hs = (_p * len(indexes))(*[ix._h for ix in indexes])
+    total = np.zeros(nq, np.uint64)
+    count = np.zeros(nq * len(ct), np.uint64)
+    _check(_lib.fg_count_batch(hs, len(indexes), C.byref(qb), _ptr(ct, _u32p) if len(ct) else None, len(ct),
+                               _ptr(total, _u64p), _ptr(count, _u64p) if len(ct) else None))
+    return total, count.reshape(nq, len(ct))
+
+
+COUNT_KERNELS = ("k_cfilter", "k_cmatch", "k_ccount", "k_cfacet")
+
+
+def count_trace(enable: int = -1):
+    """fg_count_trace: ({kernel: summed device ms}, calls) of this thread's count_batch
+    calls since the last read; enable 1 / 0 switches the timing, -1 leaves it."""
+    ms = np.zeros(4, np.float64)
+    n = C.c_uint32(0)
+    _check(_lib.fg_count_trace(enable, _ptr(ms, _f64p), C.byref(n)))
+    return dict(zip(COUNT_KERNELS, ms.tolist())), n.value
 
 
 def merge_shards(n_shards: int, n_queries: int, k: int, d_score: int, d_doc: int, d_n: int, d_out_score: int,

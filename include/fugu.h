@@ -436,6 +436,51 @@ int fg_plan_destroy(fg_plan* p);
 int fg_search_batch(fg_index* ix, const fg_query_batch* q, uint32_t k, float* out_score, uint32_t* out_doc,
                     uint32_t* out_n);
 
+/* ---- hit totals and facet counts ---------------------------
+ * Replaces: searcher.search(&query, &(Count, FacetCollector)) -- the collector
+ * behind the reference's facet routes (src/db/facet.rs: get_namespace_facets,
+ * list_facet, get_facets_at, and get_facet_tree's one AllQuery pass per tree
+ * node, :113-233).  New symbols only: FG_ABI_VERSION stays 6 and fg_query_batch
+ * is unchanged (no struct changed layout, no existing call changed contract).
+ *
+ * Every query of the batch is evaluated WITHOUT scores or top-k over the
+ * n_segs snapshots of one namespace (disjoint docs, one device; snapshots on
+ * several devices: FG_EUNSUPPORTED -- the sums are additive, a caller adds
+ * per-device results).  Match set, per snapshot: alive docs only; with a Must
+ * clause the docs of every Must term's merged (text U name) list, Should
+ * clauses ignored; without one the union of the Should lists; minus every
+ * MustNot list; a Must on FG_TERM_MISSING or a term the snapshot lacks empties
+ * the query there, a Should / MustNot on one is dropped; no positive clause: no
+ * matches.  Facet clauses (f_off / f_terms) intersect the text match with the
+ * union of their lists (a missing facet term matches nothing); without text
+ * terms the union alone, and without clauses AllQuery (every alive doc).  A
+ * phrase clause (phrase_len >= 2): FG_EUNSUPPORTED, "phrase clause in a count
+ * query".
+ *   out_total[i]               = |match(i)| summed over the snapshots (Count);
+ *   out_count[i * n_count + j] = |match(i) & postings(count_terms[j])| summed --
+ *     the facet field indexes every ancestor of a doc's facets once per doc, so
+ *     this is FacetCollector's count of the facet count_terms[j] encodes: the
+ *     matching docs with a facet at or below it, each once.  A count term that
+ *     is FG_TERM_MISSING or past a snapshot's facet terms counts 0 there.
+ * count_terms are facet term ids given once per batch; out_count may be NULL
+ * when n_count == 0.  Synchronous; thread-safe like fg_search_batch (the
+ * calling thread's stream, workspaces from the same pools).  The batch runs in
+ * slices of queries whose match bitmaps (N / 8 bytes per query and snapshot)
+ * fit 256 MiB (env FUGU_COUNT_WS_KB, in KiB, read per call).
+ * FG_EINVAL / FG_EUNSUPPORTED as fg_plan_create for q_off, f_off, occur and the
+ * per-query limits; n_count > FG_MAX_COUNT_TERMS or n_queries * n_count >
+ * FG_MAX_COUNT_CELLS: FG_EUNSUPPORTED. */
+#define FG_MAX_COUNT_TERMS 1048576  /* count terms per fg_count_batch call */
+#define FG_MAX_COUNT_CELLS 33554432 /* n_queries * n_count per call (8 B each on the device) */
+int fg_count_batch(fg_index* const* ixs, uint32_t n_segs, const fg_query_batch* q, const uint32_t* count_terms,
+                   uint32_t n_count, uint64_t* out_total, uint64_t* out_count);
+/* Diagnostic: per-kernel HIP-event timing of the CALLING thread's fg_count_batch
+ * calls while enabled (enable: 1 on, 0 off, -1 unchanged; off by default).
+ * ms_out[4] (may be NULL) = the summed device ms of k_cfilter, k_cmatch, k_ccount,
+ * k_cfacet since the last call, *calls (may be NULL) the fg_count_batch calls timed.
+ * Reading resets the sums. */
+int fg_count_trace(int enable, double* ms_out, uint32_t* calls);
+
 /* Cross-shard merge: per-shard top-k lists gathered from
  * n_shards GPUs (RCCL all-gather) merged into the global top-k by (score
  * desc, shard asc, doc asc).  Device pointers, layout [n_shards][n_queries][k]

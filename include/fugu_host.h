@@ -169,6 +169,33 @@ int fg_db_search_json_post(fg_db* db, const char* ns, const char* query, const c
 /* Stored facets of doc `doc` as Facet Display strings, '\n'-separated. */
 int fg_db_doc_facets(fg_db* db, const char* ns, uint32_t doc, char* out, size_t cap, size_t* len);
 
+/* ---- facet counts (src/db/facet.rs; fg_count_batch on the device).
+ * Facets come back as Facet Display strings, '\n'-separated, in encoded-facet
+ * byte order (FacetCounts::get's), with out_counts[i] the count of the i-th;
+ * *n_out = how many.  Both *len and *n_out are set whenever the count ran, also
+ * when a buffer is NULL or too small (out_paths: cap < *len + 1; out_counts:
+ * count_cap < *n_out; either: FG_EINVAL), so one retry with the reported sizes fits.  A facet no matching doc
+ * carries is not listed.  The namespace's current segments are counted under the
+ * snapshot reference a search holds; nothing committed yet: no facets. */
+/* list_facet / get_facets_at (:78-110), and the count the reference left
+ * commented out (src/db/search.rs:436-454) over ALL matches: the direct children
+ * of root_path ("/" = the top level) among the docs matching `query` (NULL or
+ * blank: AllQuery; parsed as fg_db_search_ex parses it; a phrase clause:
+ * FG_EUNSUPPORTED) and `filters`; *total (may be NULL) = the matching docs. */
+int fg_db_facet_counts(fg_db* db, const char* ns, const char* query, const char* const* filters, uint32_t n_filters,
+                       const char* root_path, char* out_paths, size_t cap, size_t* len, uint64_t* out_counts,
+                       uint32_t count_cap, uint32_t* n_out, uint64_t* total);
+/* get_facet_tree's collect_facets_recursive (:113-233) under "/": every facet
+ * with its AllQuery count in pre-order, at most max_depth levels deep (< 0: no
+ * limit; 0: nothing), from ONE device call instead of one collector pass per node. */
+int fg_db_facet_tree(fg_db* db, const char* ns, int max_depth, char* out_paths, size_t cap, size_t* len,
+                     uint64_t* out_counts, uint32_t count_cap, uint32_t* n_out);
+/* GET /namespaces/{ns}/facets (handlers/namespaces.rs:45-87 over
+ * DatasetManager::get_namespace_facets(ns, "/"), src/db/config.rs:251-255, which is
+ * get_facets_at("/") on the namespace's dataset: the direct children of the root):
+ * {"facets":[{"count":..,"path":..},..],"namespace":..,"status":"success"}. */
+int fg_db_facets_json(fg_db* db, const char* ns, char* out, size_t cap, size_t* len);
+
 /* Analyzer / parser exposed for tests: tokens separated by '\n'. */
 int fg_analyze(const char* text, char* out, size_t cap, size_t* len);
 /* mode (FG_MODE_AND / FG_MODE_OR: every clause Must / Should; FG_MODE_MIXED

@@ -32,6 +32,8 @@ pub const FG_EUNSUPPORTED: c_int = -5;  // outside the device subset: run tantiv
 pub const FG_MAX_TERMS: u32 = 16;
 pub const FG_MAX_FACET_CLAUSES: u32 = 8;
 pub const FG_MAX_K: u32 = 1024;
+pub const FG_MAX_COUNT_TERMS: u32 = 1 << 20;
+pub const FG_MAX_COUNT_CELLS: u32 = 1 << 25;
 pub const FG_HIST_BINS: u32 = 512;
 pub const FG_MAX_SEGMENTS: u32 = 64;
 pub const FG_TERM_MISSING: u32 = 0xFFFF_FFFF;
@@ -255,6 +257,9 @@ extern "C" {
     pub fn fg_plan_destroy(p: *mut fg_plan) -> c_int;
     pub fn fg_search_batch(ix: *mut fg_index, q: *const fg_query_batch, k: u32, out_score: *mut f32,
                            out_doc: *mut u32, out_n: *mut u32) -> c_int;
+    pub fn fg_count_batch(ixs: *const *mut fg_index, n_segs: u32, q: *const fg_query_batch, count_terms: *const u32,
+                          n_count: u32, out_total: *mut u64, out_count: *mut u64) -> c_int;
+    pub fn fg_count_trace(enable: c_int, ms_out: *mut f64, calls: *mut u32) -> c_int;
     pub fn fg_merge_shards(n_shards: u32, n_queries: u32, k: u32, d_score: *const f32, d_doc: *const u32,
                            d_n: *const u32, d_out_score: *mut f32, d_out_doc: *mut u32, d_out_shard: *mut u32,
                            d_out_n: *mut u32, stream: *mut c_void) -> c_int;
@@ -308,6 +313,14 @@ extern "C" {
                                   body_include_data: c_int, out: *mut c_char, cap: usize, len: *mut usize) -> c_int;
     pub fn fg_db_doc_facets(db: *mut fg_db, ns: *const c_char, doc: u32, out: *mut c_char, cap: usize,
                             len: *mut usize) -> c_int;
+    pub fn fg_db_facet_counts(db: *mut fg_db, ns: *const c_char, query: *const c_char,
+                              filters: *const *const c_char, n_filters: u32, root_path: *const c_char,
+                              out_paths: *mut c_char, cap: usize, len: *mut usize, out_counts: *mut u64,
+                              count_cap: u32, n_out: *mut u32, total: *mut u64) -> c_int;
+    pub fn fg_db_facet_tree(db: *mut fg_db, ns: *const c_char, max_depth: c_int, out_paths: *mut c_char, cap: usize,
+                            len: *mut usize, out_counts: *mut u64, count_cap: u32, n_out: *mut u32) -> c_int;
+    pub fn fg_db_facets_json(db: *mut fg_db, ns: *const c_char, out: *mut c_char, cap: usize, len: *mut usize)
+                             -> c_int;
     pub fn fg_analyze(text: *const c_char, out: *mut c_char, cap: usize, len: *mut usize) -> c_int;
     pub fn fg_parse_query(query: *const c_char, mode: *mut c_int, out: *mut c_char, cap: usize, len: *mut usize)
                           -> c_int;
