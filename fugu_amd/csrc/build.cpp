@@ -745,6 +745,7 @@ void host_bookkeeping(fg_index& ix, HostPostings& hp, StructTables& st, const Ra
   ix.n_rank = (uint32_t)(rk.plain.size() + rk.sparse.size());
   ix.n_srank_words = rk.sparse.empty() ? 0 : 1 + rk.n_swords;
   ix.tmeta = std::move(st.tmeta);
+  ix.dir_off = std::move(st.dir_off);
   ix.d.rank = rk.d_rank;
   ix.d.srank = rk.d_srank;
   ix.d.srank_w = rk.d_srank ? rk.d_srank + (uint64_t)rk.sblocks * rk.sparse.size() : nullptr;

@@ -398,6 +398,7 @@ struct IndexStructure : ChunkTables {
   SharedVec<uint32_t> first_doc, last_doc;
   std::shared_ptr<const std::vector<uint32_t>> h_doc;  // optional host copy for fg_bytes_model(_gpu)
   SharedVec<uint32_t> tmeta;  // host copy of DevIndex::tmeta (probe kind of each term)
+  SharedVec<uint32_t> dir_off;  // host copy of DevIndex::dir_off (the plans' probe descriptors)
   uint64_t tot_local[2] = {0, 0};
   // facet field (FG_FIELD_FACET)
   uint32_t n_fterms = 0;

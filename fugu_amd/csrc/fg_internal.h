@@ -1,7 +1,9 @@
 // Internal layout shared by the host side (fugu.cpp) and the gfx950 kernels
 // (kernels.hip).  See DESIGN.md §HBM layout.
 #pragma once
+#include <algorithm>
 #include <cstdint>
+#include <initializer_list>
 
 #include <hip/hip_runtime.h>
 
@@ -314,6 +316,112 @@ __host__ __device__ inline float field_score(uint32_t tf, uint32_t fn, float w, 
   return w * (f / (f + cache[fn]));
 }
 
+// Probe descriptors (DevPlan::q_probe): everything k_conj needs to read one
+// clause's lists, as eight words per (query slot, clause position) that the
+// planner fills and a probe stage loads with ONE scalar load -- where the kernel
+// used to chase terms[i] -> tmeta[t] / off[t] / dir_off[t] through two dependent
+// memory round trips in front of every probe (probe descriptors).
+// Three byte ranges, each a 48-bit device address (low word + a 16-bit high
+// part) and, for the two the kernel reads through buffer resources, a size:
+//   structure  entry i >= 1: the probed term's plain rank words, its sparse
+//              block entries (then srank_index into DevIndex::srank_w) or its
+//              bucket directory; entry 0 (the lead list): its doc ids;
+//   scores     the term's build-time scores psc + off[t], or (a query-time plan,
+//              DevPlan::feat & 4) its tfn payloads;
+//   aux        a directory term's doc ids doc + off[t] (no size: read through
+//              plain loads inside the directory's buckets).
+// A load through a range's buffer resource at a byte offset past its size moves
+// no bytes and returns 0, so a lane that is not live passes kPdDead* and needs
+// no branch.  A range of more than kPdMaxBytes cannot be addressed that way:
+// kPdWide then tells the kernel to read that clause's ranges with plain
+// predicated loads from the same base addresses.
+struct ProbeDesc {
+  uint32_t base_lo;   // structure: address bits 0-31
+  uint32_t bytes;     //            size in bytes
+  uint32_t sc_lo;     // scores / payloads: address bits 0-31
+  uint32_t sc_bytes;  //            size in bytes
+  uint32_t aux_lo;    // a directory term's doc ids: address bits 0-31
+  uint32_t hi;        // address bits 32-47: structure | scores << 16
+  uint32_t kind;      // bits 0-5 shift (structure index = doc >> shift: 5 plain rank words, 10 sparse
+                      // block entries, B_t directory), 6-11 S_t (directory search steps), kPd* flags,
+                      // 16-31 aux address bits 32-47
+  uint32_t ub;        // f32 bits of q_ub[i + 1], the MaxScore bound applied after list i (0.0 past the last)
+};
+static_assert(sizeof(ProbeDesc) == 32, "one s_load_dwordx8");
+constexpr uint32_t kPdDir = 1u << 12;     // a bucket directory (else rank words)
+constexpr uint32_t kPdWide = 1u << 13;    // a range does not fit a buffer resource: plain loads
+constexpr uint32_t kPdSparse = 1u << 14;  // sparse rank words: the structure holds block entries
+constexpr uint32_t kPdMaxBytes = 0x80000000u;  // largest range read through a buffer resource
+// offsets of a lane that is not live: past every range, aligned to the load, and no
+// dword of the load wraps around 2^32
+constexpr uint32_t kPdDead8 = 0xFFFFFFF8u, kPdDead4 = 0xFFFFFFFCu, kPdDead2 = 0xFFFFFFFEu;
+__host__ __device__ inline uint32_t pd_shift(uint32_t kind) { return kind & 0x3Fu; }
+__host__ __device__ inline uint32_t pd_steps(uint32_t kind) { return (kind >> 6) & 0x3Fu; }
+__host__ __device__ inline uint64_t pd_base(const ProbeDesc& p) { return ((uint64_t)(p.hi & 0xFFFFu) << 32) | p.base_lo; }
+__host__ __device__ inline uint64_t pd_scores(const ProbeDesc& p) { return ((uint64_t)(p.hi >> 16) << 32) | p.sc_lo; }
+__host__ __device__ inline uint64_t pd_aux(const ProbeDesc& p) { return ((uint64_t)(p.kind >> 16) << 32) | p.aux_lo; }
+
+// What the planner knows of a term on the host (fg_index: off, tmeta, dir_off)
+struct ProbeTerm {
+  uint64_t off, end;  // its postings [off, end)
+  uint32_t meta;      // tmeta
+  uint32_t dir_off;   // first directory entry
+};
+
+// Do the arrays the descriptors point into lie where 48 bits address them?
+// (every array is < 2^47 bytes, so its base below 2^47 covers its end)
+inline bool probe_addr_ok(const DevIndex& ix) {
+  for (const void* p : {(const void*)ix.doc, (const void*)ix.psc, (const void*)ix.tfn, (const void*)ix.dir,
+                        (const void*)ix.rank, (const void*)ix.srank})
+    if ((uint64_t)(uintptr_t)p >> 47) return false;
+  return true;
+}
+
+// The descriptor of term t for a plan over snapshot view ix (device addresses;
+// nothing is dereferenced): the lead list's (entry 0) or a probed list's, with
+// the build-time scores or (qt) the payloads, ub = q_ub[i + 1].
+inline ProbeDesc probe_desc(const DevIndex& ix, const ProbeTerm& t, bool lead, bool qt, float ub) {
+  const uint64_t df = t.end - t.off;
+  uint64_t base, bytes, aux = 0;
+  uint32_t kind;
+  const uint32_t slot = meta_slot(t.meta);
+  if (lead) {
+    base = (uint64_t)(uintptr_t)(ix.doc + t.off);
+    bytes = df * 4;
+    kind = 0;
+  } else if (slot && slot <= ix.n_prank) {
+    base = (uint64_t)(uintptr_t)(ix.rank + (uint64_t)(slot - 1) * ix.rank_words);
+    bytes = (uint64_t)ix.rank_words * 8;
+    kind = 5u;
+  } else if (slot) {
+    base = (uint64_t)(uintptr_t)(ix.srank + (uint64_t)(slot - 1 - ix.n_prank) * ix.srank_blocks);
+    bytes = (uint64_t)ix.srank_blocks * 8;
+    kind = 10u | kPdSparse;
+  } else {
+    const uint32_t B = t.meta & 0xFFu, S = (t.meta >> 8) & 0xFFu;
+    base = (uint64_t)(uintptr_t)(ix.dir + t.dir_off);
+    bytes = ((((uint64_t)(ix.n_docs ? ix.n_docs - 1 : 0)) >> B) + 2) * 4;  // one entry per bucket and the closing one
+    aux = (uint64_t)(uintptr_t)(ix.doc + t.off);
+    kind = (B & 0x3Fu) | ((S & 0x3Fu) << 6) | kPdDir;
+  }
+  const uint64_t sc = qt ? (uint64_t)(uintptr_t)(ix.tfn + t.off) : (uint64_t)(uintptr_t)(ix.psc + t.off);
+  const uint64_t sc_bytes = df * (qt ? 2 : 4);
+  // (addresses are packed in 48 bits: the planner refuses a snapshot whose arrays lie higher, probe_addr_ok)
+  if (bytes > kPdMaxBytes || sc_bytes > kPdMaxBytes) kind |= kPdWide;
+  ProbeDesc p;
+  p.base_lo = (uint32_t)base;
+  p.bytes = (uint32_t)std::min<uint64_t>(bytes, 0xFFFFFFFFull);
+  p.sc_lo = (uint32_t)sc;
+  p.sc_bytes = (uint32_t)std::min<uint64_t>(sc_bytes, 0xFFFFFFFFull);
+  p.aux_lo = (uint32_t)aux;
+  p.hi = (uint32_t)((base >> 32) & 0xFFFFu) | (uint32_t)((sc >> 32) & 0xFFFFu) << 16;
+  p.kind = kind | (uint32_t)((aux >> 32) & 0xFFFFu) << 16;
+  union { float f; uint32_t u; } c;
+  c.f = ub;
+  p.ub = c.u;
+  return p;
+}
+
 // Facet filters of a planned batch (DevPlan).  Every distinct clause list
 // (filter) gets a doc-indexed mask in HBM built by k_fmask from the facet
 // postings: 2^shift bits per doc (shift 0..3, >= the filter's clause count),
@@ -362,6 +470,9 @@ struct DevPlan {
   const uint64_t* q_thr0;       // [nq] starting threshold key (k_disj: per-term top-K bound), 0 = none
   const float* q_ub;            // [nq * kMaxTerms] k_conj MaxScore bounds: q_ub[i] = sum over the query's
                                 //     terms j >= i (intersection order) of their scaled tmaxs, i >= 1
+  const ProbeDesc* q_probe;     // [nq * kMaxTerms] k_conj's probe descriptors, on the slot's own snapshot: entry 0
+                                //     the lead list's, entry i the i-th probed list's (q_terms order) with
+                                //     q_ub[i + 1]; the first qm_terms entries of a k_conj slot are filled
   const float* q_wt;            // [nq * kMaxTerms] each clause's BM25 weight, text field (query time)
   const float* q_wn;            // [nq * kMaxTerms] ... and name field
   const float* q_rup;           // [nq * kMaxTerms] factor on the clause's build-time bounds (tmax, bmax,

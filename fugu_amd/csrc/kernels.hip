@@ -64,6 +64,41 @@ __device__ inline DevIndex seg_index(const DevPlan& pl, uint32_t s) {
 }
 __device__ inline uint32_t wave_id() { return threadIdx.x >> 6; }
 
+// A probe descriptor (DevPlan::q_probe) read the same way: one s_load_dwordx8
+// into SGPRs, no VMEM round trip.  p must be workgroup-uniform.
+typedef const __attribute__((address_space(4))) ProbeDesc ConstProbeDesc;
+__device__ inline ProbeDesc probe_load(const ProbeDesc* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  // (through the address as an integer: a pointer cast is folded back to a global
+  // load, which this kernel -- it writes global memory -- issues as VMEM + readfirstlane)
+  return *(ConstProbeDesc*)(uintptr_t)p;
+#else
+  return *p;
+#endif
+}
+// The buffer resource of a descriptor's range, from scalar words only (a
+// resource the compiler cannot prove uniform gets a readfirstlane loop around
+// every load).  0x00020000: raw 32-bit data, offsets checked against `bytes`:
+// a load at or past it moves no bytes and returns 0.
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef __amdgpu_buffer_rsrc_t BufRsrc;
+__device__ inline BufRsrc pd_rsrc(uint64_t base, uint32_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)base, 0, (int)bytes, 0x00020000);
+}
+__device__ inline uint64_t buf_u64(BufRsrc r, uint32_t off) {
+  const auto v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, 0);
+  return (uint64_t)v[0] | ((uint64_t)v[1] << 32);
+}
+__device__ inline uint32_t buf_u32(BufRsrc r, uint32_t off) { return __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0); }
+__device__ inline uint32_t buf_u16(BufRsrc r, uint32_t off) { return __builtin_amdgcn_raw_buffer_load_b16(r, (int)off, 0, 0); }
+#else  // the host pass only parses device code
+typedef int BufRsrc;
+__device__ inline BufRsrc pd_rsrc(uint64_t, uint32_t) { return 0; }
+__device__ inline uint64_t buf_u64(BufRsrc, uint32_t) { return 0; }
+__device__ inline uint32_t buf_u32(BufRsrc, uint32_t) { return 0; }
+__device__ inline uint32_t buf_u16(BufRsrc, uint32_t) { return 0; }
+#endif
+
 // Upper bounds are compared after inflating by 2^-17 relative: a bound sums at
 // most 16 clauses plus the facet maximum (17 non-negative addends), whose f32
 // summation-order error is below 2 * 17 * 2^-24 < 2^-18 relative, so
@@ -462,58 +497,90 @@ __device__ uint32_t flush_candidates(const DevPlan& pl, uint32_t q, const uint64
   return total;
 }
 
-// Term ti's score at the doc of each live item (-1: the term is absent from
-// it), through the term's rank words or its bucket directory, then the hits'
-// tf / fieldnorm payloads and their query-time scores (weights wt / wn, caches
-// ct / cn); the N items' loads are in flight together.
+// One item of a kPdWide clause (a range past what a buffer resource addresses:
+// a term of more than 2^29 postings): the score of pd's term at doc d, or -1,
+// through plain loads from the descriptor's base addresses, one item at a time
+// -- the cold path stays out of the gathers' register allocation.
+template <uint32_t kF>
+__device__ inline float probe_wide_one(const DevIndex& ix, const ProbeDesc& pd, uint32_t d, float wt, float wn,
+                                       const float* ct, const float* cn) {
+  const uint32_t sh = pd_shift(pd.kind);
+  uint32_t pos;
+  if (!(pd.kind & kPdDir)) {
+    uint64_t x = ((const uint64_t*)(uintptr_t)pd_base(pd))[d >> sh];
+    if (pd.kind & kPdSparse) x = ix.srank_w[srank_index(x, d)];
+    pos = rank_pos(x, d);
+  } else {
+    const uint32_t* __restrict__ dir = (const uint32_t*)(uintptr_t)pd_base(pd);
+    const uint32_t* __restrict__ di = (const uint32_t*)(uintptr_t)pd_aux(pd);
+    const uint32_t b = d >> sh, hi = dir[b + 1];
+    uint32_t lo = dir[b];
+    for (uint32_t st = pd_steps(pd.kind); st > 0; --st) {
+      const uint32_t half = 1u << (st - 1), idx = lo + half - 1;
+      if (idx < hi && di[idx] < d) lo += half;
+    }
+    pos = lo < hi && di[lo] == d ? lo : kInvalid;
+  }
+  if (pos == kInvalid) return -1.0f;
+  if constexpr (!(kF & kFQt)) return ((const float*)(uintptr_t)pd_scores(pd))[pos];
+  const uint16_t* __restrict__ pay = (const uint16_t*)(uintptr_t)pd_scores(pd);
+  const uint64_t p = (uint64_t)(pay - ix.tfn) + pos;  // the posting
+  uint32_t v = pay[pos];
+  if ((kF & kFName) && ix.tfn_name) v |= (uint32_t)ix.tfn_name[p] << 16;
+  if (tfn_escaped<kF>(v)) return tfn_score(ix, p, v, wt, wn, ct, cn);
+  return tfn_score_fast<kF>(v, wt, wn, ct, cn);
+}
+
+// The score at the doc of each live item of the clause that descriptor pd
+// describes (-1: its term is absent from the doc), through the term's rank words
+// or its bucket directory, then the hits' build-time scores -- or their tf /
+// fieldnorm payloads and query-time scores (weights wt / wn, caches ct / cn);
+// the N items' loads are in flight together.  Everything comes from pd's scalar
+// words; the gathers go through its ranges' buffer resources at per-lane byte
+// offsets (a lane that is not live: kPdDead*, no bytes moved, no branch); a
+// kPdWide clause goes item by item through probe_wide_one.  term_p: the clause's
+// term id (DevPlan::q_terms), read by the escaped-tf fix-up alone.
 template <uint32_t N, uint32_t kF>
-__device__ inline void probe_list(const DevIndex& ix, uint32_t ti, const uint32_t (&doc)[N], uint32_t live,
-                                  float wt, float wn, const float* ct, const float* cn, float (&sc)[N]) {
-  const uint32_t meta = ix.tmeta[ti];
-  const uint32_t dslot = meta_slot(meta);
-  const uint64_t bi = ix.off[ti];
+__device__ inline void probe_list(const DevIndex& ix, const ProbeDesc& pd, const uint32_t* term_p,
+                                  const uint32_t (&doc)[N], uint32_t live, float wt, float wn, const float* ct,
+                                  const float* cn, float (&sc)[N]) {
+  if (__builtin_expect((pd.kind & kPdWide) != 0, 0)) {
+#pragma unroll
+    for (uint32_t j = 0; j < N; ++j) sc[j] = (live & (1u << j)) ? probe_wide_one<kF>(ix, pd, doc[j], wt, wn, ct, cn) : -1.0f;
+    return;
+  }
+  const uint32_t sh = pd_shift(pd.kind);
+  const uint64_t sbase = pd_scores(pd);
+  const BufRsrc rs = pd_rsrc(sbase, pd.sc_bytes);
+  const BufRsrc rr = pd_rsrc(pd_base(pd), pd.bytes);
   uint32_t pos[N];
-  if (dslot) {
+  if (!(pd.kind & kPdDir)) {
     // rank words: presence + rank in one 8-B load per item (all items'
     // loads in flight together; sparse ones: the block entries, then the
     // words), then the score (or payload) of the hits
-    uint32_t sh;
-    const uint64_t* __restrict__ rw = rank_base(ix, dslot, sh);
+    // (never past kPdMaxBytes: 8 B per 32 docs of < 2^32)
     uint64_t x[N];
 #pragma unroll
-    for (uint32_t j = 0; j < N; ++j) x[j] = (live & (1u << j)) ? rw[doc[j] >> sh] : 0ull;
-    if (sh != 5u) {
+    for (uint32_t j = 0; j < N; ++j) x[j] = buf_u64(rr, (live & (1u << j)) ? (doc[j] >> sh) << 3 : kPdDead8);
+    if (pd.kind & kPdSparse) {
 #pragma unroll
       for (uint32_t j = 0; j < N; ++j) {
         x[j] = ix.srank_w[srank_index(x[j], doc[j])];
       }
     }
-    if constexpr (!(kF & kFQt)) {  // the build-time scores: one load per hit
-      const float* __restrict__ ps = ix.psc + bi;
-#pragma unroll
-      for (uint32_t j = 0; j < N; ++j) {
-        const uint32_t p = rank_pos(x[j], doc[j]);
-        sc[j] = p != kInvalid ? ps[p] : -1.0f;
-      }
-      return;
-    }
 #pragma unroll
     for (uint32_t j = 0; j < N; ++j) pos[j] = rank_pos(x[j], doc[j]);
   } else {
-    const uint32_t B = meta & 0xFFu, S = (meta >> 8) & 0xFFu;
-    const uint32_t* __restrict__ di = ix.doc + bi;
-    const uint32_t* __restrict__ dir = ix.dir + ix.dir_off[ti];
-    // bucket of each live item, then a branchless power-of-two search in it
+    const uint32_t S = pd_steps(pd.kind);
+    const uint32_t* __restrict__ di = (const uint32_t*)(uintptr_t)pd_aux(pd);
+    // bucket of each live item (its two directory entries: one 8-B load), then a
+    // branchless power-of-two search in it
     uint32_t hi[N];
 #pragma unroll
     for (uint32_t j = 0; j < N; ++j) {
-      pos[j] = 0;
-      hi[j] = 0;
-      if (live & (1u << j)) {
-        const uint32_t b = doc[j] >> B;
-        pos[j] = dir[b];
-        hi[j] = dir[b + 1];
-      }
+      const uint64_t e = buf_u64(rr, (live & (1u << j)) ? (doc[j] >> sh) << 2 : kPdDead8);
+      pos[j] = (uint32_t)e;
+      hi[j] = (uint32_t)(e >> 32);
     }
     for (uint32_t st = S; st > 0; --st) {
       const uint32_t half = 1u << (st - 1);
@@ -523,23 +590,30 @@ __device__ inline void probe_list(const DevIndex& ix, uint32_t ti, const uint32_
         if ((live & (1u << j)) && idx < hi[j] && di[idx] < doc[j]) pos[j] += half;
       }
     }
-    if constexpr (!(kF & kFQt)) {
-#pragma unroll
-      for (uint32_t j = 0; j < N; ++j) {
-        sc[j] = -1.0f;
-        if ((live & (1u << j)) && pos[j] < hi[j] && di[pos[j]] == doc[j]) sc[j] = ix.psc[bi + pos[j]];
-      }
-      return;
-    }
 #pragma unroll
     for (uint32_t j = 0; j < N; ++j)
       if (!((live & (1u << j)) && pos[j] < hi[j] && di[pos[j]] == doc[j])) pos[j] = kInvalid;
   }
-  // the hits' payloads (a posting's is never 0: tf >= 1 in some field), then their
-  // scores; an escaped tf finds its position again (posting_pos)
+  if constexpr (!(kF & kFQt)) {  // the build-time scores: one load per hit (kInvalid << 2 is kPdDead4)
+#pragma unroll
+    for (uint32_t j = 0; j < N; ++j) {
+      const float s = __uint_as_float(buf_u32(rs, pos[j] << 2));
+      sc[j] = pos[j] != kInvalid ? s : -1.0f;
+    }
+    return;
+  }
+  // the hits' payloads (a posting's is never 0: tf >= 1 in some field; kInvalid << 1
+  // is kPdDead2), then their scores; an escaped tf finds its position again (posting_pos)
+  const uint16_t* __restrict__ pay = (const uint16_t*)(uintptr_t)sbase;
   uint32_t v[N];
 #pragma unroll
-  for (uint32_t j = 0; j < N; ++j) v[j] = pos[j] != kInvalid ? tfn_load<kF>(ix, bi + pos[j]) : 0u;
+  for (uint32_t j = 0; j < N; ++j) v[j] = buf_u16(rs, pos[j] << 1);
+  if ((kF & kFName) && ix.tfn_name) {
+    const uint16_t* __restrict__ pn = ix.tfn_name + (pay - ix.tfn);  // the term's name payloads
+#pragma unroll
+    for (uint32_t j = 0; j < N; ++j)
+      if (pos[j] != kInvalid) v[j] |= (uint32_t)pn[pos[j]] << 16;
+  }
   uint32_t esc = 0;
 #pragma unroll
   for (uint32_t j = 0; j < N; ++j) {
@@ -547,6 +621,8 @@ __device__ inline void probe_list(const DevIndex& ix, uint32_t ti, const uint32_
     esc |= (tfn_escaped<kF>(v[j]) ? 1u : 0u) << j;
   }
   if constexpr ((kF & kFEsc) != 0) if (__builtin_expect(esc != 0, 0)) {
+    const uint32_t ti = *term_p;
+    const uint64_t bi = ix.off[ti];
 #pragma unroll
     for (uint32_t j = 0; j < N; ++j)
       if ((esc >> j) & 1u) {
@@ -561,8 +637,8 @@ __device__ inline void probe_list(const DevIndex& ix, uint32_t ti, const uint32_
 // the survivors' keys.  The sums are the ones the inline path forms:
 // (left + right) + (0.0 + s_2 + ...).  Unfiltered queries only (no facet term).
 template <uint32_t kF>
-__device__ void flush_deferred(const DevIndex& ix, ConjShared& sh, const uint32_t* terms, const float* qwt,
-                               const float* qwn, uint32_t m, const float* qub, uint64_t thr, uint32_t nd) {
+__device__ void flush_deferred(const DevIndex& ix, ConjShared& sh, const ProbeDesc* probes, const uint32_t* terms,
+                               const float* qwt, const float* qwn, uint32_t m, uint64_t thr, uint32_t nd) {
   const uint32_t tid = threadIdx.x;
   uint32_t doc[kDeferR], live = 0;
   float s01[kDeferR], acc[kDeferR];
@@ -578,14 +654,15 @@ __device__ void flush_deferred(const DevIndex& ix, ConjShared& sh, const uint32_
   for (uint32_t i = 2; i < m; ++i) {
     if (!__any(live != 0)) break;
     float sc[kDeferR];
-    probe_list<kDeferR, kF>(ix, terms[i], doc, live, qwt[i], qwn[i], sh.cache, sh.cache + 256, sc);
+    const ProbeDesc pd = probe_load(probes + i);
+    probe_list<kDeferR, kF>(ix, pd, terms + i, doc, live, qwt[i], qwn[i], sh.cache, sh.cache + 256, sc);
 #pragma unroll
     for (uint32_t r = 0; r < kDeferR; ++r) {
       if (sc[r] < 0.0f) live &= ~(1u << r);
       else acc[r] += sc[r];
     }
     if (thr != 0 && i + 1 < m) {
-      const float ub = qub[i + 1];
+      const float ub = __uint_as_float(pd.ub);
 #pragma unroll
       for (uint32_t r = 0; r < kDeferR; ++r)
         if ((live & (1u << r)) && make_key(inflate_bound(s01[r] + acc[r] + ub), doc[r]) < thr) live &= ~(1u << r);
@@ -617,6 +694,21 @@ __device__ void flush_deferred(const DevIndex& ix, ConjShared& sh, const uint32_
 // single item's k-th key (items reading the bins themselves cost more than
 // they pruned: profiles/r03/ab/ab_conj_hist.log).
 // kMulti: a multi-snapshot plan (DevPlan::segs): the item's snapshot from its query slot
+// Probe descriptors (DevPlan::q_probe, fg_internal.h ProbeDesc): what a stage
+// needs of its clause -- where its rank words / block entries / directory and
+// its scores (or payloads) lie, how large they are, the probe kind, the
+// MaxScore bound applied after it -- is filled by the planner per (slot,
+// clause) and arrives with scalar loads; the kernel no longer reads terms[i],
+// then tmeta[t] / off[t] / dir_off[t] (two dependent VMEM round trips, each
+// draining every load in flight, in front of every probe of every chunk).  The
+// gathers go through buffer resources built from those scalar words: a lane
+// that is not live passes an offset past the range, which moves no bytes, so the
+// 8 rank-word loads and the 8 score loads of a stage issue back to back with no
+// exec bracket between them, on 32-bit offsets.  The lead list's 8 + 8 loads per
+// chunk go through resources over the chunk's own window, so the short last
+// chunk falls out of the range check.  Same bytes at the same addresses, same
+// f32 order: identical hits.  Headline k_conj 0.953 -> 0.909 ms
+// (profiles/probe_desc/ab/conj_probe_desc.log); DESIGN.md §3.
 template <bool kSingle, bool kMulti, uint32_t kF>
 __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPlan pl) {
   __shared__ ConjShared sh;
@@ -643,13 +735,13 @@ __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPl
   const uint32_t m = qm_terms(qmv), nm = qm_must(qmv), nmx = nm + qm_not(qmv);
   const bool has_opt = m > nmx;
   const uint32_t* terms = pl.q_terms + (size_t)q * kMaxTerms;
-  const float* qub = pl.q_ub + (size_t)q * kMaxTerms;
+  // the clauses' probe descriptors (DevPlan::q_probe): entry 0 the lead list's,
+  // entry i the i-th probed list's with the MaxScore bound applied after it
+  const ProbeDesc* probes = pl.q_probe + (size_t)q * kMaxTerms;
   // the clauses' query-time BM25 weights (uniform: scalar loads)
   const float* qwt = pl.q_wt + (size_t)q * kMaxTerms;
   const float* qwn = pl.q_wn + (size_t)q * kMaxTerms;
   const uint32_t K = pl.k;
-  const uint32_t t0 = terms[0];
-  const uint64_t lead_base = ix.off[t0];
   const uint32_t lead_df = pl.q_lead_df[q];
   unsigned long long* gthr = reinterpret_cast<unsigned long long*>(&pl.thresh[ql]);
   // facet filter (uniform per work item): Bool[Must(text), Must(facet union)]
@@ -693,7 +785,7 @@ __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPl
   // maximum) cannot reach the threshold is not loaded.  thr_k is the threshold
   // as every thread last saw it (uniform), so the skip is uniform too.  The
   // build-time chunk maxima scale by the lead's bound factor (DevPlan::q_rup).
-  const float* __restrict__ cmax = ix.cmax + ix.coff[t0];
+  const float* __restrict__ cmax = ix.cmax + (kSingle ? ix.coff[terms[0]] : 0u);
   const float rup0 = pl.q_rup[(size_t)q * kMaxTerms];
   uint64_t thr_k = thr0;
   // pure conjunctions (the multi-snapshot instantiation too: without deferred
@@ -706,23 +798,44 @@ __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPl
     uint64_t tp0 = FG_NOW(), tp1 = tp0;
     (void)tp0; (void)tp1;
     if (!kSingle || make_key(inflate_bound(cmax[c] * rup0 + fmax), 0u) >= thr_k) {
-    const uint64_t base0 = lead_base + (uint64_t)c * kChunk;
     const uint32_t cnt = min(kChunk, lead_df - c * kChunk);
+    // the chunk's doc ids and scores (or payloads) through two resources over the
+    // chunk's own window of the lead descriptor's ranges (a list of any length:
+    // kPdWide does not matter here): a lane past the list's end (the short last
+    // chunk) is past the window, moves no bytes and reads 0
+    const ProbeDesc ld = probe_load(probes);
+    constexpr uint32_t kScB = (kF & kFQt) ? 2u : 4u;  // bytes per score / payload
+    const BufRsrc lrd = pd_rsrc(pd_base(ld) + (uint64_t)c * (kChunk * 4u), cnt * 4u);
+    const BufRsrc lrs = pd_rsrc(pd_scores(ld) + (uint64_t)c * (kChunk * kScB), cnt * kScB);
+    // (the name payloads and the escaped-tf fix-up address the snapshot's arrays by posting)
+    const uint64_t base0 =
+        (kF & (kFName | kFEsc)) ? (uint64_t)((const uint16_t*)(uintptr_t)pd_scores(ld) - ix.tfn) + (uint64_t)c * kChunk : 0ull;
     // lead candidates: item j of lane l = wv*512 + j*64 + l (coalesced per j)
     uint32_t doc[kItems];
     float s0[kItems];
     uint32_t live = 0;
     {
       uint32_t tv[kItems];
+      // the lane's first item, formed again in every chunk: hoisted out of the chunk
+      // loop, the 8 indices and their 8 byte offsets stay live through all of it and
+      // spill; from one register the offsets fold into the loads' immediates
+      uint32_t t = tid;
+#if defined(__HIP_DEVICE_COMPILE__)
+      asm volatile("" : "+v"(t));
+#endif
+      const uint32_t i0 = (t >> 6) * kWaveSpan + (t & 63u);
 #pragma unroll
       for (uint32_t j = 0; j < kItems; ++j) {
-        const uint32_t idx = wv * kWaveSpan + j * 64 + lane;
+        const uint32_t idx = i0 + j * 64;
         const bool in = idx < cnt;
-        // predicated loads: tools/ab_variants.py measured clamped unconditional
-        // loads (every lane issuing) slower here, 1.57 -> 2.05 ms
-        doc[j] = in ? ix.doc[base0 + idx] : kInvalid;
-        if constexpr (kF & kFQt) tv[j] = in ? tfn_load<kF>(ix, base0 + idx) : 0u;
-        else s0[j] = in ? ix.psc[base0 + idx] : 0.0f;
+        // predicated in effect by the range check: tools/ab_variants.py measured
+        // clamped unconditional loads (every lane moving bytes) slower here, 1.57 -> 2.05 ms
+        const uint32_t d = buf_u32(lrd, idx << 2);
+        doc[j] = in ? d : kInvalid;
+        if constexpr (kF & kFQt) tv[j] = buf_u16(lrs, idx << 1);
+        else s0[j] = __uint_as_float(buf_u32(lrs, idx << 2));
+        if constexpr ((kF & kFName) != 0)
+          if (in && ix.tfn_name) tv[j] |= (uint32_t)ix.tfn_name[base0 + idx] << 16;
         live |= (in ? 1u : 0u) << j;
       }
       if (tid == 0 && pend > sh.thr) sh.thr = pend;
@@ -759,7 +872,7 @@ __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPl
     FG_COUNT(0, live);
     if (!prune) FG_COUNT(7, live);  // candidates of chunks that start with no threshold
     if (prune) {
-      const float ub = qub[1] + fmax;
+      const float ub = __uint_as_float(ld.ub) + fmax;
 #pragma unroll
       for (uint32_t j = 0; j < kItems; ++j)
         if ((live & (1u << j)) && make_key(inflate_bound(s0[j] + ub), doc[j]) < thr) live &= ~(1u << j);
@@ -807,9 +920,9 @@ __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPl
           acc_o[j] = 0.0f;
         }
       }
-      const uint32_t ti = terms[i];
+      const ProbeDesc pd = probe_load(probes + i);
       float sc[kItems];
-      probe_list<kItems, kF>(ix, ti, doc, live, qwt[i], qwn[i], sh.cache, sh.cache + 256, sc);
+      probe_list<kItems, kF>(ix, pd, terms + i, doc, live, qwt[i], qwn[i], sh.cache, sh.cache + 256, sc);
       // Intersection::score = left + right + (0.0 + others...)
       if (i < nm) {
 #pragma unroll
@@ -827,7 +940,7 @@ __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPl
           if (sc[j] >= 0.0f) acc_o[j] += sc[j];  // RequiredOptionalScorer's optional union
       }
       if (prune && i + 1 < m) {
-        const float ub = qub[i + 1] + fmax;
+        const float ub = __uint_as_float(pd.ub) + fmax;
 #pragma unroll
         for (uint32_t j = 0; j < kItems; ++j)
           if ((live & (1u << j)) && make_key(inflate_bound(s0[j] + acc_o[j] + ub), doc[j]) < thr)
@@ -894,7 +1007,7 @@ __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPl
           local_T = truncate_topk(sh, n, K);
           if (local_T > thr_k) thr_k = local_T;
         }
-        flush_deferred<kF>(ix, sh, terms, qwt, qwn, m, qub, thr_k, nd);
+        flush_deferred<kF>(ix, sh, probes, terms, qwt, qwn, m, thr_k, nd);
         __syncthreads();
         n = sh.n_buf;
         if (tid == 0) sh.n_dq = 0;

@@ -45,6 +45,7 @@ struct PlanTables {
   std::vector<uint32_t> q_pterm, q_ppos;  // phrase queries' (term, offset) rows; empty without phrase_len
   std::vector<uint64_t> thr0;
   std::vector<float> q_ub, q_wt, q_wn, q_rup;
+  std::vector<fg::ProbeDesc> q_probe;  // k_conj slots' probe descriptors (rows as above)
   // facet filters (fg_internal.h DevFilters) and the chunks of their postings
   uint32_t nf = 0;
   std::vector<uint32_t> f_shift, f_seg;  // f_seg: the filter's snapshot (joined tables only)
@@ -59,7 +60,7 @@ struct PlanTables {
   void clear() {
     auto all = [](auto&... v) { (v.clear(), ...); };
     all(q_m, q_terms, lead, q_filter, ngroup, q_hlo, q_hhi, q_hsh, thr0, q_ub, q_wt, q_wn, q_rup, f_shift, f_seg, f_woff,
-        f_tab, f_max, ch_f, ch_c, ch_t, ch_s, citems, ditems, scan, phrase, items, q_pterm, q_ppos);
+        f_tab, f_max, ch_f, ch_c, ch_t, ch_s, citems, ditems, scan, phrase, items, q_pterm, q_ppos, q_probe);
     nf = 0;
   }
 };
@@ -147,8 +148,10 @@ int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_
 // all of them, so each snapshot gets its share of the per-query item counts.
 // nq_size: the batch size the item counts are sized for (q may be a slice of
 // that batch: plan_pieces plans a snapshot's queries in pieces)
+// qtime: the plan forms its scores at query time (some snapshot's statistics
+// changed since its build: DevPlan::feat), so the descriptors point at payloads
 int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t n_segs, PlanTables& h,
-              uint32_t nq_size) {
+              uint32_t nq_size, bool qtime) {
   if (!ix || !q || (q->n_queries && !q->q_off)) return fail(FG_EINVAL, "bad arguments");
   if (q->n_queries && q->q_off[q->n_queries] > q->q_off[0] && !q->terms) return fail(FG_EINVAL, "q_off without terms");
   if (q->f_off && q->n_queries && q->f_off[q->n_queries] > q->f_off[0] && !q->f_terms)
@@ -166,6 +169,7 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
   h.thr0.assign(nq, 0);
   for (auto* v : {&h.q_ub, &h.q_wt, &h.q_wn}) v->assign(nqt, 0.0f);
   h.q_rup.assign(nqt, 1.0f);
+  h.q_probe.assign(nqt, fg::ProbeDesc{});
   if (q->phrase_len) {
     if (!q->phrase_pos) return fail(FG_EINVAL, "phrase_len without phrase_pos");
     h.q_pterm.assign(nqt, 0);
@@ -407,6 +411,14 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
         if (j < nm || j >= nm + nx) acc += cm[j];
         h.q_ub[(size_t)i * fg::kMaxTerms + j] = acc;
       }
+      // the clauses' probe descriptors: the lead list's, then each probed list's
+      // with the bound applied after it
+      const size_t row = (size_t)i * fg::kMaxTerms;
+      for (uint32_t j = 0; j < mt; ++j) {
+        const uint32_t t = qt[j];
+        const fg::ProbeTerm pt{ix->off[t], ix->off[t + 1], ix->tmeta[t], ix->dir_off[t]};
+        h.q_probe[row + j] = fg::probe_desc(ix->d, pt, j == 0, qtime, j + 1 < mt ? h.q_ub[row + j + 1] : 0.0f);
+      }
     }
     // one list: its K'-th best alive score (the smallest stored K' >= k) bounds
     // the query's k-th best from below, so k_conj starts from that threshold and
@@ -475,13 +487,19 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
   pc.P = par ? std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)fgh::hw_threads(0) / S, nq1 / 128)) : 1u;
   const uint32_t n = pc.count();
   if (hs.size() < n) hs.resize(n);
-  if (S == 1) return plan_host(ixs[0], q, k, S, hs[0], nq1);  // (used in place: nothing to join)
+  bool qt = false;  // fill_view's DevPlan::feat & 4
+  for (uint32_t s = 0; s < S; ++s) {
+    qt |= !ixs[s]->same_stats;
+    if (!fg::probe_addr_ok(ixs[s]->d)) return fail(FG_EUNSUPPORTED, "snapshot %u: device arrays above 2^47", s);
+  }
+  if (S == 1) return plan_host(ixs[0], q, k, S, hs[0], nq1, qt);  // (used in place: nothing to join)
   J.clear();
   const size_t nq = (size_t)S * nq1, nqt = nq * fg::kMaxTerms;
   for (auto* v : {&J.q_m, &J.lead, &J.ngroup}) v->resize(nq);
   J.thr0.resize(nq);
   J.q_terms.resize(nqt);
   for (auto* v : {&J.q_ub, &J.q_wt, &J.q_wn, &J.q_rup}) v->resize(nqt);
+  J.q_probe.resize(nqt);
   if (q->phrase_len)
     for (auto* v : {&J.q_pterm, &J.q_ppos}) v->resize(nqt);
   auto put_slot = [&](uint32_t p) {  // piece p's per-query tables into its slots
@@ -491,6 +509,7 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
     cp(J.q_m, h.q_m, v0); cp(J.lead, h.lead, v0); cp(J.ngroup, h.ngroup, v0); cp(J.thr0, h.thr0, v0);
     cp(J.q_terms, h.q_terms, t0);
     cp(J.q_ub, h.q_ub, t0); cp(J.q_wt, h.q_wt, t0); cp(J.q_wn, h.q_wn, t0); cp(J.q_rup, h.q_rup, t0);
+    cp(J.q_probe, h.q_probe, t0);
     cp(J.q_pterm, h.q_pterm, t0); cp(J.q_ppos, h.q_ppos, t0);  // (empty without phrase_len)
   };
   if (par) {
@@ -502,14 +521,14 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
       qp.n_queries = b - a;
       qp.q_off = q->q_off + a;
       if (q->f_off) qp.f_off = q->f_off + a;
-      if ((rcs[p] = plan_host(ixs[p / pc.P], &qp, k, S, hs[p], nq1))) errs[p] = fg_last_error();
+      if ((rcs[p] = plan_host(ixs[p / pc.P], &qp, k, S, hs[p], nq1, qt))) errs[p] = fg_last_error();
       else put_slot(p);
     });
     for (uint32_t p = 0; p < n; ++p)
       if (rcs[p]) return fail(rcs[p], "snapshot %u: %s", p / pc.P, errs[p].c_str());
   } else {
     for (uint32_t s = 0; s < S; ++s) {
-      if (int rc = plan_host(ixs[s], q, k, S, hs[s], nq1)) {
+      if (int rc = plan_host(ixs[s], q, k, S, hs[s], nq1, qt)) {
         const std::string e = fg_last_error();
         return fail(rc, "snapshot %u: %s", s, e.c_str());
       }
@@ -770,6 +789,7 @@ int stage_and_upload(fg_plan* p, fg_index* const* ixs, PlanTables& t, const Work
   L.in(d.cand_off, w.cand_off.data(), 8ull * (nq + 1));
   L.in(d.q_thr0, t.thr0.data(), 8ull * nq);
   L.in(d.q_ub, t.q_ub.data(), 4 * nqt);
+  L.in(d.q_probe, t.q_probe.data(), sizeof(fg::ProbeDesc) * nqt);
   L.in(d.q_wt, t.q_wt.data(), 4 * nqt);
   L.in(d.q_wn, t.q_wn.data(), 4 * nqt);
   L.in(d.q_rup, t.q_rup.data(), 4 * nqt);
