@@ -172,6 +172,28 @@ int score_postings(const fg_index* ix, fg::ScoreJob& j, float* cmax, float* psc,
   return FG_OK;
 }
 
+// The terms that get a doc-indexed score table (DevIndex::dtab): df >= N /
+// FUGU_DOCTAB_DIV (default kDocTabDiv; 0: none), densest first (ties by term
+// id), at most kDocTabMax and within 1/kDocTabFrac of the snapshot's own
+// posting bytes (12 B each, as the rank budget counts them), so a small shard
+// or namespace pays in proportion.  None for a snapshot of fewer than
+// kDocTabMinDocs docs, or one whose table would not fit a buffer resource.
+std::vector<uint32_t> choose_doctab_terms(const fg_index* ix, uint64_t stride) {
+  std::vector<uint32_t> ts;
+  const uint64_t N = ix->n_docs;
+  uint32_t div = fg::kDocTabDiv;
+  if (const char* e = getenv("FUGU_DOCTAB_DIV"))
+    if (*e) div = (uint32_t)std::max(0l, atol(e));
+  if (!div || N < fg::kDocTabMinDocs || 4 * N > fg::kPdMaxBytes) return ts;
+  auto df = [&](uint32_t t) { return ix->off[t + 1] - ix->off[t]; };
+  for (uint32_t t = 0; t < ix->n_terms; ++t)
+    if (df(t) * div >= N) ts.push_back(t);
+  std::stable_sort(ts.begin(), ts.end(), [&](uint32_t a, uint32_t b) { return df(a) > df(b); });
+  const uint64_t budget = 12ull * ix->n_postings / fg::kDocTabFrac;
+  ts.resize(std::min<uint64_t>({(uint64_t)ts.size(), (uint64_t)fg::kDocTabMax, budget / (4 * stride)}));
+  return ts;
+}
+
 // The bounds of a freshly built structure under its build statistics (which
 // are its current ones): the posting scores (k_score, with the block-max per
 // 2048 postings), bucket / term / tile maxima (k_bucket), sub-tile maxima
@@ -186,13 +208,24 @@ int build_bounds(fg_index* ix, const std::vector<uint32_t>& alive) {
   const Parts::P p_alive = L.add(4ull * alive.size()), p_bmax = L.add(4ull * ix->dir_entries), p_tmaxs = L.add(4ull * V),
                  p_tmax = L.add(4ull * ix->tile_entries), p_ktop = L.add(4ull * V * fg::kNumTopK),
                  p_cmax = L.add(4ull * ix->n_sc), p_tsub = L.add(8ull * ix->tile_entries);
-  const size_t total = L.total;
+  // the score tables last: a block without them is the same block cut short
+  const uint64_t tab_stride = ((uint64_t)ix->n_docs + 31) & ~31ull;
+  std::vector<uint32_t> tabs = choose_doctab_terms(ix, tab_stride);
+  const size_t bounds_total = L.total;
+  const Parts::P p_dtab = L.add(4ull * tab_stride * tabs.size());
+  size_t total = tabs.empty() ? bounds_total : L.total;
   if (!ix->spool) {
     ix->spool = std::make_shared<fgh::ScorePool>();
     ix->spool->dev = ix->dev;
   }
   auto sb = std::make_shared<fgh::ScoreBlock>();
   void* blk = ix->spool->get(total);
+  if (!blk && !tabs.empty()) {  // (a build never fails for want of the tables)
+    (void)hipGetLastError();
+    tabs.clear();
+    total = bounds_total;
+    blk = ix->spool->get(total);
+  }
   if (!blk) return fail(FG_EOOM, "bound tables: hipMalloc(%zu) failed", total);
   sb->p = blk;
   sb->bytes = total;
@@ -211,6 +244,28 @@ int build_bounds(fg_index* ix, const std::vector<uint32_t>& alive) {
   fg::ScoreJob j{};
   AsyncTmp tmp;
   if (int rc = score_postings(ix, j, d_cmax, d_psc, tmp)) return rc;
+  // the densest terms' score tables from those scores (none: no launch)
+  float* d_dtab = tabs.empty() ? nullptr : Parts::at<float>(blk, p_dtab);
+  if (d_dtab) {
+    fg::DocTabJob tj{};
+    tj.doc = ix->d.doc;
+    tj.psc = d_psc;
+    tj.tab = d_dtab;
+    tj.stride = tab_stride;
+    tj.n = (uint32_t)tabs.size();
+    std::vector<uint64_t> map(tabs.size());
+    for (uint32_t i = 0; i < tabs.size(); ++i) {
+      tj.off[i] = ix->off[tabs[i]];
+      tj.df[i] = (uint32_t)(ix->off[tabs[i] + 1] - ix->off[tabs[i]]);
+      map[i] = ((uint64_t)tabs[i] << 32) | i;
+    }
+    HIPCHK(fg::launch_doctab(tj, j.grid_cap, kBuildStream));
+    std::sort(map.begin(), map.end());
+    ix->dtab_map = std::move(map);
+  }
+  ix->dtab_bytes = 4ull * tab_stride * tabs.size();
+  if (g_bt.on)
+    fprintf(stderr, "[fg build] score tables: %zu terms, %.1f MiB\n", tabs.size(), (double)ix->dtab_bytes / (double)(1 << 20));
   j.alive = d_alive;
   j.bmax = d_bmax;
   j.tmaxs = d_tmaxs;
@@ -263,6 +318,8 @@ int build_bounds(fg_index* ix, const std::vector<uint32_t>& alive) {
   ix->d.tmax = reinterpret_cast<const float*>(d_tmax);
   ix->d.tsub = d_tsub;
   ix->d.cmax = d_cmax;
+  ix->d.dtab = d_dtab;
+  ix->d.dtab_stride = (uint32_t)tab_stride;
   ix->d.alive = d_alive;
   ix->device_bytes = ix->struct_bytes + total;
   return FG_OK;

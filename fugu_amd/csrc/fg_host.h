@@ -427,8 +427,25 @@ struct IndexBounds {
   SharedVec<float> wb_text, wb_name;  // the build's BM25 weights
   float cache_b[512];                 // the build's tf caches
   SharedVec<uint32_t> h_alive_b;      // the alive bitset ktop was selected over (empty: every doc)
+  // the doc-indexed score tables (DevIndex::dtab, in sblock): (term << 32) | table slot of each
+  // term that has one, ascending by term (doctab_slot), and their bytes
+  SharedVec<uint64_t> dtab_map;
+  uint64_t dtab_bytes = 0;
   uint64_t device_bytes = 0;
 };
+
+// lead candidates per table line from which a plan probes a score table
+// (fg::probe_uses_table): FUGU_DOCTAB_LEAD, read when a plan is made
+inline uint32_t doctab_lead() {
+  const char* e = getenv("FUGU_DOCTAB_LEAD");
+  return e && *e ? (uint32_t)std::max(0l, atol(e)) : fg::kDocTabLead;
+}
+
+// the score table of local term t: its slot + 1, or 0 (fg::ProbeTerm::tab)
+inline uint32_t doctab_slot(const IndexBounds& b, uint32_t t) {
+  const auto it = std::lower_bound(b.dtab_map.begin(), b.dtab_map.end(), (uint64_t)t << 32);
+  return it != b.dtab_map.end() && (uint32_t)(*it >> 32) == t ? (uint32_t)*it + 1u : 0u;
+}
 }  // namespace fgh
 
 struct fg_index : fgh::IndexStructure, fgh::IndexBounds {

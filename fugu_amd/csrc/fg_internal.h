@@ -47,6 +47,25 @@ constexpr double kRankFactor = FG_RANK_FACTOR;  // ... and within this many time
 // one sparse rank words (DevIndex::srank), unless plain ones cost it less
 constexpr uint32_t kRankPlainDiv = FG_RANK_PLAIN_DIV;
 constexpr uint32_t kMaxDense = 32767;     // slots per kind (tmeta bits 16-30)
+// Doc-indexed score tables (DevIndex::dtab) of the densest terms, beside their
+// rank words: a term in >= 1/kDocTabDiv of the docs (env FUGU_DOCTAB_DIV, 0: no
+// tables), densest first, within 1/kDocTabFrac of the snapshot's posting bytes
+// (12 B each, as the rank budget counts them) and kDocTabMax tables; k_conj
+// probes one when the lead list brings >= kDocTabLead candidates per 32-doc
+// table line (env FUGU_DOCTAB_LEAD, 0: always).  Sweep: DESIGN.md §3,
+// profiles/doc_tables/ab/.
+#ifndef FG_DOCTAB_DIV
+#define FG_DOCTAB_DIV 4   // sweep: AND3 0.904 -> 0.883 ms, AND 1-5 1.021 -> 0.978 ms; 8 and wider lose it again on AND3
+#endif
+#ifndef FG_DOCTAB_LEAD
+#define FG_DOCTAB_LEAD 8  // against the parent build, interleaved: 8 -> -0.0225 ms, 4 -> -0.0107 ms (16 loses again)
+#endif
+constexpr uint32_t kDocTabDiv = FG_DOCTAB_DIV;
+constexpr uint32_t kDocTabLead = FG_DOCTAB_LEAD;
+constexpr uint32_t kDocTabFrac = 8;
+constexpr uint32_t kDocTabMax = 64;       // tables per snapshot (DocTabJob rides in the kernel arguments)
+constexpr uint32_t kDocTabMinDocs = 8192; // a snapshot of fewer docs (a commit's segment: a few lead chunks
+                                          // per query, and its build must stay a short launch chain) gets none
 constexpr uint32_t kRankChunkWords = 2048;  // k_rank: words (65536 docs) per workgroup
 #ifndef FG_DISJ_GPQ
 #define FG_DISJ_GPQ 64
@@ -275,6 +294,10 @@ struct DevIndex {
   const float* cmax;         // [score chunks] largest posting score of each kChunk-posting chunk of a
                              //     list (block-max: k_conj skips a lead chunk that cannot reach the threshold)
   const uint32_t* coff;      // [V] index of each term's first chunk in cmax
+  const float* dtab;         // [n tables * dtab_stride] doc-indexed score tables of the densest terms (build
+                             //     statistics, as psc): entry d of a table = the term's psc value at doc d,
+                             //     -1.0f where the term is absent.  k_conj reads them through its probe
+                             //     descriptors (kPdTab); which term owns which table: fg_index::dtab_map (host)
   const uint32_t* fdoc;      // [PF] facet postings (doc ids, ascending), CSR by facet term
   const uint64_t* foff;      // [VF+1]
   uint64_t n_esc;
@@ -285,6 +308,7 @@ struct DevIndex {
   uint32_t rank_words;       // words per plain rank-kind term: ceil(N / 32)
   uint32_t n_prank;          // plain rank-kind slots
   uint32_t srank_blocks;     // block entries per sparse rank-kind term: ceil(N / 1024)
+  uint32_t dtab_stride;      // floats per score table: N rounded up to a 128-B line
   // Forward index (fg_docs_input::keep_positions; nullptr without): per field the
   // doc's tokens addressed by POSITION, fwd[fwd_off[d] + p] = the VOCABULARY id of
   // the token at analyzer position p of doc d, kFwdNone where the analyzer dropped
@@ -324,8 +348,10 @@ __host__ __device__ inline float field_score(uint32_t tf, uint32_t fn, float w, 
 // Three byte ranges, each a 48-bit device address (low word + a 16-bit high
 // part) and, for the two the kernel reads through buffer resources, a size:
 //   structure  entry i >= 1: the probed term's plain rank words, its sparse
-//              block entries (then srank_index into DevIndex::srank_w) or its
-//              bucket directory; entry 0 (the lead list): its doc ids;
+//              block entries (then srank_index into DevIndex::srank_w), its
+//              bucket directory, or (kPdTab) its doc-indexed score table, which
+//              is read in place of both the structure and the scores; entry 0
+//              (the lead list): its doc ids;
 //   scores     the term's build-time scores psc + off[t], or (a query-time plan,
 //              DevPlan::feat & 4) its tfn payloads;
 //   aux        a directory term's doc ids doc + off[t] (no size: read through
@@ -351,6 +377,7 @@ static_assert(sizeof(ProbeDesc) == 32, "one s_load_dwordx8");
 constexpr uint32_t kPdDir = 1u << 12;     // a bucket directory (else rank words)
 constexpr uint32_t kPdWide = 1u << 13;    // a range does not fit a buffer resource: plain loads
 constexpr uint32_t kPdSparse = 1u << 14;  // sparse rank words: the structure holds block entries
+constexpr uint32_t kPdTab = 1u << 15;     // a doc-indexed score table (DevIndex::dtab): the score at doc << 2
 constexpr uint32_t kPdMaxBytes = 0x80000000u;  // largest range read through a buffer resource
 // offsets of a lane that is not live: past every range, aligned to the load, and no
 // dword of the load wraps around 2^32
@@ -366,21 +393,34 @@ struct ProbeTerm {
   uint64_t off, end;  // its postings [off, end)
   uint32_t meta;      // tmeta
   uint32_t dir_off;   // first directory entry
+  uint32_t tab;       // its score table's slot + 1 (DevIndex::dtab), 0: none
 };
+
+// Does a probe of a term with a score table (df of n_docs docs) read the table?
+// A table line covers 32 docs, so lead_df * 32 / n_docs lead candidates share
+// one: at least tab_lead of them (0: always), or the term is in half the docs
+// (its psc is then as dense as its table).
+inline bool probe_uses_table(uint64_t n_docs, uint64_t df, uint64_t lead_df, uint32_t tab_lead) {
+  return lead_df * 32 >= n_docs * tab_lead || df * 2 >= n_docs;
+}
 
 // Do the arrays the descriptors point into lie where 48 bits address them?
 // (every array is < 2^47 bytes, so its base below 2^47 covers its end)
 inline bool probe_addr_ok(const DevIndex& ix) {
   for (const void* p : {(const void*)ix.doc, (const void*)ix.psc, (const void*)ix.tfn, (const void*)ix.dir,
-                        (const void*)ix.rank, (const void*)ix.srank})
+                        (const void*)ix.rank, (const void*)ix.srank, (const void*)ix.dtab})
     if ((uint64_t)(uintptr_t)p >> 47) return false;
   return true;
 }
 
 // The descriptor of term t for a plan over snapshot view ix (device addresses;
 // nothing is dereferenced): the lead list's (entry 0) or a probed list's, with
-// the build-time scores or (qt) the payloads, ub = q_ub[i + 1].
-inline ProbeDesc probe_desc(const DevIndex& ix, const ProbeTerm& t, bool lead, bool qt, float ub) {
+// the build-time scores or (qt) the payloads, ub = q_ub[i + 1].  A probed term
+// with a score table gets a kPdTab descriptor over it when the plan runs on the
+// build-time scores and the lead list (lead_df postings) is dense enough
+// (probe_uses_table, tab_lead).
+inline ProbeDesc probe_desc(const DevIndex& ix, const ProbeTerm& t, bool lead, bool qt, float ub, uint64_t lead_df = 0,
+                            uint32_t tab_lead = kDocTabLead) {
   const uint64_t df = t.end - t.off;
   uint64_t base, bytes, aux = 0;
   uint32_t kind;
@@ -389,6 +429,10 @@ inline ProbeDesc probe_desc(const DevIndex& ix, const ProbeTerm& t, bool lead, b
     base = (uint64_t)(uintptr_t)(ix.doc + t.off);
     bytes = df * 4;
     kind = 0;
+  } else if (!qt && t.tab && ix.dtab && probe_uses_table(ix.n_docs, df, lead_df, tab_lead)) {
+    base = (uint64_t)(uintptr_t)(ix.dtab + (uint64_t)(t.tab - 1) * ix.dtab_stride);
+    bytes = (uint64_t)ix.n_docs * 4;  // (<= kPdMaxBytes: a longer table is not built)
+    kind = kPdTab;
   } else if (slot && slot <= ix.n_prank) {
     base = (uint64_t)(uintptr_t)(ix.rank + (uint64_t)(slot - 1) * ix.rank_words);
     bytes = (uint64_t)ix.rank_words * 8;
@@ -404,8 +448,10 @@ inline ProbeDesc probe_desc(const DevIndex& ix, const ProbeTerm& t, bool lead, b
     aux = (uint64_t)(uintptr_t)(ix.doc + t.off);
     kind = (B & 0x3Fu) | ((S & 0x3Fu) << 6) | kPdDir;
   }
-  const uint64_t sc = qt ? (uint64_t)(uintptr_t)(ix.tfn + t.off) : (uint64_t)(uintptr_t)(ix.psc + t.off);
-  const uint64_t sc_bytes = df * (qt ? 2 : 4);
+  // (a table stands for the scores too: the kernel's score loads go through this range)
+  const bool tab = (kind & kPdTab) != 0;
+  const uint64_t sc = tab ? base : qt ? (uint64_t)(uintptr_t)(ix.tfn + t.off) : (uint64_t)(uintptr_t)(ix.psc + t.off);
+  const uint64_t sc_bytes = tab ? bytes : df * (qt ? 2 : 4);
   // (addresses are packed in 48 bits: the planner refuses a snapshot whose arrays lie higher, probe_addr_ok)
   if (bytes > kPdMaxBytes || sc_bytes > kPdMaxBytes) kind |= kPdWide;
   ProbeDesc p;
@@ -669,6 +715,18 @@ constexpr uint32_t kKtopChunk = FG_KTOP_CHUNK;  // postings per k_ktop_part work
 constexpr uint32_t kKtopTiny = 64;              // k_ktop_tiny: terms of at most this many postings, one wave each
 constexpr uint32_t kPackTerms = 256;            // k_score / k_bucket: term ids per packed chunk
 
+// The score tables of a build (k_dtab_fill / k_dtab_scatter): table i takes the
+// scores psc[off[i] .. off[i] + df[i]) at their postings' docs.
+struct DocTabJob {
+  const uint32_t* doc;
+  const float* psc;
+  float* tab;
+  uint64_t stride;  // floats per table
+  uint32_t n;       // tables
+  uint32_t df[kDocTabMax];
+  uint64_t off[kDocTabMax];
+};
+
 // kernels.hip entry points (host-callable launchers)
 hipError_t launch_conj(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 // k_disj over the items [first, first + count) of the plan's k_disj range (in
@@ -687,6 +745,9 @@ hipError_t launch_count(const DevIndex& ix, const DevCount& c, hipStream_t s, hi
 hipError_t launch_rank(const uint32_t* doc, const uint64_t* slot_base, const uint32_t* slot_n, uint32_t n_slots,
                        uint32_t n_words, uint64_t* out, hipStream_t s);
 hipError_t launch_score(const ScoreJob& j, uint32_t n_chunks, hipStream_t s);
+// the score tables of a build (DevIndex::dtab) from its posting scores: one fill pass, then one
+// scatter over the chosen terms' postings
+hipError_t launch_doctab(const DocTabJob& j, uint32_t grid_cap, hipStream_t s);
 hipError_t launch_bucket(const ScoreJob& j, uint32_t n_chunks, uint32_t n_docs, hipStream_t s);  // packed chunks
 hipError_t launch_tsub(const ScoreJob& j, uint32_t n_docs, hipStream_t s);                        // after k_bucket
 hipError_t launch_ktop(const ScoreJob& j, uint32_t n_terms, uint32_t n_chunks, uint32_t n_big, hipStream_t s);

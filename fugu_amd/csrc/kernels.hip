@@ -533,7 +533,8 @@ __device__ inline float probe_wide_one(const DevIndex& ix, const ProbeDesc& pd, 
 
 // The score at the doc of each live item of the clause that descriptor pd
 // describes (-1: its term is absent from the doc), through the term's rank words
-// or its bucket directory, then the hits' build-time scores -- or their tf /
+// or its bucket directory, then the hits' build-time scores (a kPdTab clause:
+// straight from the term's doc-indexed score table, one load) -- or their tf /
 // fieldnorm payloads and query-time scores (weights wt / wn, caches ct / cn);
 // the N items' loads are in flight together.  Everything comes from pd's scalar
 // words; the gathers go through its ranges' buffer resources at per-lane byte
@@ -554,7 +555,14 @@ __device__ inline void probe_list(const DevIndex& ix, const ProbeDesc& pd, const
   const BufRsrc rs = pd_rsrc(sbase, pd.sc_bytes);
   const BufRsrc rr = pd_rsrc(pd_base(pd), pd.bytes);
   uint32_t pos[N];
-  if (!(pd.kind & kPdDir)) {
+  if (!(kF & kFQt) && (pd.kind & kPdTab)) {
+    // a doc-indexed score table (build-time plans only): the scores range IS the
+    // table, so the doc stands for the position and the score load below is the
+    // whole probe -- no rank word, no dependent round trip; an absent term's
+    // entry is -1.0f itself
+#pragma unroll
+    for (uint32_t j = 0; j < N; ++j) pos[j] = (live & (1u << j)) ? doc[j] : kInvalid;
+  } else if (!(pd.kind & kPdDir)) {
     // rank words: presence + rank in one 8-B load per item (all items'
     // loads in flight together; sparse ones: the block entries, then the
     // words), then the score (or payload) of the hits
@@ -2630,6 +2638,43 @@ hipError_t launch_rank(const uint32_t* doc, const uint64_t* slot_base, const uin
   const uint32_t cps = (n_words + kRankChunkWords - 1) / kRankChunkWords;
   if ((uint64_t)cps * n_slots > 0x7FFFFFFFull) return hipErrorInvalidValue;
   k_rank<<<cps * n_slots, kThreads, 0, s>>>(doc, slot_base, slot_n, cps, n_words, out);
+  return hipGetLastError();
+}
+
+// Snapshot build: the doc-indexed score tables of the densest terms
+// (DevIndex::dtab, DocTabJob).  k_dtab_fill writes -1.0f (absent) over every
+// table; k_dtab_scatter then puts each chosen term's build-time scores at their
+// postings' docs (blockIdx.y: the table; a doc id is < n_docs <= stride: the
+// build checked the postings).  Plain vector stores, in steps of the grid.
+__global__ __launch_bounds__(kThreads) void k_dtab_fill(float* __restrict__ tab, uint64_t n) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kThreads)
+    tab[i] = -1.0f;
+}
+
+__global__ __launch_bounds__(kThreads) void k_dtab_scatter(DocTabJob j) {
+  const uint32_t t = blockIdx.y;
+  const uint64_t off = j.off[t];
+  const uint32_t df = j.df[t];
+  float* __restrict__ tab = j.tab + (uint64_t)t * j.stride;
+  for (uint32_t p = blockIdx.x * kThreads + threadIdx.x; p < df; p += gridDim.x * kThreads) {
+    const uint32_t d = j.doc[off + p];
+    if (d < j.stride) tab[d] = j.psc[off + p];
+  }
+}
+
+hipError_t launch_doctab(const DocTabJob& j, uint32_t grid_cap, hipStream_t s) {
+  if (j.n == 0 || j.stride == 0) return hipSuccess;
+  if (j.n > kDocTabMax) return hipErrorInvalidValue;
+  const uint32_t cap = grid_cap ? grid_cap : 0x10000u;
+  const uint64_t total = (uint64_t)j.n * j.stride;
+  k_dtab_fill<<<(uint32_t)std::min<uint64_t>((total + kThreads - 1) / kThreads, cap), kThreads, 0, s>>>(j.tab, total);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  uint32_t dfmax = 1;
+  for (uint32_t i = 0; i < j.n; ++i) dfmax = std::max(dfmax, j.df[i]);
+  // (p + gridDim.x * kThreads stays below 2^32: df < 2^31, at most 2^15 workgroups per table)
+  const uint32_t gx = std::min<uint32_t>((dfmax + kThreads - 1) / kThreads, std::max<uint32_t>(1u, std::min(cap, 0x8000u) / j.n));
+  k_dtab_scatter<<<dim3(gx, j.n), kThreads, 0, s>>>(j);
   return hipGetLastError();
 }
 

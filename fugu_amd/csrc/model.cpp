@@ -27,7 +27,7 @@ using fgh::parallel_dynamic;
 
 namespace {
 
-enum Arr : uint32_t { A_DOC, A_TFN, A_RANK, A_SRANK, A_SRANKW, A_DIR, A_BMAX, A_TMAX, A_TDIR, A_CMAX, A_TSUB, A_N };
+enum Arr : uint32_t { A_DOC, A_TFN, A_RANK, A_SRANK, A_SRANKW, A_DIR, A_BMAX, A_TMAX, A_TDIR, A_CMAX, A_TSUB, A_DTAB, A_N };
 constexpr uint64_t kLine = 128;
 constexpr float kInflate = 1.00000762939453125f;  // kernels.hip inflate_bound: 1 + 2^-17
 
@@ -40,6 +40,7 @@ struct Snap {
   const fg_index* ix = nullptr;
   const uint32_t* doc = nullptr;
   uint32_t pw = 2;  // payload bytes per posting the kernels load (tfn, + tfn_name)
+  uint32_t tab_lead = 0;  // the plans' score-table rule (fg::probe_uses_table)
   std::vector<float> psc, tmax, bmax, cmax;
   std::vector<uint64_t> tsub, srank;  // srank: the sparse rank block entries
   std::vector<uint32_t> dir_off, toff, coff;
@@ -120,6 +121,8 @@ struct Snap {
     bytes[A_TMAX] = bytes[A_TDIR] = 4 * x->tile_entries;
     bytes[A_CMAX] = 4ull * x->n_sc;
     bytes[A_TSUB] = 8ull * tsub.size();
+    bytes[A_DTAB] = x->dtab_bytes;
+    tab_lead = fgh::doctab_lead();
     return FG_OK;
   }
   // the loads of a rank-kind probe of doc d (plain: the word; sparse: the
@@ -219,12 +222,19 @@ struct Union {
 inline uint64_t key_of(float s, uint32_t d) { return fg::make_key(s, d); }
 
 // Probe of term t at doc d as k_conj's probe_list / k_disj's rank probe and
-// directory search issue it (stream s); returns the posting score or -1.
-float probe_term(const Snap& S, Acc& A, uint32_t s, uint32_t t, uint32_t d, double& cat) {
+// directory search issue it (stream s); returns the posting score or -1.  tab:
+// the term's score table slot + 1 when k_conj's plan probes it (one 4-B load of
+// the table, no rank word and no score load), else 0.
+float probe_term(const Snap& S, Acc& A, uint32_t s, uint32_t t, uint32_t d, double& cat, uint32_t tab = 0) {
   const uint32_t meta = S.ix->tmeta[t];
   const uint32_t slot = fg::meta_slot(meta);
   const uint32_t* l = S.list(t);
   const uint64_t n = S.len(t), base = S.ix->off[t];
+  if (tab) {
+    A.gather(s, A_DTAB, ((uint64_t)(tab - 1) * S.ix->d.dtab_stride + d) * 4, 4, cat);
+    const uint64_t p = std::lower_bound(l, l + n, d) - l;
+    return p < n && l[p] == d ? S.psc[base + p] : -1.0f;
+  }
   if (slot && fg::meta_rank(meta)) {
     S.rank_loads(A, s, slot, d, cat);
     const uint64_t p = std::lower_bound(l, l + n, d) - l;
@@ -295,13 +305,20 @@ uint64_t model_conj(const Snap& S, const uint32_t* terms, uint32_t m, bool has_t
   }
   A.range(0, A_DOC, base, df, 4, A.stream);
   A.range(0, A_TFN, base, df, S.pw, A.stream);
+  // the probed lists a build-time plan reads through their score tables (plan.cpp: probe_desc)
+  uint32_t tab[fg::kMaxTerms] = {0};
+  if (ix->same_stats && !ix->dtab_map.empty())
+    for (uint32_t j = 1; j < m; ++j) {
+      const uint32_t sl = fgh::doctab_slot(*ix, terms[j]);
+      if (sl && fg::probe_uses_table(ix->n_docs, S.len(terms[j]), df, S.tab_lead)) tab[j] = sl;
+    }
   for (uint64_t p = 0; p < df; ++p) {
     const uint32_t d = ld[p];
     float s0 = S.psc[base + p], acc = 0.0f;
     if (thk && key_of((s0 + qub[1]) * kInflate, d) < thk) continue;
     bool ok = true;
     for (uint32_t j = 1; j < m && ok; ++j) {
-      const float sc = probe_term(S, A, j, terms[j], d, A.probe);
+      const float sc = probe_term(S, A, j, terms[j], d, A.probe, tab[j]);
       if (sc < 0.0f) { ok = false; break; }
       if (j == 1) s0 = s0 + sc; else acc += sc;
       if (thk && j + 1 < m && key_of((s0 + acc + qub[j + 1]) * kInflate, d) < thk) ok = false;
@@ -610,7 +627,7 @@ int fg_model_batch(const fg_index* ix, const fg_query_batch* q, uint32_t k, cons
   out->alg_bytes = out->stream_bytes + out->probe_bytes + out->output_bytes;
   out->line_bytes = (double)kLine * (double)U.count();
   if (getenv("FUGU_MODEL_TRACE")) {  // the line floor and the per-query line sum, by array
-    static const char* names[A_N] = {"doc", "tfn", "rank", "srank", "srankw", "dir", "bmax", "tmax", "tdir", "cmax", "tsub"};
+    static const char* names[A_N] = {"doc", "tfn", "rank", "srank", "srankw", "dir", "bmax", "tmax", "tdir", "cmax", "tsub", "dtab"};
     for (uint32_t a = 0; a < A_N; ++a)
       fprintf(stderr, "[fg model] %-6s floor %8.3f GB  per-query sum %8.3f GB\n", names[a],
               (double)kLine * (double)U.count(a) * 1e-9, (double)kLine * (double)U.qlines[a].load() * 1e-9);

@@ -162,6 +162,7 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
   const uint32_t nq = q->n_queries;
   const uint64_t N = ix->n_docs;
   const bool disj = q->mode == FG_MODE_OR;
+  const uint32_t tab_lead = fgh::doctab_lead();
   h.clear();
   const size_t nqt = (size_t)nq * fg::kMaxTerms;
   for (auto* v : {&h.q_m, &h.lead}) v->assign(nq, 0);
@@ -414,10 +415,13 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
       // the clauses' probe descriptors: the lead list's, then each probed list's
       // with the bound applied after it
       const size_t row = (size_t)i * fg::kMaxTerms;
+      const uint64_t lead_df = ix->off[qt[0] + 1] - ix->off[qt[0]];
       for (uint32_t j = 0; j < mt; ++j) {
         const uint32_t t = qt[j];
-        const fg::ProbeTerm pt{ix->off[t], ix->off[t + 1], ix->tmeta[t], ix->dir_off[t]};
-        h.q_probe[row + j] = fg::probe_desc(ix->d, pt, j == 0, qtime, j + 1 < mt ? h.q_ub[row + j + 1] : 0.0f);
+        const uint32_t tab = j && !qtime && !ix->dtab_map.empty() ? fgh::doctab_slot(*ix, t) : 0u;
+        const fg::ProbeTerm pt{ix->off[t], ix->off[t + 1], ix->tmeta[t], ix->dir_off[t], tab};
+        h.q_probe[row + j] =
+            fg::probe_desc(ix->d, pt, j == 0, qtime, j + 1 < mt ? h.q_ub[row + j + 1] : 0.0f, lead_df, tab_lead);
       }
     }
     // one list: its K'-th best alive score (the smallest stored K' >= k) bounds

@@ -60,7 +60,7 @@ EXPORTS = (
     "fg_ctx_peer_access", "fg_plan_link", "fg_bytes_model_or", "fg_plan_create_multi", "fg_plan_execute_merged", "fg_index_term_kth",
     "fg_model_batch", "fg_abi_version", "fg_index_term_ladder", "fg_kth_floor_combine", "fg_index_set_kth_floor",
     "fg_plan_set_peers", "fg_plan_ipc_export", "fg_plan_set_ipc_peers", "fg_plan_reset",
-    "fg_count_batch", "fg_count_trace",
+    "fg_count_batch", "fg_count_trace", "fg_index_doctab_get",
 )
 LADDER_KS = (1, 2, 3, 5, 10, 13, 20, 25, 50, 100, 125, 250, 500, 1000)  # FG_LADDER_LEVELS ranks
 KTH_KS = (1, 10, 20, 100, 1000)  # fg_index_term_kth / fg_index_set_kth_floor ranks
@@ -162,6 +162,7 @@ _sig("fg_index_retain", C.c_int, _p)
 _sig("fg_thread_background", C.c_int, C.c_int)
 _sig("fg_index_release", C.c_int, _p)
 _sig("fg_index_stats_get", C.c_int, _p, C.POINTER(IndexStats))
+_sig("fg_index_doctab_get", C.c_int, _p, _u32p, _u64p)
 _sig("fg_index_df", C.c_uint64, _p, C.c_int, C.c_uint32)
 _sig("fg_index_bm25", C.c_int, _p, C.c_uint32, _f32p, _f32p, _f32p)
 _sig("fg_plan_create", C.c_int, _p, C.POINTER(QueryBatch), C.c_uint32, C.POINTER(_p))
@@ -491,6 +492,12 @@ class Index:
         return Stats(s.n_docs, s.n_terms, s.n_postings, s.device_bytes, tuple(s.tot_tokens), tuple(s.avgdl),
                      bool(s.has_name), s.device, s.n_facet_terms, s.tot_facet_tokens, s.n_dense_f32, s.n_rank_terms,
                      s.n_sparse_rank_terms, s.rank_bytes, bool(s.has_positions))
+
+    def doc_tables(self):
+        """(terms with a doc-indexed score table, the tables' device bytes): fg_index_doctab_get."""
+        n, b = C.c_uint32(0), C.c_uint64(0)
+        _check(_lib.fg_index_doctab_get(self._h, C.byref(n), C.byref(b)))
+        return int(n.value), int(b.value)
 
     def df(self, term: int, field: int = -1) -> int:
         return int(_lib.fg_index_df(self._h, field, term))

@@ -236,6 +236,11 @@ typedef struct fg_index_stats {
   uint64_t rank_bytes;       /* device bytes of the rank words, plain and sparse */
 } fg_index_stats;
 int fg_index_stats_get(const fg_index* ix, fg_index_stats* out);
+/* The snapshot's doc-indexed score tables (the densest terms' build-time scores
+ * by doc id, which conjunctions probe in place of rank word + score; shared with
+ * its rescores and counted in device_bytes): how many terms have one and the
+ * tables' device bytes.  Either pointer may be NULL. */
+int fg_index_doctab_get(const fg_index* ix, uint32_t* n_terms, uint64_t* bytes);
 /* doc_freq of `term` in `field` (tantivy Searcher::doc_freq; FG_FIELD_FACET:
  * a facet term), and the merged (text U name) posting-list length when field < 0. */
 uint64_t fg_index_df(const fg_index* ix, int field, uint32_t term);
