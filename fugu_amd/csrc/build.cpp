@@ -178,19 +178,21 @@ int score_postings(const fg_index* ix, fg::ScoreJob& j, float* cmax, float* psc,
 // posting bytes (12 B each, as the rank budget counts them), so a small shard
 // or namespace pays in proportion.  None for a snapshot of fewer than
 // kDocTabMinDocs docs, or one whose table would not fit a buffer resource.
-std::vector<uint32_t> choose_doctab_terms(const fg_index* ix, uint64_t stride) {
+// The one-byte bound tables (DevIndex::dtab8) are chosen the same way: env
+// FUGU_DOCTAB8_DIV (default kDocTab8Div), eb = 1 byte per doc.
+std::vector<uint32_t> choose_doctab_terms(const fg_index* ix, uint64_t stride, const char* env = "FUGU_DOCTAB_DIV",
+                                          uint32_t div = fg::kDocTabDiv, uint64_t eb = 4) {
   std::vector<uint32_t> ts;
   const uint64_t N = ix->n_docs;
-  uint32_t div = fg::kDocTabDiv;
-  if (const char* e = getenv("FUGU_DOCTAB_DIV"))
+  if (const char* e = getenv(env))
     if (*e) div = (uint32_t)std::max(0l, atol(e));
-  if (!div || N < fg::kDocTabMinDocs || 4 * N > fg::kPdMaxBytes) return ts;
+  if (!div || N < fg::kDocTabMinDocs || 4 * N > fg::kPdMaxBytes || !stride) return ts;
   auto df = [&](uint32_t t) { return ix->off[t + 1] - ix->off[t]; };
   for (uint32_t t = 0; t < ix->n_terms; ++t)
     if (df(t) * div >= N) ts.push_back(t);
   std::stable_sort(ts.begin(), ts.end(), [&](uint32_t a, uint32_t b) { return df(a) > df(b); });
   const uint64_t budget = 12ull * ix->n_postings / fg::kDocTabFrac;
-  ts.resize(std::min<uint64_t>({(uint64_t)ts.size(), (uint64_t)fg::kDocTabMax, budget / (4 * stride)}));
+  ts.resize(std::min<uint64_t>({(uint64_t)ts.size(), (uint64_t)fg::kDocTabMax, budget / (eb * stride)}));
   return ts;
 }
 
@@ -212,17 +214,23 @@ int build_bounds(fg_index* ix, const std::vector<uint32_t>& alive) {
   const uint64_t tab_stride = ((uint64_t)ix->n_docs + 31) & ~31ull;
   std::vector<uint32_t> tabs = choose_doctab_terms(ix, tab_stride);
   const size_t bounds_total = L.total;
-  const Parts::P p_dtab = L.add(4ull * tab_stride * tabs.size());
-  size_t total = tabs.empty() ? bounds_total : L.total;
+  // (a kind with no table takes no part: not even an empty part's alignment slot)
+  const Parts::P p_dtab = tabs.empty() ? Parts::P{} : L.add(4ull * tab_stride * tabs.size());
+  // ... then the one-byte bound tables, the same way (FUGU_DOCTAB_DIV=0 leaves these)
+  const uint64_t tab8_stride = ((uint64_t)ix->n_docs + 127) & ~127ull;
+  std::vector<uint32_t> tabs8 = choose_doctab_terms(ix, tab8_stride, "FUGU_DOCTAB8_DIV", fg::kDocTab8Div, 1);
+  const Parts::P p_dtab8 = tabs8.empty() ? Parts::P{} : L.add(tab8_stride * tabs8.size());
+  size_t total = L.total;
   if (!ix->spool) {
     ix->spool = std::make_shared<fgh::ScorePool>();
     ix->spool->dev = ix->dev;
   }
   auto sb = std::make_shared<fgh::ScoreBlock>();
   void* blk = ix->spool->get(total);
-  if (!blk && !tabs.empty()) {  // (a build never fails for want of the tables)
+  if (!blk && !(tabs.empty() && tabs8.empty())) {  // (a build never fails for want of the tables)
     (void)hipGetLastError();
     tabs.clear();
+    tabs8.clear();
     total = bounds_total;
     blk = ix->spool->get(total);
   }
@@ -273,6 +281,31 @@ int build_bounds(fg_index* ix, const std::vector<uint32_t>& alive) {
   j.ktop = d_ktop;
   j.n_dir = ix->dir_entries;
   HIPCHK(fg::launch_bucket(j, ix->n_bk, ix->n_docs, kBuildStream));
+  // the dense terms' bound tables: each score quantized up against its term's
+  // maximum, which k_bucket has just written (none: no launch)
+  uint8_t* d_dtab8 = tabs8.empty() ? nullptr : Parts::at<uint8_t>(blk, p_dtab8);
+  if (d_dtab8) {
+    fg::DocTab8Job tj{};
+    tj.doc = ix->d.doc;
+    tj.psc = d_psc;
+    tj.tmaxs = reinterpret_cast<const float*>(d_tmaxs);
+    tj.tab = d_dtab8;
+    tj.stride = tab8_stride;
+    tj.n = (uint32_t)tabs8.size();
+    std::vector<uint64_t> map(tabs8.size());
+    for (uint32_t i = 0; i < tabs8.size(); ++i) {
+      tj.term[i] = tabs8[i];
+      tj.off[i] = ix->off[tabs8[i]];
+      tj.df[i] = (uint32_t)(ix->off[tabs8[i] + 1] - ix->off[tabs8[i]]);
+      map[i] = ((uint64_t)tabs8[i] << 32) | i;
+    }
+    HIPCHK(fg::launch_doctab8(tj, j.grid_cap, kBuildStream));
+    std::sort(map.begin(), map.end());
+    ix->dtab8_map = std::move(map);
+  }
+  ix->dtab8_bytes = tab8_stride * tabs8.size();
+  if (g_bt.on)
+    fprintf(stderr, "[fg build] bound tables: %zu terms, %.1f MiB\n", tabs8.size(), (double)ix->dtab8_bytes / (double)(1 << 20));
   j.tsub = d_tsub;
   HIPCHK(fg::launch_tsub(j, ix->n_docs, kBuildStream));
   if (int rc = ktop_pass(ix, j)) return rc;
@@ -320,6 +353,8 @@ int build_bounds(fg_index* ix, const std::vector<uint32_t>& alive) {
   ix->d.cmax = d_cmax;
   ix->d.dtab = d_dtab;
   ix->d.dtab_stride = (uint32_t)tab_stride;
+  ix->d.dtab8 = d_dtab8;
+  ix->d.dtab8_stride = (uint32_t)tab8_stride;
   ix->d.alive = d_alive;
   ix->device_bytes = ix->struct_bytes + total;
   return FG_OK;

@@ -431,6 +431,9 @@ struct IndexBounds {
   // term that has one, ascending by term (doctab_slot), and their bytes
   SharedVec<uint64_t> dtab_map;
   uint64_t dtab_bytes = 0;
+  // the one-byte bound tables (DevIndex::dtab8, in sblock), the same way (doctab8_slot)
+  SharedVec<uint64_t> dtab8_map;
+  uint64_t dtab8_bytes = 0;
   uint64_t device_bytes = 0;
 };
 
@@ -445,6 +448,19 @@ inline uint32_t doctab_lead() {
 inline uint32_t doctab_slot(const IndexBounds& b, uint32_t t) {
   const auto it = std::lower_bound(b.dtab_map.begin(), b.dtab_map.end(), (uint64_t)t << 32);
   return it != b.dtab_map.end() && (uint32_t)(*it >> 32) == t ? (uint32_t)*it + 1u : 0u;
+}
+
+// lead candidates per 128-doc line from which a plan attaches a bound table to
+// clause 1 (fg::probe_uses_bound): FUGU_DOCTAB8_LEAD, read when a plan is made
+inline uint32_t doctab8_lead() {
+  const char* e = getenv("FUGU_DOCTAB8_LEAD");
+  return e && *e ? (uint32_t)std::max(0l, atol(e)) : fg::kDocTab8Lead;
+}
+
+// the bound table of local term t: its slot + 1, or 0
+inline uint32_t doctab8_slot(const IndexBounds& b, uint32_t t) {
+  const auto it = std::lower_bound(b.dtab8_map.begin(), b.dtab8_map.end(), (uint64_t)t << 32);
+  return it != b.dtab8_map.end() && (uint32_t)(*it >> 32) == t ? (uint32_t)*it + 1u : 0u;
 }
 }  // namespace fgh
 

@@ -66,6 +66,27 @@ constexpr uint32_t kDocTabFrac = 8;
 constexpr uint32_t kDocTabMax = 64;       // tables per snapshot (DocTabJob rides in the kernel arguments)
 constexpr uint32_t kDocTabMinDocs = 8192; // a snapshot of fewer docs (a commit's segment: a few lead chunks
                                           // per query, and its build must stay a short launch chain) gets none
+// One-byte score BOUND tables (DevIndex::dtab8) of the dense terms: byte d of a
+// term's table = quant8(its psc value at doc d, the term's maximum), 0 where the
+// term is absent.  k_conj reads one in front of the exact probe of a deferred
+// query's first probed list: presence and an upper bound of the score from ONE
+// byte of a line that serves 128 docs, and only the candidates the bound lets
+// through fetch the exact score.  A term in >= 1/kDocTab8Div of
+// the docs (env FUGU_DOCTAB8_DIV, 0: no tables), densest first, within the same
+// caps as the f32 tables (kDocTabFrac, kDocTabMax, kDocTabMinDocs); a plan
+// attaches the bound when the lead list brings >= kDocTab8Lead candidates per
+// 128-doc table line (env FUGU_DOCTAB8_LEAD, 0: always).  Sweep: DESIGN.md §3,
+// profiles/doctab8/.
+#ifndef FG_DOCTAB8_DIV
+// OFF by default: against the parent build, interleaved, the best swept setting (4 / 8) took k_conj 0.8796 ->
+// 0.8669 ms where the same kernel with no tables ran 0.8550 ms (tried and dropped as a default)
+#define FG_DOCTAB8_DIV 0
+#endif
+#ifndef FG_DOCTAB8_LEAD
+#define FG_DOCTAB8_LEAD 8
+#endif
+constexpr uint32_t kDocTab8Div = FG_DOCTAB8_DIV;
+constexpr uint32_t kDocTab8Lead = FG_DOCTAB8_LEAD;
 constexpr uint32_t kRankChunkWords = 2048;  // k_rank: words (65536 docs) per workgroup
 #ifndef FG_DISJ_GPQ
 #define FG_DISJ_GPQ 64
@@ -298,6 +319,11 @@ struct DevIndex {
                              //     statistics, as psc): entry d of a table = the term's psc value at doc d,
                              //     -1.0f where the term is absent.  k_conj reads them through its probe
                              //     descriptors (kPdTab); which term owns which table: fg_index::dtab_map (host)
+  const uint8_t* dtab8;      // [n tables * dtab8_stride] one-byte bound tables of the dense terms (build statistics):
+                             //     byte d of a table = quant8(the term's psc value at doc d, tmaxs[term]), never 0
+                             //     for a posting, 0 where the term is absent.  k_conj reads them through the
+                             //     bound fields of clause 1's probe descriptor (kPdBound); which term owns which
+                             //     table: fg_index::dtab8_map (host)
   const uint32_t* fdoc;      // [PF] facet postings (doc ids, ascending), CSR by facet term
   const uint64_t* foff;      // [VF+1]
   uint64_t n_esc;
@@ -309,6 +335,7 @@ struct DevIndex {
   uint32_t n_prank;          // plain rank-kind slots
   uint32_t srank_blocks;     // block entries per sparse rank-kind term: ceil(N / 1024)
   uint32_t dtab_stride;      // floats per score table: N rounded up to a 128-B line
+  uint32_t dtab8_stride;     // bytes per bound table: N rounded up to a 128-B line
   // Forward index (fg_docs_input::keep_positions; nullptr without): per field the
   // doc's tokens addressed by POSITION, fwd[fwd_off[d] + p] = the VOCABULARY id of
   // the token at analyzer position p of doc d, kFwdNone where the analyzer dropped
@@ -371,6 +398,9 @@ struct ProbeDesc {
   uint32_t kind;      // bits 0-5 shift (structure index = doc >> shift: 5 plain rank words, 10 sparse
                       // block entries, B_t directory), 6-11 S_t (directory search steps), kPd* flags,
                       // 16-31 aux address bits 32-47
+                      // A rank-word or table clause has no aux range and no S_t; entry 1 of a deferred
+                      // query may carry a BOUND there (probe_desc_bound): kPdBound (bit 6), the bound
+                      // table's address in aux_lo / bits 16-31, the term's maximum in ENTRY 0's aux_lo
   uint32_t ub;        // f32 bits of q_ub[i + 1], the MaxScore bound applied after list i (0.0 past the last)
 };
 static_assert(sizeof(ProbeDesc) == 32, "one s_load_dwordx8");
@@ -378,6 +408,7 @@ constexpr uint32_t kPdDir = 1u << 12;     // a bucket directory (else rank words
 constexpr uint32_t kPdWide = 1u << 13;    // a range does not fit a buffer resource: plain loads
 constexpr uint32_t kPdSparse = 1u << 14;  // sparse rank words: the structure holds block entries
 constexpr uint32_t kPdTab = 1u << 15;     // a doc-indexed score table (DevIndex::dtab): the score at doc << 2
+constexpr uint32_t kPdBound = 1u << 6;    // (never with kPdDir) aux = the term's one-byte bound table (DevIndex::dtab8)
 constexpr uint32_t kPdMaxBytes = 0x80000000u;  // largest range read through a buffer resource
 // offsets of a lane that is not live: past every range, aligned to the load, and no
 // dword of the load wraps around 2^32
@@ -408,7 +439,7 @@ inline bool probe_uses_table(uint64_t n_docs, uint64_t df, uint64_t lead_df, uin
 // (every array is < 2^47 bytes, so its base below 2^47 covers its end)
 inline bool probe_addr_ok(const DevIndex& ix) {
   for (const void* p : {(const void*)ix.doc, (const void*)ix.psc, (const void*)ix.tfn, (const void*)ix.dir,
-                        (const void*)ix.rank, (const void*)ix.srank, (const void*)ix.dtab})
+                        (const void*)ix.rank, (const void*)ix.srank, (const void*)ix.dtab, (const void*)ix.dtab8})
     if ((uint64_t)(uintptr_t)p >> 47) return false;
   return true;
 }
@@ -466,6 +497,35 @@ inline ProbeDesc probe_desc(const DevIndex& ix, const ProbeTerm& t, bool lead, b
   c.f = ub;
   p.ub = c.u;
   return p;
+}
+
+// Does clause 1 of a deferred query read its term's bound table first?  The
+// shape of probe_uses_table with a line of 128 docs: at least tab8_lead lead
+// candidates per table line (0: always), or the term is in half the docs.
+inline bool probe_uses_bound(uint64_t n_docs, uint64_t df, uint64_t lead_df, uint32_t tab8_lead) {
+  return lead_df * 128 >= n_docs * tab8_lead || df * 2 >= n_docs;
+}
+
+// The bound of clause 1 (p1, the first probed list's descriptor as probe_desc
+// made it; lead: entry 0): attached when the query takes k_conj's deferred path
+// (>= 3 unfiltered Must lists and nothing else), the plan runs on build-time
+// scores (!qt), the term has a bound table (tab8: its slot + 1) and the lead
+// rule holds.  p1's exact ranges stay what they are; its unused aux fields take
+// the table's address and kPdBound, entry 0's unused aux_lo the f32 bits of M
+// (the term's build-time maximum, tmaxs: what the table was quantized against).
+// Returns whether it was attached; otherwise both descriptors are untouched.
+inline bool probe_desc_bound(const DevIndex& ix, ProbeDesc& lead, ProbeDesc& p1, uint32_t tab8, float M, bool deferred,
+                             bool qt, uint64_t df, uint64_t lead_df, uint32_t tab8_lead = kDocTab8Lead) {
+  if (!deferred || qt || !tab8 || !ix.dtab8 || !(M > 0.0f)) return false;
+  if (p1.kind & (kPdDir | kPdWide)) return false;  // (a table term has rank words; a wide clause is probed item by item)
+  if (!probe_uses_bound(ix.n_docs, df, lead_df, tab8_lead)) return false;
+  const uint64_t a = (uint64_t)(uintptr_t)(ix.dtab8 + (uint64_t)(tab8 - 1) * ix.dtab8_stride);
+  p1.aux_lo = (uint32_t)a;
+  p1.kind = (p1.kind & 0xFFFFu) | kPdBound | (uint32_t)((a >> 32) & 0xFFFFu) << 16;
+  union { float f; uint32_t u; } c;
+  c.f = M;
+  lead.aux_lo = c.u;
+  return true;
 }
 
 // Facet filters of a planned batch (DevPlan).  Every distinct clause list
@@ -727,6 +787,20 @@ struct DocTabJob {
   uint64_t off[kDocTabMax];
 };
 
+// The bound tables of a build (k_dtab8_fill / k_dtab8_scatter): table i takes
+// quant8(psc[off[i] + p], tmaxs[term[i]]) at the doc of posting p of its term.
+struct DocTab8Job {
+  const uint32_t* doc;
+  const float* psc;
+  const float* tmaxs;  // [V] the term maxima (k_bucket has run)
+  uint8_t* tab;
+  uint64_t stride;  // bytes per table (a multiple of 128)
+  uint32_t n;       // tables
+  uint32_t term[kDocTabMax];
+  uint32_t df[kDocTabMax];
+  uint64_t off[kDocTabMax];
+};
+
 // kernels.hip entry points (host-callable launchers)
 hipError_t launch_conj(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 // k_disj over the items [first, first + count) of the plan's k_disj range (in
@@ -748,6 +822,8 @@ hipError_t launch_score(const ScoreJob& j, uint32_t n_chunks, hipStream_t s);
 // the score tables of a build (DevIndex::dtab) from its posting scores: one fill pass, then one
 // scatter over the chosen terms' postings
 hipError_t launch_doctab(const DocTabJob& j, uint32_t grid_cap, hipStream_t s);
+// the bound tables of a build (DevIndex::dtab8), after launch_bucket: one fill pass, one scatter
+hipError_t launch_doctab8(const DocTab8Job& j, uint32_t grid_cap, hipStream_t s);
 hipError_t launch_bucket(const ScoreJob& j, uint32_t n_chunks, uint32_t n_docs, hipStream_t s);  // packed chunks
 hipError_t launch_tsub(const ScoreJob& j, uint32_t n_docs, hipStream_t s);                        // after k_bucket
 hipError_t launch_ktop(const ScoreJob& j, uint32_t n_terms, uint32_t n_chunks, uint32_t n_big, hipStream_t s);

@@ -767,6 +767,13 @@ int fg_index_doctab_get(const fg_index* ix, uint32_t* n_terms, uint64_t* bytes) 
   return FG_OK;
 }
 
+int fg_index_doctab8_get(const fg_index* ix, uint32_t* n_terms, uint64_t* bytes) {
+  if (!ix) return fail(FG_EINVAL, "bad arguments");
+  if (n_terms) *n_terms = (uint32_t)ix->dtab8_map.size();
+  if (bytes) *bytes = ix->dtab8_bytes;
+  return FG_OK;
+}
+
 uint64_t fg_index_df(const fg_index* ix, int field, uint32_t term) {
   if (ix && field == FG_FIELD_FACET) return term < ix->n_fterms ? ix->df_facet[term] : 0;
   if (!ix) return 0;

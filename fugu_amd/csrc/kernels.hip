@@ -91,13 +91,29 @@ __device__ inline uint64_t buf_u64(BufRsrc r, uint32_t off) {
 }
 __device__ inline uint32_t buf_u32(BufRsrc r, uint32_t off) { return __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0); }
 __device__ inline uint32_t buf_u16(BufRsrc r, uint32_t off) { return __builtin_amdgcn_raw_buffer_load_b16(r, (int)off, 0, 0); }
+__device__ inline uint32_t buf_u8(BufRsrc r, uint32_t off) { return __builtin_amdgcn_raw_buffer_load_b8(r, (int)off, 0, 0); }
 #else  // the host pass only parses device code
 typedef int BufRsrc;
 __device__ inline BufRsrc pd_rsrc(uint64_t, uint32_t) { return 0; }
 __device__ inline uint64_t buf_u64(BufRsrc, uint32_t) { return 0; }
 __device__ inline uint32_t buf_u32(BufRsrc, uint32_t) { return 0; }
 __device__ inline uint32_t buf_u16(BufRsrc, uint32_t) { return 0; }
+__device__ inline uint32_t buf_u8(BufRsrc, uint32_t) { return 0; }
 #endif
+
+// The results of N independent gathers as one group: an empty asm that names
+// all of them, so every load is issued before any result is consumed and the N
+// round trips overlap (8 and 4: k_conj's items per lane and flush entries per
+// thread; another N is left to the scheduler).
+template <uint32_t N>
+__device__ inline void loads_in_flight(uint32_t (&v)[N]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (N == 8)
+    asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
+  else if constexpr (N == 4)
+    asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
+#endif
+}
 
 // Upper bounds are compared after inflating by 2^-17 relative: a bound sums at
 // most 16 clauses plus the facet maximum (17 non-negative addends), whose f32
@@ -419,6 +435,9 @@ constexpr uint32_t kDeferCap = FG_DEFER;                                // entri
 constexpr uint32_t kDeferFlush = FG_DEFER_FLUSH;                        // flush once this full at a chunk end
 constexpr uint32_t kDeferR = kDeferCap ? (kDeferCap + kThreads - 1) / kThreads : 1;  // entries per thread in a flush
 constexpr uint64_t kDeferNone = ~0ull;                                  // a reserved slot left empty
+constexpr uint32_t kDeferNeed1 = 0x80000000u;  // an entry's score word: still to be probed in clause 1 (flush_deferred)
+// does a clause's descriptor carry a bound table? (kPdBound shares its bit with a directory's S_t)
+__device__ inline bool pd_bounded(uint32_t kind) { return (kind & (kPdDir | kPdBound)) == kPdBound; }
 static_assert(kTrunc + kDeferCap <= kBuf, "a flush after truncation must fit the key buffer");
 
 struct ConjShared {
@@ -603,11 +622,15 @@ __device__ inline void probe_list(const DevIndex& ix, const ProbeDesc& pd, const
       if (!((live & (1u << j)) && pos[j] < hi[j] && di[pos[j]] == doc[j])) pos[j] = kInvalid;
   }
   if constexpr (!(kF & kFQt)) {  // the build-time scores: one load per hit (kInvalid << 2 is kPdDead4)
+    // all N loads issued before the first result is used (loads_in_flight): left to
+    // itself the scheduler interleaved them with their selects, one or two in
+    // flight at a time, whenever the code around the probe changed
+    uint32_t raw[N];
 #pragma unroll
-    for (uint32_t j = 0; j < N; ++j) {
-      const float s = __uint_as_float(buf_u32(rs, pos[j] << 2));
-      sc[j] = pos[j] != kInvalid ? s : -1.0f;
-    }
+    for (uint32_t j = 0; j < N; ++j) raw[j] = buf_u32(rs, pos[j] << 2);
+    loads_in_flight(raw);
+#pragma unroll
+    for (uint32_t j = 0; j < N; ++j) sc[j] = pos[j] != kInvalid ? __uint_as_float(raw[j]) : -1.0f;
     return;
   }
   // the hits' payloads (a posting's is never 0: tf >= 1 in some field; kInvalid << 1
@@ -644,29 +667,69 @@ __device__ inline void probe_list(const DevIndex& ix, const ProbeDesc& pd, const
 // score), in intersection order with the MaxScore bound after each, and append
 // the survivors' keys.  The sums are the ones the inline path forms:
 // (left + right) + (0.0 + s_2 + ...).  Unfiltered queries only (no facet term).
+// A query whose clause 1 carries a bound (kPdBound) also queues candidates that
+// passed only the bound stage: (doc, left) tagged with kDeferNeed1 (the sign bit
+// of the score word; scores are >= 0).  For those the flush starts at clause 1:
+// its exact probe through the descriptor's ordinary ranges, left + right, the
+// bound after it, then on as the others.
+// Park a wave's live candidates (doc, score word | tag) in the deferred queue when
+// they fit (slots reserved with one LDS atomic) and return the lanes left live:
+// none then, all of them when the wave does not fit -- it probes on inline.
+__device__ inline uint32_t park_deferred(ConjShared& sh, const uint32_t (&doc)[kItems], const float (&s0)[kItems],
+                                         uint32_t live, uint32_t tag, uint32_t lane) {
+  uint32_t nw = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < kItems; ++j) nw += (uint32_t)__popcll(__ballot((live >> j) & 1u));
+  if (!nw) return live;
+  uint32_t base = 0;
+  if (lane == 0) base = atomicAdd(&sh.n_dq, nw);
+  base = (uint32_t)__shfl((int)base, 0, 64);
+  if (base + nw <= kDeferCap) {
+    uint32_t at = base;
+#pragma unroll
+    for (uint32_t j = 0; j < kItems; ++j) {
+      const bool b = (live >> j) & 1u;
+      const unsigned long long bal = __ballot(b);
+      if (b)
+        sh.dq[at + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] =
+            ((uint64_t)doc[j] << 32) | (__float_as_uint(s0[j]) | tag);
+      at += (uint32_t)__popcll(bal);
+    }
+    return 0;
+  }
+  for (uint32_t x = base + lane; x < kDeferCap; x += 64) sh.dq[x] = kDeferNone;  // the part that fit
+  return live;
+}
+
 template <uint32_t kF>
 __device__ void flush_deferred(const DevIndex& ix, ConjShared& sh, const ProbeDesc* probes, const uint32_t* terms,
                                const float* qwt, const float* qwn, uint32_t m, uint64_t thr, uint32_t nd) {
   const uint32_t tid = threadIdx.x;
-  uint32_t doc[kDeferR], live = 0;
+  uint32_t doc[kDeferR], live = 0, need1 = 0;
   float s01[kDeferR], acc[kDeferR];
 #pragma unroll
   for (uint32_t r = 0; r < kDeferR; ++r) {
     const uint32_t i = r * kThreads + tid;
     const uint64_t e = i < nd ? sh.dq[i] : kDeferNone;
     doc[r] = (uint32_t)(e >> 32);
-    s01[r] = __uint_as_float((uint32_t)e);
+    s01[r] = __uint_as_float((uint32_t)e & ~kDeferNeed1);
     acc[r] = 0.0f;
     live |= (doc[r] != kInvalid ? 1u : 0u) << r;
+    need1 |= (((uint32_t)e & kDeferNeed1) ? 1u : 0u) << r;
   }
-  for (uint32_t i = 2; i < m; ++i) {
+  need1 &= live;
+  for (uint32_t i = pd_bounded(probe_load(probes + 1).kind) ? 1 : 2; i < m; ++i) {
     if (!__any(live != 0)) break;
+    const uint32_t lv = i == 1 ? need1 : live;  // clause 1: the entries the bound stage queued
+    if (i == 1 && !__any(lv != 0)) continue;
     float sc[kDeferR];
     const ProbeDesc pd = probe_load(probes + i);
-    probe_list<kDeferR, kF>(ix, pd, terms + i, doc, live, qwt[i], qwn[i], sh.cache, sh.cache + 256, sc);
+    probe_list<kDeferR, kF>(ix, pd, terms + i, doc, lv, qwt[i], qwn[i], sh.cache, sh.cache + 256, sc);
 #pragma unroll
     for (uint32_t r = 0; r < kDeferR; ++r) {
+      if (!((lv >> r) & 1u)) continue;
       if (sc[r] < 0.0f) live &= ~(1u << r);
+      else if (i == 1) s01[r] = s01[r] + sc[r];  // left + right
       else acc[r] += sc[r];
     }
     if (thr != 0 && i + 1 < m) {
@@ -929,6 +992,30 @@ __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPl
         }
       }
       const ProbeDesc pd = probe_load(probes + i);
+      // The bound stage in front of the first probed list (a deferred query whose
+      // clause 1 carries a bound table, in a chunk that has a threshold): one byte
+      // per candidate at offset doc -- 0: the term is absent; else q8_bound of it is
+      // >= the posting's score, so a candidate that the bound after this list
+      // would keep out with the bound in the score's place is kept out by the
+      // exact score too (f32 addition is monotone): the same drops, decided on a
+      // line that serves 128 docs.  The survivors wait in the queue as (doc, left)
+      // and flush_deferred probes this list exactly for them; a wave that does
+      // not fit probes it inline, below.
+      // (build-time plans only: a query-time plan's descriptors never carry one)
+      const bool bstage = !(kF & kFQt) && i == 1 && defer && prune && pd_bounded(pd.kind);
+      if (bstage) {
+        const BufRsrc rb = pd_rsrc(pd_aux(pd), ix.n_docs);
+        const float M = __uint_as_float(ld.aux_lo), ub = __uint_as_float(pd.ub);
+        uint32_t b[kItems];
+#pragma unroll
+        for (uint32_t j = 0; j < kItems; ++j) b[j] = buf_u8(rb, (live & (1u << j)) ? doc[j] : 0xFFFFFFFFu);
+#pragma unroll
+        for (uint32_t j = 0; j < kItems; ++j)
+          if ((live & (1u << j)) && (b[j] == 0u || make_key(inflate_bound(s0[j] + q8_bound(b[j], M) + ub), doc[j]) < thr))
+            live &= ~(1u << j);
+        live = park_deferred(sh, doc, s0, live, kDeferNeed1, lane);
+        if (!__any(live != 0)) break;
+      }
       float sc[kItems];
       probe_list<kItems, kF>(ix, pd, terms + i, doc, live, qwt[i], qwn[i], sh.cache, sh.cache + 256, sc);
       // Intersection::score = left + right + (0.0 + others...)
@@ -954,33 +1041,10 @@ __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPl
           if ((live & (1u << j)) && make_key(inflate_bound(s0[j] + acc_o[j] + ub), doc[j]) < thr)
             live &= ~(1u << j);
       }
-      if (i == 1 && defer) {
-        // park this wave's survivors in the queue when they fit (slots reserved
-        // with one LDS atomic); a wave that does not fit probes on inline
-        uint32_t nw = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < kItems; ++j) nw += (uint32_t)__popcll(__ballot((live >> j) & 1u));
-        if (nw) {
-          uint32_t base = 0;
-          if (lane == 0) base = atomicAdd(&sh.n_dq, nw);
-          base = (uint32_t)__shfl((int)base, 0, 64);
-          if (base + nw <= kDeferCap) {
-            uint32_t at = base;
-#pragma unroll
-            for (uint32_t j = 0; j < kItems; ++j) {
-              const bool b = (live >> j) & 1u;
-              const unsigned long long bal = __ballot(b);
-              if (b)
-                sh.dq[at + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] =
-                    ((uint64_t)doc[j] << 32) | __float_as_uint(s0[j]);
-              at += (uint32_t)__popcll(bal);
-            }
-            live = 0;
-          } else {
-            for (uint32_t x = base + lane; x < kDeferCap; x += 64) sh.dq[x] = kDeferNone;  // the part that fit
-          }
-        }
-      }
+      // park this wave's survivors (doc, left + right) in the queue when they fit; a
+      // wave that does not fit -- or that overflowed out of the bound stage --
+      // probes on inline
+      if (i == 1 && defer && !bstage) live = park_deferred(sh, doc, s0, live, 0u, lane);
       if (i <= 2) FG_COUNT(1 + i, live);
     }
     tp1 = FG_NOW();
@@ -2675,6 +2739,48 @@ hipError_t launch_doctab(const DocTabJob& j, uint32_t grid_cap, hipStream_t s) {
   // (p + gridDim.x * kThreads stays below 2^32: df < 2^31, at most 2^15 workgroups per table)
   const uint32_t gx = std::min<uint32_t>((dfmax + kThreads - 1) / kThreads, std::max<uint32_t>(1u, std::min(cap, 0x8000u) / j.n));
   k_dtab_scatter<<<dim3(gx, j.n), kThreads, 0, s>>>(j);
+  return hipGetLastError();
+}
+
+// Snapshot build: the one-byte bound tables of the dense terms (DevIndex::dtab8,
+// DocTab8Job), after k_bucket (the term maxima).  k_dtab8_fill writes 0 (absent)
+// over every table, four bytes per store (a table is a multiple of 128 B);
+// k_dtab8_scatter then puts quant8(score, the term's maximum) at each posting's
+// doc: q8_bound of it is >= the score bit for bit (quant8 corrects itself).  A
+// present posting must never read as absent: scores are > 0, so quant8 gives
+// >= 1 already, and the byte is clamped to >= 1 all the same.  Byte stores of
+// distinct docs never share an address; plain vector stores, in steps of the grid.
+__global__ __launch_bounds__(kThreads) void k_dtab8_fill(uint32_t* __restrict__ tab, uint64_t n4) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (uint64_t)gridDim.x * kThreads)
+    tab[i] = 0u;
+}
+
+__global__ __launch_bounds__(kThreads) void k_dtab8_scatter(DocTab8Job j) {
+  const uint32_t t = blockIdx.y;
+  const uint64_t off = j.off[t];
+  const uint32_t df = j.df[t];
+  const float M = j.tmaxs[j.term[t]];
+  uint8_t* __restrict__ tab = j.tab + (uint64_t)t * j.stride;
+  for (uint32_t p = blockIdx.x * kThreads + threadIdx.x; p < df; p += gridDim.x * kThreads) {
+    const uint32_t d = j.doc[off + p];
+    if (d < j.stride) tab[d] = (uint8_t)max(1u, quant8(j.psc[off + p], M));
+  }
+}
+
+hipError_t launch_doctab8(const DocTab8Job& j, uint32_t grid_cap, hipStream_t s) {
+  if (j.n == 0 || j.stride == 0) return hipSuccess;
+  if (j.n > kDocTabMax || (j.stride & 127u)) return hipErrorInvalidValue;
+  const uint32_t cap = grid_cap ? grid_cap : 0x10000u;
+  const uint64_t n4 = (uint64_t)j.n * j.stride / 4;
+  k_dtab8_fill<<<(uint32_t)std::min<uint64_t>((n4 + kThreads - 1) / kThreads, cap), kThreads, 0, s>>>(
+      reinterpret_cast<uint32_t*>(j.tab), n4);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  uint32_t dfmax = 1;
+  for (uint32_t i = 0; i < j.n; ++i) dfmax = std::max(dfmax, j.df[i]);
+  // (p + gridDim.x * kThreads stays below 2^32: df < 2^31, at most 2^15 workgroups per table)
+  const uint32_t gx = std::min<uint32_t>((dfmax + kThreads - 1) / kThreads, std::max<uint32_t>(1u, std::min(cap, 0x8000u) / j.n));
+  k_dtab8_scatter<<<dim3(gx, j.n), kThreads, 0, s>>>(j);
   return hipGetLastError();
 }
 

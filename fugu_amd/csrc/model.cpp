@@ -27,8 +27,9 @@ using fgh::parallel_dynamic;
 
 namespace {
 
-enum Arr : uint32_t { A_DOC, A_TFN, A_RANK, A_SRANK, A_SRANKW, A_DIR, A_BMAX, A_TMAX, A_TDIR, A_CMAX, A_TSUB, A_DTAB, A_N };
+enum Arr : uint32_t { A_DOC, A_TFN, A_RANK, A_SRANK, A_SRANKW, A_DIR, A_BMAX, A_TMAX, A_TDIR, A_CMAX, A_TSUB, A_DTAB, A_DTAB8, A_N };
 constexpr uint64_t kLine = 128;
+constexpr uint32_t kTraceClauses = 4;  // FUGU_MODEL_TRACE splits the lines by clause position 0, 1, 2, >= 3
 constexpr float kInflate = 1.00000762939453125f;  // kernels.hip inflate_bound: 1 + 2^-17
 
 // host view of one snapshot: the postings (host copy) and the device tables the
@@ -41,6 +42,7 @@ struct Snap {
   const uint32_t* doc = nullptr;
   uint32_t pw = 2;  // payload bytes per posting the kernels load (tfn, + tfn_name)
   uint32_t tab_lead = 0;  // the plans' score-table rule (fg::probe_uses_table)
+  uint32_t tab8_lead = 0;  // ... and their bound-table rule (fg::probe_uses_bound)
   std::vector<float> psc, tmax, bmax, cmax;
   std::vector<uint64_t> tsub, srank;  // srank: the sparse rank block entries
   std::vector<uint32_t> dir_off, toff, coff;
@@ -123,6 +125,8 @@ struct Snap {
     bytes[A_TSUB] = 8ull * tsub.size();
     bytes[A_DTAB] = x->dtab_bytes;
     tab_lead = fgh::doctab_lead();
+    bytes[A_DTAB8] = x->dtab8_bytes;
+    tab8_lead = fgh::doctab8_lead();
     return FG_OK;
   }
   // the loads of a rank-kind probe of doc d (plain: the word; sparse: the
@@ -154,10 +158,13 @@ struct Snap {
 // of one line are recorded once (the set of lines is what counts)
 struct Acc {
   std::vector<uint64_t> lines;
+  std::vector<uint64_t> clines;  // FUGU_MODEL_TRACE: the same lines tagged with their clause position
+  bool by_clause = false;
   uint64_t last[fg::kMaxTerms + 1][A_N];
   double stream = 0, probe = 0, loads = 0;
   void reset() {
     lines.clear();
+    clines.clear();
     std::memset(last, 0xFF, sizeof last);
     stream = probe = loads = 0;
   }
@@ -165,6 +172,7 @@ struct Acc {
     if (last[s][a] == l) return;
     last[s][a] = l;
     lines.push_back(((uint64_t)a << 56) | l);
+    if (by_clause) clines.push_back(((uint64_t)std::min(s, kTraceClauses - 1) << 60) | ((uint64_t)a << 52) | l);
   }
   // one load of nb bytes at byte offset `at` of array a (stream s)
   void gather(uint32_t s, Arr a, uint64_t at, uint32_t nb, double& cat) {
@@ -195,6 +203,33 @@ struct Union {
     }
   }
   std::atomic<uint64_t> qlines[A_N];  // per-query distinct lines summed, by array
+  // FUGU_MODEL_TRACE: the same two figures by (clause position, array)
+  std::vector<std::atomic<uint64_t>> cbm[kTraceClauses][A_N];
+  std::atomic<uint64_t> cq[kTraceClauses][A_N];
+  void init_by_clause(const Snap& s) {
+    for (uint32_t c = 0; c < kTraceClauses; ++c)
+      for (uint32_t a = 0; a < A_N; ++a) {
+        cq[c][a].store(0, std::memory_order_relaxed);
+        std::vector<std::atomic<uint64_t>> v((s.bytes[a] / kLine + 2 + 63) / 64);
+        for (auto& w : v) w.store(0, std::memory_order_relaxed);
+        cbm[c][a].swap(v);
+      }
+  }
+  void add_by_clause(std::vector<uint64_t>& lines) {
+    std::sort(lines.begin(), lines.end());
+    lines.erase(std::unique(lines.begin(), lines.end()), lines.end());
+    for (uint64_t x : lines) {
+      const uint32_t c = (uint32_t)(x >> 60), a = (uint32_t)(x >> 52) & 0xFFu;
+      const uint64_t l = x & ((1ull << 52) - 1);
+      cq[c][a].fetch_add(1, std::memory_order_relaxed);
+      if ((l >> 6) < cbm[c][a].size()) cbm[c][a][l >> 6].fetch_or(1ull << (l & 63), std::memory_order_relaxed);
+    }
+  }
+  uint64_t count_by_clause(uint32_t c, uint32_t a) const {
+    uint64_t n = 0;
+    for (const auto& w : cbm[c][a]) n += (uint64_t)__builtin_popcountll(w.load(std::memory_order_relaxed));
+    return n;
+  }
   // sorts / dedups the query's lines; returns how many are distinct
   uint64_t add(std::vector<uint64_t>& lines) {
     std::sort(lines.begin(), lines.end());
@@ -312,10 +347,31 @@ uint64_t model_conj(const Snap& S, const uint32_t* terms, uint32_t m, bool has_t
       const uint32_t sl = fgh::doctab_slot(*ix, terms[j]);
       if (sl && fg::probe_uses_table(ix->n_docs, S.len(terms[j]), df, S.tab_lead)) tab[j] = sl;
     }
+  // the bound table in front of the first probed list (plan.cpp: probe_desc_bound;
+  // kernels.hip: the bound stage, only with a threshold): one byte of a 128-doc
+  // line per candidate; the survivors are probed exactly, as before
+  uint32_t tab8 = 0;
+  float M8 = 0.0f;
+  if (ix->same_stats && !ix->dtab8_map.empty() && m >= 3 && thk) {
+    const uint32_t sl = fgh::doctab8_slot(*ix, terms[1]);
+    M8 = ix->tmaxs[terms[1]];
+    const uint32_t k1 = fg::meta_slot(ix->tmeta[terms[1]]) ? 0u : fg::kPdDir;
+    if (sl && M8 > 0.0f && !k1 && fg::probe_uses_bound(ix->n_docs, S.len(terms[1]), df, S.tab8_lead)) tab8 = sl;
+  }
+  const uint32_t* l1 = m > 1 ? S.list(terms[1]) : nullptr;
+  const uint64_t n1 = m > 1 ? S.len(terms[1]) : 0, base1 = m > 1 ? ix->off[terms[1]] : 0;
+  uint64_t c1 = 0;  // list 1's cursor (the lead docs ascend)
   for (uint64_t p = 0; p < df; ++p) {
     const uint32_t d = ld[p];
     float s0 = S.psc[base + p], acc = 0.0f;
     if (thk && key_of((s0 + qub[1]) * kInflate, d) < thk) continue;
+    if (tab8) {
+      A.gather(1, A_DTAB8, (uint64_t)(tab8 - 1) * ix->d.dtab8_stride + d, 1, A.probe);
+      while (c1 < n1 && l1[c1] < d) ++c1;
+      if (c1 >= n1 || l1[c1] != d) continue;  // byte 0: absent
+      const float bnd = fg::q8_bound(std::max(1u, fg::quant8(S.psc[base1 + c1], M8)), M8);
+      if (key_of((s0 + bnd + qub[2]) * kInflate, d) < thk) continue;
+    }
     bool ok = true;
     for (uint32_t j = 1; j < m && ok; ++j) {
       const float sc = probe_term(S, A, j, terms[j], d, A.probe, tab[j]);
@@ -565,11 +621,14 @@ int fg_model_batch(const fg_index* ix, const fg_query_batch* q, uint32_t k, cons
   if (int rc = S.load(ix)) return rc;
   Union U;
   U.init(S);
+  const bool trace = getenv("FUGU_MODEL_TRACE") != nullptr;
+  if (trace) U.init_by_clause(S);
   const uint32_t nq = q->n_queries;
   std::vector<double> st(nq, 0.0), pr(nq, 0.0), ou(nq, 0.0), ld(nq, 0.0), ql(nq, 0.0), kp(nq, 0.0);
   std::atomic<bool> bad{false};
   parallel_dynamic(nq, hw_threads(0), 1, [&](int, uint32_t qb, uint32_t qe) {
     Acc A;
+    A.by_clause = trace;
     for (uint32_t i = qb; i < qe; ++i) {
       A.reset();
       const uint32_t b = q->q_off[i], e = q->q_off[i + 1];
@@ -606,6 +665,7 @@ int fg_model_batch(const fg_index* ix, const fg_query_batch* q, uint32_t k, cons
       ld[i] = A.loads;
       kp[i] = (double)kept;
       ql[i] = (double)U.add(A.lines);
+      if (trace) U.add_by_clause(A.clines);
     }
   });
   if (bad) return fail(FG_EINVAL, "bad query batch (the model covers pure Must / pure Should queries)");
@@ -626,11 +686,17 @@ int fg_model_batch(const fg_index* ix, const fg_query_batch* q, uint32_t k, cons
   }
   out->alg_bytes = out->stream_bytes + out->probe_bytes + out->output_bytes;
   out->line_bytes = (double)kLine * (double)U.count();
-  if (getenv("FUGU_MODEL_TRACE")) {  // the line floor and the per-query line sum, by array
-    static const char* names[A_N] = {"doc", "tfn", "rank", "srank", "srankw", "dir", "bmax", "tmax", "tdir", "cmax", "tsub", "dtab"};
+  if (trace) {  // the line floor and the per-query line sum, by array, then by (clause position, array)
+    static const char* names[A_N] = {"doc", "tfn", "rank", "srank", "srankw", "dir", "bmax", "tmax", "tdir", "cmax", "tsub", "dtab", "dtab8"};
     for (uint32_t a = 0; a < A_N; ++a)
       fprintf(stderr, "[fg model] %-6s floor %8.3f GB  per-query sum %8.3f GB\n", names[a],
               (double)kLine * (double)U.count(a) * 1e-9, (double)kLine * (double)U.qlines[a].load() * 1e-9);
+    for (uint32_t c = 0; c < kTraceClauses; ++c)
+      for (uint32_t a = 0; a < A_N; ++a)
+        if (U.cq[c][a].load())
+          fprintf(stderr, "[fg model] clause %u%s %-6s floor %8.3f GB  per-query sum %8.3f GB\n", c,
+                  c + 1 == kTraceClauses ? "+" : " ", names[a], (double)kLine * (double)U.count_by_clause(c, a) * 1e-9,
+                  (double)kLine * (double)U.cq[c][a].load() * 1e-9);
   }
   return FG_OK;
 }

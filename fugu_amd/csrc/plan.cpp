@@ -162,7 +162,7 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
   const uint32_t nq = q->n_queries;
   const uint64_t N = ix->n_docs;
   const bool disj = q->mode == FG_MODE_OR;
-  const uint32_t tab_lead = fgh::doctab_lead();
+  const uint32_t tab_lead = fgh::doctab_lead(), tab8_lead = fgh::doctab8_lead();
   h.clear();
   const size_t nqt = (size_t)nq * fg::kMaxTerms;
   for (auto* v : {&h.q_m, &h.lead}) v->assign(nq, 0);
@@ -423,6 +423,11 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
         h.q_probe[row + j] =
             fg::probe_desc(ix->d, pt, j == 0, qtime, j + 1 < mt ? h.q_ub[row + j + 1] : 0.0f, lead_df, tab_lead);
       }
+      // the first probed list's one-byte bound table, for a query that takes
+      // k_conj's deferred path (>= 3 unfiltered Must lists and nothing else)
+      if (!qtime && !ix->dtab8_map.empty() && mt >= 3 && nm == mt && flt == 0xFFFFFFFFu)
+        fg::probe_desc_bound(ix->d, h.q_probe[row], h.q_probe[row + 1], fgh::doctab8_slot(*ix, qt[1]), ix->tmaxs[qt[1]],
+                             true, qtime, ix->off[qt[1] + 1] - ix->off[qt[1]], lead_df, tab8_lead);
     }
     // one list: its K'-th best alive score (the smallest stored K' >= k) bounds
     // the query's k-th best from below, so k_conj starts from that threshold and

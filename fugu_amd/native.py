@@ -60,7 +60,7 @@ EXPORTS = (
     "fg_ctx_peer_access", "fg_plan_link", "fg_bytes_model_or", "fg_plan_create_multi", "fg_plan_execute_merged", "fg_index_term_kth",
     "fg_model_batch", "fg_abi_version", "fg_index_term_ladder", "fg_kth_floor_combine", "fg_index_set_kth_floor",
     "fg_plan_set_peers", "fg_plan_ipc_export", "fg_plan_set_ipc_peers", "fg_plan_reset",
-    "fg_count_batch", "fg_count_trace", "fg_index_doctab_get",
+    "fg_count_batch", "fg_count_trace", "fg_index_doctab_get", "fg_index_doctab8_get",
 )
 LADDER_KS = (1, 2, 3, 5, 10, 13, 20, 25, 50, 100, 125, 250, 500, 1000)  # FG_LADDER_LEVELS ranks
 KTH_KS = (1, 10, 20, 100, 1000)  # fg_index_term_kth / fg_index_set_kth_floor ranks
@@ -163,6 +163,8 @@ _sig("fg_thread_background", C.c_int, C.c_int)
 _sig("fg_index_release", C.c_int, _p)
 _sig("fg_index_stats_get", C.c_int, _p, C.POINTER(IndexStats))
 _sig("fg_index_doctab_get", C.c_int, _p, _u32p, _u64p)
+if hasattr(_lib, "fg_index_doctab8_get"):  # (FG_ABI_VERSION did not move with it: an A/B library built before it lacks it)
+    _sig("fg_index_doctab8_get", C.c_int, _p, _u32p, _u64p)
 _sig("fg_index_df", C.c_uint64, _p, C.c_int, C.c_uint32)
 _sig("fg_index_bm25", C.c_int, _p, C.c_uint32, _f32p, _f32p, _f32p)
 _sig("fg_plan_create", C.c_int, _p, C.POINTER(QueryBatch), C.c_uint32, C.POINTER(_p))
@@ -497,6 +499,14 @@ class Index:
         """(terms with a doc-indexed score table, the tables' device bytes): fg_index_doctab_get."""
         n, b = C.c_uint32(0), C.c_uint64(0)
         _check(_lib.fg_index_doctab_get(self._h, C.byref(n), C.byref(b)))
+        return int(n.value), int(b.value)
+
+    def bound_tables(self):
+        """(terms with a one-byte bound table, the tables' device bytes): fg_index_doctab8_get."""
+        n, b = C.c_uint32(0), C.c_uint64(0)
+        if not hasattr(_lib, "fg_index_doctab8_get"):
+            return 0, 0
+        _check(_lib.fg_index_doctab8_get(self._h, C.byref(n), C.byref(b)))
         return int(n.value), int(b.value)
 
     def df(self, term: int, field: int = -1) -> int:

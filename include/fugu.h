@@ -241,6 +241,11 @@ int fg_index_stats_get(const fg_index* ix, fg_index_stats* out);
  * its rescores and counted in device_bytes): how many terms have one and the
  * tables' device bytes.  Either pointer may be NULL. */
 int fg_index_doctab_get(const fg_index* ix, uint32_t* n_terms, uint64_t* bytes);
+/* The snapshot's one-byte bound tables (per dense term an upper bound of its
+ * build-time score at every doc, 0 where absent: conjunctions of >= 3 lists test
+ * it before the exact probe of their second list; shared with its rescores and
+ * counted in device_bytes): terms and device bytes.  Either pointer may be NULL. */
+int fg_index_doctab8_get(const fg_index* ix, uint32_t* n_terms, uint64_t* bytes);
 /* doc_freq of `term` in `field` (tantivy Searcher::doc_freq; FG_FIELD_FACET:
  * a facet term), and the merged (text U name) posting-list length when field < 0. */
 uint64_t fg_index_df(const fg_index* ix, int field, uint32_t term);
