@@ -1261,6 +1261,169 @@ int attach_positions(fg_index* ix, const fg_docs_input* in) {
   return FG_OK;
 }
 
+// fg_index_build_global's first checks of `in` and g (after the NULL arguments;
+// they need no context): fg_index_build_positional runs them before its own
+int index_input_head(const fg_index_input* in, const fg_global_stats* g) {
+  if (!global_stats_ok(g, in->n_docs)) return fail(FG_EINVAL, "bad global statistics");
+  if (in->n_docs == 0 || in->n_docs >= 0x7FFFFFFFu) return fail(FG_EINVAL, "n_docs out of range");
+  if (in->term_off[0] != 0) return fail(FG_EINVAL, "term_off[0] must be 0");
+  if (in->term_off[in->n_terms] > 0 && (!in->doc || (!in->tf_text && !in->tf_name)))
+    return fail(FG_EINVAL, "postings without doc ids or term frequencies");
+  return FG_OK;
+}
+
+// ---------------------------------------------------------------- forward index from positional postings
+// fg_index_build_positional's checks of `pos` against the postings' tf: host only
+// (no context, no device), each message names the field.
+int check_positions_input(const fg_index_input* in, const fg_positions_input* pos) {
+  const uint64_t P = in->term_off[in->n_terms];
+  uint64_t st = 0, sn = 0;
+  if (in->tf_text)
+    for (uint64_t p = 0; p < P; ++p) st += in->tf_text[p];
+  if (in->tf_name)
+    for (uint64_t p = 0; p < P; ++p) sn += in->tf_name[p];
+  if (pos->n_text_pos && !pos->text_pos) return fail(FG_EINVAL, "text positions: text_pos is NULL with n_text_pos = %llu", (unsigned long long)pos->n_text_pos);
+  if (pos->n_text_pos != st)
+    return fail(FG_EINVAL, "text positions: n_text_pos = %llu, the postings' tf_text sum to %llu",
+                (unsigned long long)pos->n_text_pos, (unsigned long long)st);
+  if (pos->n_name_pos && !pos->name_pos) return fail(FG_EINVAL, "name positions: name_pos is NULL with n_name_pos = %llu", (unsigned long long)pos->n_name_pos);
+  if (sn && !pos->name_pos) return fail(FG_EINVAL, "name positions: the postings have tf_name > 0 but name_pos is NULL");
+  if (pos->n_name_pos != sn)
+    return fail(FG_EINVAL, "name positions: n_name_pos = %llu, the postings' tf_name sum to %llu",
+                (unsigned long long)pos->n_name_pos, (unsigned long long)sn);
+  return FG_OK;
+}
+
+// One field's forward index built on the device from the field's
+// tf per posting (tf may be nullptr: all 0) and its positions in posting order,
+// over the snapshot's uploaded postings (ix->d.doc / off, k_score's chunk
+// tables).  fwd_off and fwd go into the structure's allocations; the field's
+// temporaries (tf, positions, posting offsets, row lengths) are one
+// stream-ordered block freed when the field is done.  Two read-backs: the row
+// total with the error word (fwd is allocated by it), then the error word with
+// the count of filled entries.
+int fwd_from_postings(fg_index* ix, const char* field, const uint16_t* tf, const uint32_t* pos, uint64_t n_pos,
+                      const uint64_t** d_off, const uint32_t** d_fwd, uint64_t* bytes) {
+  static_assert(fg::kFwdSlices == FG_FWD_SCAN_SLICES, "fugu.h FG_FWD_SCAN_SLICES");
+  const uint64_t P = ix->n_postings, N = ix->n_docs;
+  Parts L;
+  const Parts::P p_tf = L.add(2 * P), p_pos = L.add(4 * n_pos), p_poff = L.add(8 * (P + 1)), p_len = L.add(4 * N),
+                 p_part = L.add(8ull * (fg::kFwdSlices + 1)), p_words = L.add(16);
+  AsyncTmp tmp;
+  if (fgh::dev_malloc_async(&tmp.p, L.total, kBuildStream) != hipSuccess)
+    return fail(FG_EOOM, "forward index (%s): hipMallocAsync(%zu) failed", field, L.total);
+  char* t = static_cast<char*>(tmp.p);
+  void* q = nullptr;
+  const size_t off_b = 8 * (N + 1);
+  if (fgh::dev_malloc(&q, off_b) != hipSuccess) return fail(FG_EOOM, "forward index (%s): hipMalloc(%zu) failed", field, off_b);
+  ix->smem->ptrs.push_back(q);
+  *bytes += off_b;
+  // (events only under FUGU_BUILD_TRACE: the upload, then the 3 + 3 spans of the launches)
+  hipEvent_t ev[8] = {};
+  struct EvGuard {
+    hipEvent_t* e;
+    ~EvGuard() { for (int i = 0; i < 8; ++i) if (e[i]) (void)hipEventDestroy(e[i]); }
+  } ev_guard{ev};
+  const bool timed = g_bt.on;
+  if (timed)
+    for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+  fg::FwdJob j{};
+  j.doc = ix->d.doc;
+  j.off = ix->d.off;
+  j.tf = reinterpret_cast<const uint16_t*>(t + p_tf.off);
+  j.pos = reinterpret_cast<const uint32_t*>(t + p_pos.off);
+  j.poff = reinterpret_cast<uint64_t*>(t + p_poff.off);
+  j.len = reinterpret_cast<uint32_t*>(t + p_len.off);
+  j.part = reinterpret_cast<uint64_t*>(t + p_part.off);
+  j.err = reinterpret_cast<uint32_t*>(t + p_words.off);
+  j.filled = reinterpret_cast<unsigned long long*>(t + p_words.off + 8);
+  j.fwd_off = static_cast<uint64_t*>(q);
+  j.n_post = P;
+  j.n_docs = (uint32_t)N;
+  j.sc_tf = ix->d_sc_tf;
+  j.sc_tl = ix->d_sc_tl;
+  j.sc_e0 = ix->d_sc_e0;
+  j.sc_e1 = ix->d_sc_e1;
+  j.n_chunks = ix->n_scb;
+  j.grid_cap = fgh::bg_grid_cap(ix->dev);
+  const auto t_up = std::chrono::steady_clock::now();
+  if (P) {
+    if (tf) HIPCHK(hipMemcpyAsync(t + p_tf.off, tf, 2 * P, hipMemcpyHostToDevice, kBuildStream));
+    else HIPCHK(hipMemsetAsync(t + p_tf.off, 0, 2 * P, kBuildStream));
+  }
+  if (n_pos) HIPCHK(hipMemcpyAsync(t + p_pos.off, pos, 4 * n_pos, hipMemcpyHostToDevice, kBuildStream));
+  HIPCHK(hipMemsetAsync(j.len, 0, 4 * N, kBuildStream));
+  HIPCHK(hipMemsetAsync(j.err, 0, 16, kBuildStream));
+  double up_ms = 0;
+  if (timed) {
+    HIPCHK(hipStreamSynchronize(kBuildStream));
+    up_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_up).count();
+  }
+  HIPCHK(fg::launch_fwd_rows(j, kBuildStream, timed ? ev : nullptr));
+  uint64_t total = 0;
+  uint32_t err = 0;
+  HIPCHK(hipMemcpyAsync(&total, j.fwd_off + N, 8, hipMemcpyDeviceToHost, kBuildStream));
+  HIPCHK(hipMemcpyAsync(&err, j.err, 4, hipMemcpyDeviceToHost, kBuildStream));
+  HIPCHK(hipStreamSynchronize(kBuildStream));
+  auto refuse = [&](uint32_t e) {
+    if (e & fg::kFwdErrNone) return fail(FG_EINVAL, "%s positions: a position of 0xFFFFFFFF", field);
+    if (e & fg::kFwdErrOrder) return fail(FG_EINVAL, "%s positions: a posting's positions do not strictly ascend", field);
+    return fail(FG_EINVAL, "%s positions: a position past its doc's last one", field);
+  };
+  if (err) return refuse(err);
+  const size_t fwd_b = std::max<size_t>(4 * total, 16);
+  if (total > (~size_t(0) >> 3) || fgh::dev_malloc(&q, fwd_b) != hipSuccess)
+    return fail(FG_EOOM, "forward index (%s): hipMalloc of %llu positions failed", field, (unsigned long long)total);
+  ix->smem->ptrs.push_back(q);
+  *bytes += fwd_b;
+  j.fwd = static_cast<uint32_t*>(q);
+  j.n_fwd = total;
+  HIPCHK(fg::launch_fwd_fill(j, kBuildStream, timed ? ev + 4 : nullptr));
+  unsigned long long filled = 0;
+  HIPCHK(hipMemcpyAsync(&err, j.err, 4, hipMemcpyDeviceToHost, kBuildStream));
+  HIPCHK(hipMemcpyAsync(&filled, j.filled, 8, hipMemcpyDeviceToHost, kBuildStream));
+  HIPCHK(hipStreamSynchronize(kBuildStream));
+  if (err) return refuse(err);
+  if (filled != n_pos)
+    return fail(FG_EINVAL, "%s positions: two postings claim the same (doc, position) (%llu of %llu positions distinct)", field,
+                filled, (unsigned long long)n_pos);
+  if (timed) {
+    float ms[6] = {};
+    for (int i = 0; i < 3; ++i) {
+      (void)hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
+      (void)hipEventElapsedTime(&ms[3 + i], ev[4 + i], ev[5 + i]);
+    }
+    fprintf(stderr,
+            "[fg build] forward index (%s): %llu postings, %llu positions, %llu row entries; ms: upload %.3f, "
+            "scan_tf %.3f, k_fwd_len %.3f, scan_len %.3f, k_fwd_fill %.3f, k_fwd_scatter %.3f, k_fwd_check %.3f\n",
+            field, (unsigned long long)P, (unsigned long long)n_pos, (unsigned long long)total, up_ms, ms[0], ms[1], ms[2],
+            ms[3], ms[4], ms[5]);
+  }
+  *d_off = j.fwd_off;
+  *d_fwd = j.fwd;
+  return FG_OK;
+}
+
+// The forward index of a snapshot built from positional postings
+// (fg_index_build_positional), beside attach_positions: the same arrays, built by
+// the k_fwd_* kernels from the positions of the caller's postings.  The two
+// fields one after the other, so the peak is one field's temporaries.  `name`
+// only when the snapshot has name payloads and the postings any name position.
+int attach_positions_postings(fg_index* ix, const fg_index_input* in, const fg_positions_input* pos) {
+  HIPCHK(hipSetDevice(ix->dev));
+  uint64_t bytes = 0;
+  int rc = fwd_from_postings(ix, "text", in->tf_text, pos->text_pos, pos->n_text_pos, &ix->d.fwd_off, &ix->d.fwd, &bytes);
+  if (!rc && ix->d.tfn_name && pos->n_name_pos)
+    rc = fwd_from_postings(ix, "name", in->tf_name, pos->name_pos, pos->n_name_pos, &ix->d.fwd_off_name, &ix->d.fwd_name,
+                           &bytes);
+  ix->struct_bytes += bytes;
+  ix->device_bytes += bytes;
+  if (rc) return rc;
+  ix->has_positions = true;
+  g_bt.mark("forward index (device)");
+  return FG_OK;
+}
+
 // one snapshot rescored (fg_index_rescore); wts: shared precomputed weights or
 // nullptr.  Host only: tantivy scores at query time (src/db/search.rs:162), so
 // a new Searcher's statistics need no device work -- the snapshot shares every
@@ -1449,12 +1612,8 @@ int fg_index_build(fg_ctx* ctx, int dev, const fg_index_input* in, fg_index** ou
 
 int fg_index_build_global(fg_ctx* ctx, int dev, const fg_index_input* in, const fg_global_stats* g, fg_index** out) {
   if (!ctx || !in || !out || !in->term_off || !in->fn_text) return fail(FG_EINVAL, "bad arguments");
-  if (!global_stats_ok(g, in->n_docs)) return fail(FG_EINVAL, "bad global statistics");
+  if (int rc = index_input_head(in, g)) return rc;
   g_bt.start();
-  if (in->n_docs == 0 || in->n_docs >= 0x7FFFFFFFu) return fail(FG_EINVAL, "n_docs out of range");
-  if (in->term_off[0] != 0) return fail(FG_EINVAL, "term_off[0] must be 0");
-  if (in->term_off[in->n_terms] > 0 && (!in->doc || (!in->tf_text && !in->tf_name)))
-    return fail(FG_EINVAL, "postings without doc ids or term frequencies");
   if (std::find(ctx->devs.begin(), ctx->devs.end(), dev) == ctx->devs.end())
     return fail(FG_EINVAL, "device %d not in context", dev);
   HostPostings hp;
@@ -1504,6 +1663,46 @@ int fg_index_build_global(fg_ctx* ctx, int dev, const fg_index_input* in, const 
   }
   if (int rc = check_global_df(g, hp, "segment")) return rc;
   return finish_index(dev, hp, true, out, g);
+}
+
+int fg_index_build_positional(fg_ctx* ctx, int dev, const fg_index_input* in, const fg_positions_input* pos,
+                              const fg_global_stats* g, fg_index** out) {
+  // the checks of `in` that need no context, then those of `pos`: all host work, before the device is touched
+  if (!in || !out || !in->term_off || !in->fn_text) return fail(FG_EINVAL, "bad arguments");
+  if (int rc = index_input_head(in, g)) return rc;
+  if (!pos) return fail(FG_EINVAL, "no positions given (fg_index_build_global builds a snapshot without them)");
+  if (int rc = check_positions_input(in, pos)) return rc;
+  fg_index* ix = nullptr;
+  if (int rc = fg_index_build_global(ctx, dev, in, g, &ix)) return rc;
+  if (int rc = attach_positions_postings(ix, in, pos)) {
+    fg_index_release(ix);
+    return rc;
+  }
+  *out = ix;
+  return FG_OK;
+}
+
+int fg_index_positions_get(const fg_index* ix, int field, uint32_t doc0, uint32_t n_docs, uint64_t* off_out,
+                           uint32_t* tok_out, uint64_t cap, uint64_t* n_tok) {
+  if (!ix || !off_out || !n_tok || (cap && !tok_out)) return fail(FG_EINVAL, "bad arguments");
+  if (field != FG_FIELD_TEXT && field != FG_FIELD_NAME) return fail(FG_EINVAL, "field must be text (0) or name (1)");
+  if (!ix->has_positions) return fail(FG_EINVAL, "snapshot built without positions");
+  const uint64_t* d_off = field == FG_FIELD_TEXT ? ix->d.fwd_off : ix->d.fwd_off_name;
+  const uint32_t* d_fwd = field == FG_FIELD_TEXT ? ix->d.fwd : ix->d.fwd_name;
+  if (!d_off || !d_fwd) return fail(FG_EINVAL, "snapshot has no forward index of field %d", field);
+  if ((uint64_t)doc0 + n_docs > ix->n_docs) return fail(FG_EINVAL, "docs [%u, %u + %u) past the snapshot's %u", doc0, doc0, n_docs, ix->n_docs);
+  HIPCHK(hipSetDevice(ix->dev));
+  HIPCHK(hipMemcpyAsync(off_out, d_off + doc0, 8ull * (n_docs + 1ull), hipMemcpyDeviceToHost, kBuildStream));
+  HIPCHK(hipStreamSynchronize(kBuildStream));
+  const uint64_t first = off_out[0], n = off_out[n_docs] - first;
+  for (uint32_t i = 0; i <= n_docs; ++i) off_out[i] -= first;
+  *n_tok = n;
+  if (n > cap) return fail(FG_EINVAL, "%llu positions, room for %llu", (unsigned long long)n, (unsigned long long)cap);
+  if (n) {
+    HIPCHK(hipMemcpyAsync(tok_out, d_fwd + first, 4 * n, hipMemcpyDeviceToHost, kBuildStream));
+    HIPCHK(hipStreamSynchronize(kBuildStream));
+  }
+  return FG_OK;
 }
 
 int fg_index_rescore(const fg_index* base, const fg_global_stats* g, const uint8_t* deleted, fg_index** out) {

@@ -801,6 +801,49 @@ struct DocTab8Job {
   uint64_t off[kDocTabMax];
 };
 
+// The forward index of ONE field from positional postings (fg_index_build_positional,
+// DESIGN.md §13; k_fwd_*).  posting p of the snapshot (doc[p], CSR by term in off)
+// owns tf[p] consecutive entries of pos from poff[p]: its token positions in the
+// field of its doc.  launch_fwd_rows: poff = exclusive scan of tf, len[d] = the
+// largest claimed position of doc d + 1, fwd_off = exclusive scan of len (its last
+// entry, the row total, is what the host allocates fwd by).  launch_fwd_fill: fwd
+// = kFwdNone everywhere, fwd[fwd_off[doc[p]] + x] = term(p) for every position x
+// of every posting, and filled = the entries of fwd that are not kFwdNone.
+// Invalid input sets bits of *err and stores nothing outside a row.
+constexpr uint32_t kFwdSlices = 1024;  // G: slices of a scan (fugu.h FG_FWD_SCAN_SLICES)
+constexpr uint32_t kFwdShort = 16;     // k_fwd_scatter: a posting of at most this many positions is one lane's loop
+constexpr uint32_t kFwdErrOrder = 1u;  // a posting's positions do not strictly ascend
+constexpr uint32_t kFwdErrNone = 2u;   // a position of kFwdNone
+constexpr uint32_t kFwdErrRow = 4u;    // a position past its doc's row (after one of the above)
+struct FwdJob {
+  const uint32_t* doc;       // [P] DevIndex::doc
+  const uint64_t* off;       // [V+1] DevIndex::off
+  const uint16_t* tf;        // [P] the field's tf (a temporary)
+  const uint32_t* pos;       // [n_pos] the field's positions in posting order (a temporary)
+  uint64_t* poff;            // [P+1] temporary
+  uint32_t* len;             // [N] temporary, zeroed
+  uint64_t* part;            // [kFwdSlices + 1] temporary: a scan's slice sums, then their bases
+  uint32_t* err;             // the error word, zeroed
+  unsigned long long* filled;  // zeroed
+  uint64_t* fwd_off;         // [N+1]
+  uint32_t* fwd;             // [fwd_off[N]] (launch_fwd_fill)
+  uint64_t n_fwd;            // fwd_off[N] (launch_fwd_fill)
+  uint64_t n_post;           // P
+  uint32_t n_docs;
+  // k_score's packed chunks of the postings (ChunkTables): <= kScoreChunk postings of <= kPackTerms term ids each
+  const uint32_t* sc_tf;
+  const uint32_t* sc_tl;
+  const uint64_t* sc_e0;
+  const uint64_t* sc_e1;
+  uint32_t n_chunks;
+  uint32_t grid_cap;         // at most this many workgroups per launch (0: no cap)
+};
+// ev (or nullptr): 4 events each, recorded around launch_fwd_rows' three steps (the
+// scan of tf, k_fwd_len, the scan of len: a scan's three kernels are one span) and
+// around launch_fwd_fill's three kernels
+hipError_t launch_fwd_rows(const FwdJob& j, hipStream_t s, hipEvent_t* ev = nullptr);
+hipError_t launch_fwd_fill(const FwdJob& j, hipStream_t s, hipEvent_t* ev = nullptr);
+
 // kernels.hip entry points (host-callable launchers)
 hipError_t launch_conj(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 // k_disj over the items [first, first + count) of the plan's k_disj range (in

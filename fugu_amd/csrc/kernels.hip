@@ -3243,6 +3243,285 @@ hipError_t launch_copy32(uint32_t* dst, const uint32_t* src, uint64_t n, uint32_
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- forward index from positional postings
+// fg_index_build_positional (FwdJob): the position-addressed
+// forward index k_phrase reads, built from the positions a host's inverted index
+// holds per posting.  Every kernel walks its items in steps of the grid (a
+// background build launches at most FwdJob::grid_cap workgroups); plain vector
+// loads, stores and atomics.
+//
+// The scans (posting offsets from tf, row offsets from the row lengths) run over
+// a FIXED number of slices, kFwdSlices: k_fwd_reduce sums each slice, k_fwd_spine
+// (one workgroup) turns the sums into the slices' bases, k_fwd_prefix scans each
+// slice from its base.  No workgroup waits for another, and any n costs the same
+// three launches.  One kernel of each serves both scans: the items are u16 (in16)
+// or u32 (in32, when in16 is nullptr), a uniform choice.
+__device__ inline uint64_t fwd_item(const uint16_t* in16, const uint32_t* in32, uint64_t i) {
+  return in16 ? (uint64_t)in16[i] : (uint64_t)in32[i];
+}
+
+// v summed over the workgroup (s4: 4 words of LDS, reusable after the call's first barrier)
+__device__ inline uint64_t fwd_block_sum(uint64_t v, uint64_t* s4) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();  // the previous round's reads of s4 are done
+  if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return s4[0] + s4[1] + s4[2] + s4[3];
+}
+
+// the sum of v over the workgroup's threads before this one; *total: over all of them
+__device__ inline uint64_t fwd_block_scan(uint64_t v, uint64_t* s4, uint64_t* total) {
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint64_t inc = v;
+  for (uint32_t o = 1; o < 64; o <<= 1) {
+    const uint64_t u = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += u;
+  }
+  __syncthreads();  // the previous round's reads of s4 are done
+  if (lane == 63) s4[wave] = inc;
+  __syncthreads();
+  uint64_t base = 0, tot = 0;
+  for (uint32_t w = 0; w < kThreads / 64; ++w) {
+    if (w < wave) base += s4[w];
+    tot += s4[w];
+  }
+  *total = tot;
+  return base + inc - v;
+}
+
+// slice s of n items in slices of L: [b, e)
+__device__ inline void fwd_slice(uint32_t s, uint64_t n, uint64_t L, uint64_t* b, uint64_t* e) {
+  const uint64_t lo = (uint64_t)s * L;
+  *b = lo < n ? lo : n;
+  *e = n - *b < L ? n : *b + L;
+}
+
+__global__ __launch_bounds__(kThreads) void k_fwd_reduce(const uint16_t* __restrict__ in16, const uint32_t* __restrict__ in32,
+                                                        uint64_t n, uint64_t L, uint64_t* __restrict__ part) {
+  __shared__ uint64_t s4[kThreads / 64];
+  for (uint32_t s = blockIdx.x; s < kFwdSlices; s += gridDim.x) {
+    uint64_t b, e;
+    fwd_slice(s, n, L, &b, &e);
+    uint64_t v = 0;
+    for (uint64_t i = b + threadIdx.x; i < e; i += kThreads) v += fwd_item(in16, in32, i);
+    v = fwd_block_sum(v, s4);
+    if (threadIdx.x == 0) part[s] = v;
+  }
+}
+
+// one workgroup: part[0 .. kFwdSlices) -> their exclusive prefix, part[kFwdSlices] and *total = the sum
+__global__ __launch_bounds__(kThreads) void k_fwd_spine(uint64_t* __restrict__ part, uint64_t* __restrict__ total) {
+  __shared__ uint64_t s4[kThreads / 64];
+  constexpr uint32_t R = kFwdSlices / kThreads;
+  static_assert(kFwdSlices % kThreads == 0, "k_fwd_spine: whole slices per thread");
+  uint64_t x[R], sum = 0;
+#pragma unroll
+  for (uint32_t r = 0; r < R; ++r) {
+    x[r] = part[threadIdx.x * R + r];
+    sum += x[r];
+  }
+  uint64_t tot;
+  uint64_t run = fwd_block_scan(sum, s4, &tot);
+#pragma unroll
+  for (uint32_t r = 0; r < R; ++r) {
+    part[threadIdx.x * R + r] = run;
+    run += x[r];
+  }
+  if (threadIdx.x == 0) {
+    part[kFwdSlices] = tot;
+    *total = tot;
+  }
+}
+
+// out[i] = the sum of the items before i, for i < n (out[n]: k_fwd_spine's total)
+__global__ __launch_bounds__(kThreads) void k_fwd_prefix(const uint16_t* __restrict__ in16, const uint32_t* __restrict__ in32,
+                                                        uint64_t n, uint64_t L, const uint64_t* __restrict__ part,
+                                                        uint64_t* __restrict__ out) {
+  __shared__ uint64_t s4[kThreads / 64];
+  constexpr uint32_t R = 4;  // consecutive items per thread and round
+  for (uint32_t s = blockIdx.x; s < kFwdSlices; s += gridDim.x) {
+    uint64_t b, e;
+    fwd_slice(s, n, L, &b, &e);
+    uint64_t carry = part[s];
+    for (uint64_t t0 = b; t0 < e; t0 += (uint64_t)kThreads * R) {  // (uniform trip count: barriers inside)
+      const uint64_t i0 = t0 + (uint64_t)threadIdx.x * R;
+      uint64_t x[R], sum = 0;
+#pragma unroll
+      for (uint32_t r = 0; r < R; ++r) {
+        x[r] = i0 + r < e ? fwd_item(in16, in32, i0 + r) : 0ull;
+        sum += x[r];
+      }
+      uint64_t tot;
+      uint64_t run = carry + fwd_block_scan(sum, s4, &tot);
+#pragma unroll
+      for (uint32_t r = 0; r < R; ++r) {
+        if (i0 + r < e) out[i0 + r] = run;
+        run += x[r];
+      }
+      carry += tot;
+    }
+  }
+}
+
+// Row lengths: len[doc] = max over the doc's postings of (last position + 1).  One
+// lane per posting with tf > 0: one atomic per (doc, distinct term), spread over
+// the N words of len.  (doc[p] < n_docs: the host checked the postings.)
+__global__ __launch_bounds__(kThreads) void k_fwd_len(FwdJob j) {
+  for (uint64_t p = (uint64_t)blockIdx.x * kThreads + threadIdx.x; p < j.n_post; p += (uint64_t)gridDim.x * kThreads) {
+    const uint32_t tf = j.tf[p];
+    if (!tf) continue;
+    const uint32_t last = j.pos[j.poff[p] + tf - 1];
+    const uint32_t d = j.doc[p];
+    if (last == kFwdNone) atomicOr(j.err, kFwdErrNone);
+    else if (d < j.n_docs) atomicMax(&j.len[d], last + 1u);
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void k_fwd_fill(uint32_t* __restrict__ fwd, uint64_t n) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kThreads)
+    fwd[i] = kFwdNone;
+}
+
+// one position x (the one before it in its posting: prev, when has_prev) of a
+// posting of term t into the row [base, base + len) of its doc; returns error bits.
+// The store is issued only inside the row: base + len = fwd_off[doc + 1] <= the
+// size of fwd, whatever the positions hold.
+__device__ inline uint32_t fwd_put(uint32_t* __restrict__ fwd, uint64_t base, uint64_t len, uint32_t x, bool has_prev,
+                                   uint32_t prev, uint32_t t) {
+  uint32_t bad = 0;
+  if (x == kFwdNone) bad |= kFwdErrNone;
+  if (has_prev && x <= prev) bad |= kFwdErrOrder;
+  if ((uint64_t)x < len) fwd[base + x] = t;
+  else bad |= kFwdErrRow;
+  return bad;
+}
+
+// The scatter, over k_score's packed chunks of the postings (<= kScoreChunk
+// postings of <= kPackTerms term ids): the chunk's term offsets are staged in
+// LDS and a posting's term is the last of them at or below it (slot_of).  A lane
+// takes a posting; one of at most kFwdShort positions it writes in its own loop,
+// a longer one is compacted by ballot into an LDS list that the workgroup's waves
+// then take one posting each, the lanes striding over its positions: no lane's
+// work grows with tf.
+__global__ __launch_bounds__(kThreads) void k_fwd_scatter(FwdJob j) {
+  __shared__ uint64_t s_off[kPackTerms + 1];
+  __shared__ uint16_t s_q[kScoreChunk];
+  __shared__ uint32_t s_nq;
+  static_assert(kScoreChunk <= 0x10000u, "k_fwd_scatter: a chunk-local posting index is a u16");
+  constexpr uint32_t R = kScoreChunk / kThreads;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t bad = 0;
+  for (uint32_t c = blockIdx.x; c < j.n_chunks; c += gridDim.x) {
+    __syncthreads();  // the previous chunk's LDS reads are done
+    const uint32_t tf0 = j.sc_tf[c], nterm = j.sc_tl[c] - tf0 + 1;
+    const uint64_t e0 = j.sc_e0[c], e1 = j.sc_e1[c];
+    for (uint32_t i = threadIdx.x; i <= nterm && i <= kPackTerms; i += kThreads) s_off[i] = j.off[tf0 + i];
+    if (threadIdx.x == 0) s_nq = 0;
+    __syncthreads();
+    uint32_t tfs[R];
+#pragma unroll
+    for (uint32_t r = 0; r < R; ++r) {
+      const uint64_t p = e0 + r * kThreads + threadIdx.x;
+      tfs[r] = p < e1 ? (uint32_t)j.tf[p] : 0u;
+    }
+    // the long postings into the list (a wave's by one LDS atomic)
+#pragma unroll
+    for (uint32_t r = 0; r < R; ++r) {
+      const bool lng = tfs[r] > kFwdShort;
+      const uint64_t m = __ballot(lng);
+      if (!m) continue;
+      uint32_t at = 0;
+      if (lane == 0) at = atomicAdd(&s_nq, (uint32_t)__popcll(m));
+      at = __shfl(at, 0, 64);
+      if (lng) s_q[at + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(r * kThreads + threadIdx.x);
+    }
+    // the short ones: a lane each
+#pragma unroll
+    for (uint32_t r = 0; r < R; ++r) {
+      const uint32_t tf = tfs[r];
+      if (!tf || tf > kFwdShort) continue;
+      const uint64_t p = e0 + r * kThreads + threadIdx.x;
+      const uint32_t d = j.doc[p];
+      if (d >= j.n_docs) continue;
+      const uint32_t t = tf0 + (nterm == 1 ? 0u : slot_of(s_off, nterm, p));
+      const uint64_t base = j.fwd_off[d], len = j.fwd_off[d + 1] - base, st = j.poff[p];
+      uint32_t prev = 0;
+      for (uint32_t i = 0; i < tf; ++i) {
+        const uint32_t x = j.pos[st + i];
+        bad |= fwd_put(j.fwd, base, len, x, i != 0, prev, t);
+        prev = x;
+      }
+    }
+    __syncthreads();
+    // the long ones: a wave each, the lanes over the posting's positions
+    const uint32_t nq = s_nq;
+    for (uint32_t q = wave; q < nq; q += kThreads / 64) {
+      const uint64_t p = e0 + s_q[q];
+      const uint32_t tf = j.tf[p], d = j.doc[p];
+      if (d >= j.n_docs) continue;
+      const uint32_t t = tf0 + (nterm == 1 ? 0u : slot_of(s_off, nterm, p));
+      const uint64_t base = j.fwd_off[d], len = j.fwd_off[d + 1] - base, st = j.poff[p];
+      for (uint32_t i = lane; i < tf; i += 64) {
+        const uint32_t x = j.pos[st + i];
+        const uint32_t prev = i ? j.pos[st + i - 1] : 0u;
+        bad |= fwd_put(j.fwd, base, len, x, i != 0, prev, t);
+      }
+    }
+  }
+  if (bad) atomicOr(j.err, bad);
+}
+
+// the entries of fwd that hold a term: fewer than the positions given means two
+// postings claimed one slot.  Summed per workgroup, one atomic each.
+__global__ __launch_bounds__(kThreads) void k_fwd_check(const uint32_t* __restrict__ fwd, uint64_t n,
+                                                       unsigned long long* __restrict__ filled) {
+  __shared__ uint64_t s4[kThreads / 64];
+  uint64_t v = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kThreads)
+    v += fwd[i] != kFwdNone;
+  v = fwd_block_sum(v, s4);
+  if (threadIdx.x == 0 && v) atomicAdd(filled, (unsigned long long)v);
+}
+
+// workgroups of a launch over n items of `per` each, at most cap (0: 65536)
+static inline uint32_t fwd_grid(uint64_t n, uint64_t per, uint32_t cap) {
+  const uint64_t want = std::max<uint64_t>(1, (n + per - 1) / per);
+  return (uint32_t)std::min<uint64_t>(want, cap ? cap : 0x10000u);
+}
+
+static hipError_t fwd_scan(const uint16_t* in16, const uint32_t* in32, uint64_t n, uint64_t* part, uint64_t* out,
+                           uint32_t cap, hipStream_t s) {
+  const uint64_t L = std::max<uint64_t>(1, (n + kFwdSlices - 1) / kFwdSlices);
+  const uint32_t g = fwd_grid(kFwdSlices, 1, cap);
+  k_fwd_reduce<<<g, kThreads, 0, s>>>(in16, in32, n, L, part);
+  k_fwd_spine<<<1, kThreads, 0, s>>>(part, out + n);
+  k_fwd_prefix<<<g, kThreads, 0, s>>>(in16, in32, n, L, part, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_fwd_rows(const FwdJob& j, hipStream_t s, hipEvent_t* ev) {
+  if (ev) (void)hipEventRecord(ev[0], s);
+  hipError_t e = fwd_scan(j.tf, nullptr, j.n_post, j.part, j.poff, j.grid_cap, s);
+  if (e != hipSuccess) return e;
+  if (ev) (void)hipEventRecord(ev[1], s);
+  if (j.n_post) k_fwd_len<<<fwd_grid(j.n_post, kThreads, j.grid_cap), kThreads, 0, s>>>(j);
+  if (ev) (void)hipEventRecord(ev[2], s);
+  e = fwd_scan(nullptr, j.len, j.n_docs, j.part, j.fwd_off, j.grid_cap, s);
+  if (ev) (void)hipEventRecord(ev[3], s);
+  return e;
+}
+
+hipError_t launch_fwd_fill(const FwdJob& j, hipStream_t s, hipEvent_t* ev) {
+  if (ev) (void)hipEventRecord(ev[0], s);
+  if (j.n_fwd) k_fwd_fill<<<fwd_grid(j.n_fwd, kThreads * 8, j.grid_cap), kThreads, 0, s>>>(j.fwd, j.n_fwd);
+  if (ev) (void)hipEventRecord(ev[1], s);
+  if (j.n_chunks && j.n_fwd) k_fwd_scatter<<<fwd_grid(j.n_chunks, 1, j.grid_cap), kThreads, 0, s>>>(j);
+  if (ev) (void)hipEventRecord(ev[2], s);
+  if (j.n_fwd) k_fwd_check<<<fwd_grid(j.n_fwd, kThreads * 8, j.grid_cap), kThreads, 0, s>>>(j.fwd, j.n_fwd, j.filled);
+  if (ev) (void)hipEventRecord(ev[3], s);
+  return hipGetLastError();
+}
+
 hipError_t launch_merge(uint32_t n_shards, uint32_t n_queries, uint32_t k, const float* score, const uint32_t* doc,
                         const uint32_t* n, float* out_score, uint32_t* out_doc, uint32_t* out_shard, uint32_t* out_n,
                         hipStream_t s) {

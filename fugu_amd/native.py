@@ -61,11 +61,14 @@ EXPORTS = (
     "fg_model_batch", "fg_abi_version", "fg_index_term_ladder", "fg_kth_floor_combine", "fg_index_set_kth_floor",
     "fg_plan_set_peers", "fg_plan_ipc_export", "fg_plan_set_ipc_peers", "fg_plan_reset",
     "fg_count_batch", "fg_count_trace", "fg_index_doctab_get", "fg_index_doctab8_get",
+    "fg_index_build_positional", "fg_index_positions_get",
 )
 LADDER_KS = (1, 2, 3, 5, 10, 13, 20, 25, 50, 100, 125, 250, 500, 1000)  # FG_LADDER_LEVELS ranks
 KTH_KS = (1, 10, 20, 100, 1000)  # fg_index_term_kth / fg_index_set_kth_floor ranks
 HIST_BINS = 512  # fugu.h FG_HIST_BINS: score-histogram bins per query
 MAX_PEERS = 15  # fugu.h FG_MAX_PEERS
+FWD_SCAN_SLICES = 1024  # fugu.h FG_FWD_SCAN_SLICES: slices of fg_index_build_positional's device scans
+FWD_NONE = 0xFFFFFFFF  # a dropped position (a hole) in Index.positions() rows
 ABI_VERSION = 6  # include/fugu.h FG_ABI_VERSION this binding's structs follow
 
 if not os.path.exists(LIB_PATH):
@@ -97,6 +100,11 @@ class IndexInput(C.Structure):
                 ("tf_text", _u16p), ("tf_name", _u16p), ("fn_text", _u8p), ("fn_name", _u8p),
                 ("tot_tokens", C.c_uint64 * 2), ("deleted", _u8p), ("n_facet_terms", C.c_uint32),
                 ("facet_term_off", _u64p), ("facet_doc", _u32p), ("tot_facet_tokens", C.c_uint64)]
+
+
+class PositionsInput(C.Structure):
+    """fugu.h fg_positions_input: the postings' positions per field, in posting order."""
+    _fields_ = [("text_pos", _u32p), ("n_text_pos", C.c_uint64), ("name_pos", _u32p), ("n_name_pos", C.c_uint64)]
 
 
 class GlobalStats(C.Structure):
@@ -151,6 +159,10 @@ _sig("fg_version", C.c_char_p)
 _sig("fg_index_build_from_docs", C.c_int, _p, C.c_int, C.POINTER(DocsInput), C.POINTER(_p))
 _sig("fg_index_build", C.c_int, _p, C.c_int, C.POINTER(IndexInput), C.POINTER(_p))
 _sig("fg_index_build_global", C.c_int, _p, C.c_int, C.POINTER(IndexInput), C.POINTER(GlobalStats), C.POINTER(_p))
+if hasattr(_lib, "fg_index_build_positional"):  # (FG_ABI_VERSION did not move with them: an A/B library built before lacks them)
+    _sig("fg_index_build_positional", C.c_int, _p, C.c_int, C.POINTER(IndexInput), C.POINTER(PositionsInput),
+         C.POINTER(GlobalStats), C.POINTER(_p))
+    _sig("fg_index_positions_get", C.c_int, _p, C.c_int, C.c_uint32, C.c_uint32, _u64p, _u32p, C.c_uint64, _u64p)
 _sig("fg_docs_stats", C.c_int, C.POINTER(DocsInput), _u32p, _u32p, _u64p)
 _sig("fg_docs_facet_stats", C.c_int, C.POINTER(DocsInput), _u32p, _u64p)
 _sig("fg_index_build_from_docs_global", C.c_int, _p, C.c_int, C.POINTER(DocsInput), C.POINTER(GlobalStats),
@@ -342,6 +354,37 @@ def _docs_input(text_off, text_tok, n_terms, name_off=None, name_tok=None, delet
     return (text_off, text_tok, name_off, name_tok, deleted, fo, ft, tg, ng), inp
 
 
+def _index_input(n_docs, term_off, doc, tf_text, tf_name, fn_text, fn_name, tot_tokens, deleted=None, facets=None):
+    """(arrays it points into, IndexInput) of pre-inverted postings; facets:
+    (facet_term_off, facet_doc, n_facet_terms, tot_facet_tokens) or None."""
+    term_off = _u64(term_off)
+    doc = _u32(doc)
+    tf_text = None if tf_text is None else np.ascontiguousarray(tf_text, np.uint16)
+    tf_name = None if tf_name is None else np.ascontiguousarray(tf_name, np.uint16)
+    fn_text = np.ascontiguousarray(fn_text, np.uint8)
+    fn_name = None if fn_name is None else np.ascontiguousarray(fn_name, np.uint8)
+    deleted = None if deleted is None else np.ascontiguousarray(deleted, np.uint8)
+    fo = fd = None
+    nft, totf = 0, 0
+    if facets is not None:
+        fo, fd, nft, totf = _u64(facets[0]), _u32(facets[1]), int(facets[2]), int(facets[3])
+    inp = IndexInput(n_docs, len(term_off) - 1, _ptr(term_off, _u64p), _ptr(doc, _u32p), _ptr(tf_text, _u16p),
+                     _ptr(tf_name, _u16p), _ptr(fn_text, _u8p), _ptr(fn_name, _u8p),
+                     (C.c_uint64 * 2)(*[int(x) for x in tot_tokens]), _ptr(deleted, _u8p), nft,
+                     _ptr(fo, _u64p), _ptr(fd, _u32p), totf)
+    return (term_off, doc, tf_text, tf_name, fn_text, fn_name, deleted, fo, fd), inp
+
+
+def _positions_input(text_pos, name_pos=None):
+    """(arrays it points into, PositionsInput): the postings' positions per field
+    in posting order; name_pos None: no name postings."""
+    tp = _u32(text_pos)
+    npos = None if name_pos is None else _u32(name_pos)
+    pos = PositionsInput(_ptr(tp, _u32p) if len(tp) else None, len(tp),
+                         _ptr(npos, _u32p) if npos is not None and len(npos) else None, 0 if npos is None else len(npos))
+    return (tp, npos), pos
+
+
 @dataclass
 class ShardStats:
     """BM25 statistics of a (shard of a) namespace: summed across shards by one all-reduce."""
@@ -424,34 +467,47 @@ class Index:
     @classmethod
     def from_postings(cls, ctx: Context, n_docs: int, term_off, doc, tf_text, tf_name, fn_text, fn_name,
                       tot_tokens, deleted=None, facets=None, device: int | None = None,
-                      global_stats: "ShardStats | None" = None):
+                      global_stats: "ShardStats | None" = None, positions=None):
         """fg_index_build: postings already inverted by the host (the entry the Rust
         binding feeds from tantivy's segment readers).  `facets` =
-        (facet_term_off, facet_doc, n_facet_terms, tot_facet_tokens) or None."""
-        term_off = _u64(term_off)
-        doc = _u32(doc)
-        tf_text = None if tf_text is None else np.ascontiguousarray(tf_text, np.uint16)
-        tf_name = None if tf_name is None else np.ascontiguousarray(tf_name, np.uint16)
-        fn_text = np.ascontiguousarray(fn_text, np.uint8)
-        fn_name = None if fn_name is None else np.ascontiguousarray(fn_name, np.uint8)
-        deleted = None if deleted is None else np.ascontiguousarray(deleted, np.uint8)
-        fo = fd = None
-        nft, totf = 0, 0
-        if facets is not None:
-            fo, fd, nft, totf = _u64(facets[0]), _u32(facets[1]), int(facets[2]), int(facets[3])
-        inp = IndexInput(n_docs, len(term_off) - 1, _ptr(term_off, _u64p), _ptr(doc, _u32p), _ptr(tf_text, _u16p),
-                         _ptr(tf_name, _u16p), _ptr(fn_text, _u8p), _ptr(fn_name, _u8p),
-                         (C.c_uint64 * 2)(*[int(x) for x in tot_tokens]), _ptr(deleted, _u8p), nft,
-                         _ptr(fo, _u64p), _ptr(fd, _u32p), totf)
+        (facet_term_off, facet_doc, n_facet_terms, tot_facet_tokens) or None.
+        `positions` = (text_pos, name_pos or None): the postings' positions per field
+        in posting order (posting p owns tf_text[p] / tf_name[p] entries) --
+        fg_index_build_positional: the forward index is built on the device and
+        phrase queries run on the snapshot."""
+        keep, inp = _index_input(n_docs, term_off, doc, tf_text, tf_name, fn_text, fn_name, tot_tokens, deleted, facets)
         h = _p()
         dev = ctx.devices[0] if device is None else device
-        if global_stats is None:
+        gs, gkeep = (None, None) if global_stats is None else _global_stats(global_stats)
+        if positions is not None:
+            pkeep, pos = _positions_input(*positions)
+            _check(_lib.fg_index_build_positional(ctx.handle, dev, C.byref(inp), C.byref(pos),
+                                                  None if gs is None else C.byref(gs), C.byref(h)))
+            del pkeep
+        elif gs is None:
             _check(_lib.fg_index_build(ctx.handle, dev, C.byref(inp), C.byref(h)))
         else:
-            gs, keep = _global_stats(global_stats)
             _check(_lib.fg_index_build_global(ctx.handle, dev, C.byref(inp), C.byref(gs), C.byref(h)))
-            del keep
+        del keep, gkeep
         return cls(h)
+
+    def positions(self, field: int, doc0: int = 0, n_docs: int | None = None):
+        """fg_index_positions_get: the forward index rows of docs [doc0, doc0 + n_docs)
+        of `field` (FIELD_TEXT / FIELD_NAME) as (off u64 [n_docs + 1], tok u32
+        [off[-1]]): vocabulary ids by position, FWD_NONE at a hole."""
+        if n_docs is None:
+            n_docs = self.stats().n_docs - doc0
+        off = np.zeros(n_docs + 1, np.uint64)
+        n = C.c_uint64(0)
+        rc = _lib.fg_index_positions_get(self._h, field, doc0, n_docs, _ptr(off, _u64p), None, 0, C.byref(n))
+        if rc == FG_OK:  # (no entries at all)
+            return off, np.zeros(0, np.uint32)
+        if n.value == 0:
+            _check(rc)
+        tok = np.zeros(n.value, np.uint32)
+        _check(_lib.fg_index_positions_get(self._h, field, doc0, n_docs, _ptr(off, _u64p), _ptr(tok, _u32p),
+                                           n.value, C.byref(n)))
+        return off, tok
 
     @staticmethod
     def rescore_many(indexes, global_stats: "ShardStats", deleted=None) -> list:

@@ -152,7 +152,53 @@ int fg_index_build(fg_ctx* ctx, int dev, const fg_index_input* in, fg_index** ou
 /* ... one segment of a namespace scored with the namespace's statistics g
  * (below): the per-segment build a tantivy host makes for each new segment. */
 typedef struct fg_global_stats fg_global_stats;
+/* (keeps no positions: phrase queries need fg_index_build_positional, below) */
 int fg_index_build_global(fg_ctx* ctx, int dev, const fg_index_input* in, const fg_global_stats* g, fg_index** out);
+
+/* Positions of pre-inverted postings (tantivy: SegmentPostings::positions of the
+ * `text` / `name` inverted indexes), for fg_index_build_positional.  Per field one
+ * flat array in the posting order of fg_index_input (CSR by term, docs ascending):
+ * posting p owns exactly tf_text[p] (tf_name[p]) consecutive entries, its token
+ * positions in that field of its doc, strictly ascending; a posting whose tf in the
+ * field is 0 owns none.  tf_* is u16, so a posting owns at most 65535 positions:
+ * a term that occurs more often in one field of one doc cannot be given (the tf a
+ * host saturates at 65535 must come with exactly 65535 positions).  A position no
+ * posting claims is a token the analyzer dropped (a hole).  Tokens dropped after a
+ * doc's last kept token are not represented (no phrase reaches them), as with
+ * fg_docs_input's gap lists.  Positions are < 0xFFFFFFFF. */
+typedef struct fg_positions_input {
+  const uint32_t* text_pos;  uint64_t n_text_pos;   /* = sum of tf_text */
+  const uint32_t* name_pos;  uint64_t n_name_pos;   /* = sum of tf_name; NULL / 0: no name postings */
+} fg_positions_input;
+
+/* fg_index_build_global (g may be NULL: local statistics, as fg_index_build) plus a
+ * forward index built on the device from `pos`: the snapshot has
+ * has_positions = 1 and runs phrase queries exactly as one built from the same docs'
+ * token streams with keep_positions (the `name` forward index only when the
+ * snapshot has name postings).  Everything fg_index_build_global rejects is rejected
+ * the same way.  FG_EINVAL, checked on the host before the context or the device is
+ * looked at, the message naming the field: pos == NULL (use fg_index_build_global);
+ * n_*_pos not the field's tf sum; a NULL array with a non-zero count; tf_name > 0
+ * somewhere but no name_pos.  FG_EINVAL, found by the build's kernels (no snapshot
+ * is returned, nothing stays allocated): a posting whose positions do not strictly
+ * ascend; a position of 0xFFFFFFFF; two postings of one field claiming the same
+ * (doc, position). */
+int fg_index_build_positional(fg_ctx* ctx, int dev, const fg_index_input* in, const fg_positions_input* pos,
+                              const fg_global_stats* g, fg_index** out);
+/* The device scans of that build run over this many slices whatever their length
+ * (corpus sizes around it are what a test of the scans wants). */
+#define FG_FWD_SCAN_SLICES 1024
+
+/* Host-side check (as fg_index_bm25 is): the forward index rows of docs
+ * [doc0, doc0 + n_docs) of `field` (FG_FIELD_TEXT / FG_FIELD_NAME) of a snapshot
+ * with positions, from either build path or a rescore of one: off_out[n_docs + 1]
+ * relative to the first row, tok_out the rows' entries (vocabulary ids, 0xFFFFFFFF
+ * at a hole), *n_tok their number -- also when cap (the room of tok_out, in entries)
+ * is too small: then FG_EINVAL and tok_out is untouched.  FG_EINVAL on a snapshot
+ * without positions or without that field's forward index, and on docs past the
+ * snapshot's. */
+int fg_index_positions_get(const fg_index* ix, int field, uint32_t doc0, uint32_t n_docs, uint64_t* off_out,
+                           uint32_t* tok_out, uint64_t cap, uint64_t* n_tok);
 
 /* ---- doc-sharded namespace --------------------- */
 /* One namespace split into contiguous doc-id ranges, one shard per GPU, each
@@ -177,7 +223,8 @@ int fg_docs_stats(const fg_docs_input* in, uint32_t* df_text, uint32_t* df_name,
 /* ... and of its facet field: df_facet [n_facet_terms], *tot_facet. */
 int fg_docs_facet_stats(const fg_docs_input* in, uint32_t* df_facet, uint64_t* tot_facet);
 /* fg_index_build_from_docs scored with global statistics (g may be NULL = local).
- * (fg_index_build[_global] take pre-inverted postings and keep no positions.)
+ * (fg_index_build[_global] take pre-inverted postings and keep no positions;
+ * fg_index_build_positional takes the postings' positions too.)
  * A build whose docs hold fewer than a quarter of the n_terms vocabulary's terms
  * (a commit's new docs) keeps its own term dictionary -- its work and device
  * arrays then scale with its own terms, as a tantivy segment's do -- and every
@@ -232,7 +279,7 @@ typedef struct fg_index_stats {
   uint32_t n_dense_f32;      /* terms with an f32 score table */
   uint32_t n_rank_terms;     /* terms with rank words */
   uint32_t n_sparse_rank_terms;  /* ... of which sparse rank words (block entries + the words holding docs) */
-  uint32_t has_positions;    /* 1: built with fg_docs_input.keep_positions (phrase queries run on it) */
+  uint32_t has_positions;    /* 1: built with fg_docs_input.keep_positions or fg_index_build_positional (phrase queries run on it) */
   uint64_t rank_bytes;       /* device bytes of the rank words, plain and sparse */
 } fg_index_stats;
 int fg_index_stats_get(const fg_index* ix, fg_index_stats* out);

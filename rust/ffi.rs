@@ -87,6 +87,14 @@ pub struct fg_index_input {
 }
 
 #[repr(C)]
+pub struct fg_positions_input {     // SegmentPostings::positions of text / name, in fg_index_input's posting order
+    pub text_pos: *const u32,       // posting p owns tf_text[p] entries, strictly ascending
+    pub n_text_pos: u64,            // = sum of tf_text
+    pub name_pos: *const u32,       // or null (no name postings)
+    pub n_name_pos: u64,            // = sum of tf_name
+}
+
+#[repr(C)]
 pub struct fg_global_stats {        // the Searcher's Bm25StatisticsProvider, summed over segments
     pub n_docs: u64,
     pub tot_tokens: [u64; 2],
@@ -210,6 +218,11 @@ extern "C" {
     pub fn fg_index_build(ctx: *mut fg_ctx, dev: c_int, inp: *const fg_index_input, out: *mut *mut fg_index) -> c_int;
     pub fn fg_index_build_global(ctx: *mut fg_ctx, dev: c_int, inp: *const fg_index_input, g: *const fg_global_stats,
                                  out: *mut *mut fg_index) -> c_int;
+    pub fn fg_index_build_positional(ctx: *mut fg_ctx, dev: c_int, inp: *const fg_index_input,
+                                     pos: *const fg_positions_input, g: *const fg_global_stats,
+                                     out: *mut *mut fg_index) -> c_int;
+    pub fn fg_index_positions_get(ix: *const fg_index, field: c_int, doc0: u32, n_docs: u32, off_out: *mut u64,
+                                  tok_out: *mut u32, cap: u64, n_tok: *mut u64) -> c_int;
     pub fn fg_docs_stats(inp: *const fg_docs_input, df_text: *mut u32, df_name: *mut u32, tot_tokens2: *mut u64)
                          -> c_int;
     pub fn fg_docs_facet_stats(inp: *const fg_docs_input, df_facet: *mut u32, tot_facet: *mut u64) -> c_int;
