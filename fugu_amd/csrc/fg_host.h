@@ -457,6 +457,23 @@ inline uint32_t doctab8_lead() {
   return e && *e ? (uint32_t)std::max(0l, atol(e)) : fg::kDocTab8Lead;
 }
 
+// an ending multi-list k_conj item publishes the query's histogram k-th edge as
+// its threshold (fg::kOptConjHistThr): FUGU_CONJ_HIST_THR, read when a plan is
+// made, on unless set to 0
+inline bool conj_hist_thr() {
+  const char* e = getenv("FUGU_CONJ_HIST_THR");
+  return !(e && *e) || atol(e) != 0;
+}
+
+// bin 0 of a Must-driven query's histogram sits at its largest possible score
+// over this divisor (a query with a starting threshold: at that threshold):
+// FUGU_HIST_LO_DIV, read when a plan is made.  Keys below bin 0 are not counted.
+inline float hist_lo_div() {
+  const char* e = getenv("FUGU_HIST_LO_DIV");
+  const double v = e && *e ? atof(e) : 0.0;
+  return v >= 1.0 ? (float)v : 256.0f;
+}
+
 // the bound table of local term t: its slot + 1, or 0
 inline uint32_t doctab8_slot(const IndexBounds& b, uint32_t t) {
   const auto it = std::lower_bound(b.dtab8_map.begin(), b.dtab8_map.end(), (uint64_t)t << 32);
@@ -556,6 +573,11 @@ struct fg_plan {
   hipStream_t up_stream = hipStreamPerThread;  // the stream the plan was uploaded on
 };
 
+// Diagnostic entry point, not part of include/fugu.h: overwrites the plan's
+// starting thresholds (DevPlan::q_thr0) with the lowest key of score[i] per
+// batch query (0: none), e.g. each query's final k-th score of an earlier run
+// -- the ceiling of what any threshold work can give k_conj
+extern "C" int fg_plan_seed_thr0(fg_plan* p, const float* score, uint32_t n);
 
 namespace fgh {
 // the local id of vocabulary term t in snapshot ix (fg_index::tmap), or

@@ -172,6 +172,32 @@ constexpr uint32_t kModeOr = 1;
 // across ALL the query's work items (and across the shards of a linked group).
 constexpr uint32_t kQBins = 512;
 
+// Histogram bin of a hit key for query bins (lo, sh), or kQBins (not counted:
+// below bin 0's edge).
+__host__ __device__ inline uint32_t qbin(uint64_t key, uint32_t lo, uint32_t sh) {
+  const uint32_t bits = (uint32_t)(key >> 32);
+  if (bits < lo) return kQBins;
+  const uint32_t b = (bits - lo) >> sh;
+  return b < kQBins - 1 ? b : kQBins - 1;
+}
+
+// The k-th edge of a histogram, as one step over a descending run of its bins:
+// c[0 .. n) are the counts of bins `first`, first - 1, ..., and `before` docs
+// are counted in the bins above `first`.  When the highest bin b with at least
+// K counted docs in bins >= b is one of the run's, returns its lower edge as
+// the score-only key (lo + (b << sh)) << 32 (never 0: lo >= 1), else 0.  Over
+// the whole histogram (first = kQBins - 1, before = 0) that is its running
+// threshold; a workgroup calls it per thread on the thread's own bins with the
+// prefix of a scan.  Counts that miss adds only lower the result.
+__host__ __device__ inline uint64_t hist_kth_edge(const uint32_t* c, uint32_t n, uint32_t first, uint32_t before,
+                                                  uint32_t K, uint32_t lo, uint32_t sh) {
+  for (uint32_t i = 0; i < n; ++i) {
+    if (before < K && before + c[i] >= K) return (uint64_t)(lo + ((first - i) << sh)) << 32;
+    before += c[i];
+  }
+  return 0ull;
+}
+
 // DevPlan::q_m packing: bits 0-7 terms in q_terms, 8-15 Must clauses (k_conj
 // queries; 0 for k_disj queries), 16-23 MustNot clauses.  q_terms holds, per
 // query, k_conj: [Must (cost order)][MustNot][Should (clause order)];
@@ -560,6 +586,10 @@ __host__ __device__ inline uint32_t filter_bits(const uint32_t* mask, uint32_t s
 // items covering similar doc ranges of different queries run together, so the
 // segments of hot posting lists they probe are shared through L2 / MALL.
 constexpr uint32_t kMaxPeers = 15;  // peers of one plan (fugu.h FG_MAX_PEERS, fg_plan_set_peers)
+// DevPlan::opts bit: a multi-list k_conj item that ends reads the query's bins
+// back as it adds to them and publishes the query-wide k-th edge as a threshold
+// (FUGU_CONJ_HIST_THR, default on)
+constexpr uint32_t kOptConjHistThr = 1u;
 
 struct DevPlan {
   uint32_t n_queries;
@@ -596,6 +626,7 @@ struct DevPlan {
                                 // whose statistics changed since its build), with bit 0 `name` postings
                                 // (tfn_name) and bit 1 escaped tf bytes (esc_pos); the kernels are instantiated
                                 // per value (0, 4 = query-time, 7 = query-time with names / escapes)
+  uint32_t opts;                // planner settings read when the plan is made: kOptConjHistThr
   uint32_t n_single;            // k_conj: the first n_single work items belong to single-list queries
   uint32_t n_scan;              // k_scan work items (queries with no text terms), after the total_chunks
                                 // k_conj / k_disj items in work_q / work_c / work_n

@@ -1146,6 +1146,23 @@ int fg_plan_diag(fg_plan* p, uint64_t* out, size_t n_words, uint32_t* cand_cnt) 
   return FG_OK;
 }
 
+// Diagnostic (fg_host.h; tools/conj_threshold_ceiling.py): every slot of batch
+// query i starts from the lowest key with score[i] (plan_host's convention for a
+// single list's starting threshold; 0: none).  The bins stay as planned.
+int fg_plan_seed_thr0(fg_plan* p, const float* score, uint32_t n) {
+  if (!p || !score || n != p->nq_batch) return fail(FG_EINVAL, "bad arguments");
+  std::vector<uint64_t> t((size_t)p->nq);
+  for (uint32_t v = 0; v < p->nq; ++v) {
+    const float s = score[v % p->nq_batch];
+    t[v] = s > 0.0f ? fg::make_key(s, 0xFFFFFFFFu) : 0ull;
+  }
+  HIPCHK(hipSetDevice(p->ix->dev));
+  if (p->pin) HIPCHK(hipStreamSynchronize(p->up_stream));  // an upload still in flight would overwrite them
+  if (p->last_stream_used) HIPCHK(hipStreamSynchronize(p->last_stream));
+  if (p->nq) HIPCHK(hipMemcpy(const_cast<uint64_t*>(p->d.q_thr0), t.data(), 8ull * p->nq, hipMemcpyHostToDevice));
+  return FG_OK;
+}
+
 int fg_plan_destroy(fg_plan* p) {
   delete p;
   return FG_OK;

@@ -232,14 +232,6 @@ __device__ inline uint32_t posting_pos(const DevIndex& ix, uint32_t t, uint32_t 
 // namespace with an equal score is never pruned (the merge breaks ties by
 // shard); an unlinked plan publishes exact keys.
 
-// Histogram bin of a hit key for query bins (lo, sh), or kQBins (not counted:
-// below bin 0's edge).
-__device__ inline uint32_t qbin(uint64_t key, uint32_t lo, uint32_t sh) {
-  const uint32_t bits = (uint32_t)(key >> 32);
-  if (bits < lo) return kQBins;
-  return min((bits - lo) >> sh, kQBins - 1);
-}
-
 // ---------------------------------------------------------------- workgroup helpers
 // Exclusive prefix over the workgroup of one u32 per thread (256 threads).
 __device__ inline uint32_t block_exclusive_scan(uint32_t v, uint32_t* scratch /*[4]*/) {
@@ -259,24 +251,34 @@ __device__ inline uint32_t block_exclusive_scan(uint32_t v, uint32_t* scratch /*
   return base + incl - v;
 }
 
+// The k-th edge of a histogram whose counts the workgroup holds, thread t those
+// (v0, v1) of bins kQBins - 1 - 2t and the one below: hist_kth_edge over the
+// whole histogram, a scan handing each thread its prefix.  Workgroup-uniform
+// result; scratch[0..6] used.
+__device__ inline uint64_t block_kth_edge(uint32_t v0, uint32_t v1, uint32_t K, uint32_t lo, uint32_t sh,
+                                          uint32_t* scratch) {
+  static_assert(kQBins == 2 * kThreads, "two bins per thread");
+  const uint32_t tid = threadIdx.x;
+  if (tid == 0) scratch[5] = 0;
+  const uint32_t before = block_exclusive_scan(v0 + v1, scratch);
+  const uint32_t c[2] = {v0, v1};
+  const uint64_t e = hist_kth_edge(c, 2, kQBins - 1 - 2 * tid, before, K, lo, sh);
+  if (e) scratch[5] = (uint32_t)(e >> 32);  // (at most one thread: a score-only key's upper word)
+  __syncthreads();
+  const uint32_t bits = scratch[5];
+  __syncthreads();
+  return (uint64_t)bits << 32;
+}
+
 // The running threshold of query q from its score histogram: the lower edge of
 // the highest bin b with >= K counted docs in bins >= b (score-only key), or 0.
 // Relaxed agent-scope loads (sc1): the bins only grow, so a stale bin can only
-// lower the threshold.  Workgroup-uniform result; scratch[0..6] used.
+// lower the threshold.
 __device__ uint64_t hist_threshold(const uint32_t* gh, uint32_t K, uint32_t lo, uint32_t sh, uint32_t* scratch) {
-  static_assert(kQBins == 2 * kThreads, "two bins per thread");
-  const uint32_t tid = threadIdx.x;
-  const uint32_t b0 = kQBins - 1 - 2 * tid, b1 = b0 - 1;  // descending
+  const uint32_t b0 = kQBins - 1 - 2 * threadIdx.x, b1 = b0 - 1;  // descending
   const uint32_t v0 = __hip_atomic_load(gh + b0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const uint32_t v1 = __hip_atomic_load(gh + b1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (tid == 0) scratch[5] = kQBins;
-  const uint32_t before = block_exclusive_scan(v0 + v1, scratch);
-  if (before < K && before + v0 >= K) scratch[5] = b0;
-  else if (before + v0 < K && before + v0 + v1 >= K) scratch[5] = b1;
-  __syncthreads();
-  const uint32_t b = scratch[5];
-  __syncthreads();
-  return b < kQBins ? (uint64_t)(lo + (b << sh)) << 32 : 0ull;
+  return block_kth_edge(v0, v1, K, lo, sh, scratch);
 }
 
 constexpr uint64_t kScoreOnly = 0xFFFFFFFF00000000ull;  // a key's score bits (thresholds shared across shards)
@@ -288,13 +290,35 @@ __device__ inline void peer_thr_max(const DevPlan& pl, uint32_t ql, uint64_t key
     atomicMax(reinterpret_cast<unsigned long long*>(pl.peer_thr[i] + ql), (unsigned long long)(key & kScoreOnly));
 }
 
-// Add the LDS bins to the query's global histogram (and the peers', a pass
-// each over the bins: one loop holding every peer's address took k_conj past
-// its register budget) and clear them.
-__device__ inline void hist_add(uint32_t* lh, uint32_t* gh, const DevPlan& pl, uint32_t ql) {
+// The LDS bins into the peers' histograms of the query: a pass each over the
+// bins (one loop holding every peer's address took k_conj past its register
+// budget), write-only.
+__device__ inline void hist_add_peers(const uint32_t* lh, const DevPlan& pl, uint32_t ql) {
   for (uint32_t i = 0; i < pl.n_peers; ++i)
     for (uint32_t b = threadIdx.x; b < kQBins; b += kThreads)
       if (const uint32_t c = lh[b]) atomicAdd(pl.peer_hist[i] + (size_t)ql * kQBins + b, c);
+}
+
+// hist_add with the query's counts read back (kOptConjHistThr): the adds
+// return what the bins held, so old + c is every item's adds that reached the
+// bin so far (served where the threshold word's atomicMax is), and the
+// query-wide k-th edge comes out of them (block_kth_edge; workgroup-uniform).
+// Bins from `cut` up are asked even where the item adds nothing (an add of 0);
+// the bins below it count as 0 unless the item adds to them, which can only
+// lower the edge.  The peers' bins keep their write-only pass.
+__device__ inline uint64_t hist_add_kth(const uint32_t* lh, uint32_t* gh, const DevPlan& pl, uint32_t ql, uint32_t cut,
+                                        uint32_t K, uint32_t lo, uint32_t sh, uint32_t* scratch) {
+  hist_add_peers(lh, pl, ql);
+  const uint32_t b0 = kQBins - 1 - 2 * threadIdx.x, b1 = b0 - 1;  // descending, as hist_threshold
+  const uint32_t c0 = lh[b0], c1 = lh[b1];
+  const uint32_t v0 = (c0 || b0 >= cut) ? atomicAdd(&gh[b0], c0) + c0 : 0u;
+  const uint32_t v1 = (c1 || b1 >= cut) ? atomicAdd(&gh[b1], c1) + c1 : 0u;
+  return block_kth_edge(v0, v1, K, lo, sh, scratch);
+}
+
+// Add the LDS bins to the query's global histogram (and the peers') and clear them.
+__device__ inline void hist_add(uint32_t* lh, uint32_t* gh, const DevPlan& pl, uint32_t ql) {
+  hist_add_peers(lh, pl, ql);
   for (uint32_t b = threadIdx.x; b < kQBins; b += kThreads) {
     const uint32_t c = lh[b];
     if (c) {
@@ -1101,14 +1125,6 @@ __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPl
     }
   }
   if (tid == 0 && pend > sh.thr) sh.thr = pend;
-  // the peers get the item's threshold once, when it ends (inside the chunk loop
-  // the publication cost k_conj a spilled register)
-  if (tid == 0) peer_thr_max(pl, ql, sh.thr);
-  __syncthreads();
-
-  // write the kept keys that still clear the freshest threshold
-  const uint32_t total = flush_candidates(pl, q, sh.buf, sh.n_buf, sh.thr, sh.scratch);
-  (void)total;
   // count the item's kept keys (distinct docs of its own lead chunks) into the
   // query's bins, through LDS bins (sh.hist is free once the last select ran)
   {
@@ -1121,8 +1137,35 @@ __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPl
       if (b < kQBins) atomicAdd(&sh.hist[b], 1u);
     }
     __syncthreads();
-    hist_add(sh.hist, gh, pl, ql);
+    if (!kSingle && (pl.opts & kOptConjHistThr)) {
+      // The query's k-th edge over every item finished so far, from the bins'
+      // own replies: a single item's k-th key (all the threshold word carried)
+      // is the k-th of ~1/150 of a dense query's matches.  The item's >= k keys
+      // sit at or above its threshold, so the edge cannot lie below that bin: the
+      // bins from there up are asked (all of them by an item without one).  The
+      // edge goes where the item's own k-th key goes; every later chunk of the
+      // query receives it as the reply of its pending atomicMax.  Headline
+      // k_conj 0.855 -> 0.815 ms, second-list probes 127.8M -> 92.8M
+      // (profiles/conj_hist_thr/).
+      const uint64_t cur = sh.thr;
+      const uint32_t cb = qbin(cur, h_lo, h_sh);
+      const uint64_t edge = hist_add_kth(sh.hist, gh, pl, ql, cur && cb < kQBins ? cb : 0u, K, h_lo, h_sh, sh.scratch);
+      if (tid == 0 && edge > cur) {
+        sh.thr = edge;
+        atomicMax(gthr, (unsigned long long)(edge & pl.pub_mask));
+      }
+    } else {
+      hist_add(sh.hist, gh, pl, ql);
+    }
   }
+  // the peers get the item's threshold once, when it ends (inside the chunk loop
+  // the publication cost k_conj a spilled register)
+  if (tid == 0) peer_thr_max(pl, ql, sh.thr);
+  __syncthreads();
+
+  // write the kept keys that still clear the freshest threshold
+  const uint32_t total = flush_candidates(pl, q, sh.buf, sh.n_buf, sh.thr, sh.scratch);
+  (void)total;
   FG_STAMP(w, 0, t_start);
   FG_STAMP(w, 1, t_probe);
   FG_STAMP(w, 2, t_keys);

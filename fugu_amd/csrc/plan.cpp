@@ -274,10 +274,11 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
     h.q_rup[x] = rup;
     cm[j] = fgh::term_max_scaled(ix, t, rup);
   };
-  // histogram bins of query i: bin 0 at the starting threshold (or ub / 256), the
+  // histogram bins of query i: bin 0 at the starting threshold (or ub / div), the
   // top bin at the query's largest possible score ub; ~kQBins bins between
-  auto set_bins = [&](uint32_t i, float ub) {
-    const float lo = h.thr0[i] ? fg::key_score(h.thr0[i]) : ub / 256.0f;
+  const float conj_lo_div = fgh::hist_lo_div();  // (Must-driven queries: FUGU_HIST_LO_DIV)
+  auto set_bins = [&](uint32_t i, float ub, float div = 256.0f) {
+    const float lo = h.thr0[i] ? fg::key_score(h.thr0[i]) : ub / div;
     uint32_t lb, hb;
     std::memcpy(&lb, &lo, 4);
     std::memcpy(&hb, &ub, 4);
@@ -441,7 +442,7 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
       float ub = fmx + cm[0];
       for (uint32_t j = 1; j < mt; ++j)
         if (j < nm || j >= nm + nx) ub += cm[j];
-      set_bins(i, ub);
+      set_bins(i, ub, conj_lo_div);
     }
     const uint64_t df0 = ix->off[qt[0] + 1] - ix->off[qt[0]];
     h.lead[i] = (uint32_t)df0;
@@ -921,6 +922,7 @@ void fill_view(fg_plan* p, fg_index* const* ixs, PlanTables& t, const WorkList& 
   // doc of another snapshot tied with the k-th score is never pruned (the merge
   // breaks such ties by snapshot)
   p->d.pub_mask = S > 1 ? 0xFFFFFFFF00000000ull : ~0ull;
+  p->d.opts = fgh::conj_hist_thr() ? fg::kOptConjHistThr : 0u;
   p->h_any.assign(nq1, 0);
   for (uint32_t v = 0; v < nq; ++v)
     if (t.ngroup[v]) p->h_any[v % nq1] = 1;

@@ -200,6 +200,8 @@ _sig("fg_plan_info_get", C.c_int, _p, C.POINTER(PlanInfo))
 _sig("fg_plan_profile", C.c_int, _p, C.c_int)
 _sig("fg_plan_kernel_ms", C.c_int, _p, _f64p, _u32p)
 _sig("fg_plan_diag", C.c_int, _p, _u64p, C.c_size_t, _u32p)
+if hasattr(_lib, "fg_plan_seed_thr0"):  # (diagnostic, fg_host.h: not in fugu.h; an A/B library built before lacks it)
+    _sig("fg_plan_seed_thr0", C.c_int, _p, _f32p, C.c_uint32)
 _sig("fg_plan_destroy", C.c_int, _p)
 _sig("fg_search_batch", C.c_int, _p, C.POINTER(QueryBatch), C.c_uint32, _f32p, _u32p, _u32p)
 _sig("fg_search_sharded", C.c_int, _p, C.POINTER(_p), C.c_uint32, C.POINTER(QueryBatch), C.c_uint32, _f32p, _u32p,
@@ -773,6 +775,14 @@ class Plan:
         n = C.c_uint32(0)
         _check(_lib.fg_plan_kernel_ms(self._h, _ptr(ms, _f64p), C.byref(n)))
         return ms, n.value
+
+    def seed_thresholds(self, score):
+        """fg_plan_seed_thr0 (diagnostic): every query starts from the lowest key with
+        score[i] ([n_batch] f32, 0: no starting threshold)."""
+        s = np.ascontiguousarray(score, np.float32)
+        if s.shape != (self.n_batch,):
+            raise ValueError(f"scores of {s.shape}, expected ({self.n_batch},)")
+        _check(_lib.fg_plan_seed_thr0(self._h, _ptr(s, _f32p), self.n_batch))
 
     def candidate_counts(self):
         cnt = np.zeros(self.n_queries, np.uint32)

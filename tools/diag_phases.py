@@ -27,6 +27,8 @@ def main():
     ap.add_argument("--terms", type=int, default=3)
     ap.add_argument("--mixed", action="store_true")
     ap.add_argument("--k", type=int, default=100)
+    ap.add_argument("--seed", action="store_true",
+                    help="stamps of a plan seeded with the final k-th scores (fg_plan_seed_thr0): the threshold ceiling")
     args = ap.parse_args()
     from fugu_amd import native, synth
     ctx = native.Context((0,))
@@ -36,7 +38,14 @@ def main():
     plan = ix.plan(q_off, terms, args.k)
     for _ in range(3):
         plan.execute()
-    plan.results()
+    s, _, n = plan.results()
+    if args.seed:  # the same batch from a plan that starts at each query's final k-th score (0: fewer than k hits)
+        kth = np.where(n == args.k, s[:, args.k - 1], np.float32(0.0)).astype(np.float32)
+        plan = ix.plan(q_off, terms, args.k)
+        plan.seed_thresholds(kth)
+        for _ in range(3):
+            plan.execute()
+        plan.results()
     conj, fin = plan.diag()
     cc = plan.candidate_counts()
     us = 1e-2  # 10 ns ticks -> us

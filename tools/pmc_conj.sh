@@ -2,16 +2,19 @@
 # Hardware-counter passes of the bench's k_conj (or k_disj: pass --disj --k 1000) (run on the MI355X box through
 # gpurun).  One rocprofv3 --pmc run per pass (slot limits: 8 SQ, 4 TCP, 2 TA,
 # 2 TD, 4 TCC), each under its own hard time limit, then tools/pmc_summary.py.
+# PMC_PASSES="sq1 tcc dram" runs only those passes (default: all six).
 set -euo pipefail
 R=${GRAFT_REPO_ROOT:-/root/repo}
 TAG=${1:-conj}
 shift || true
 ARGS="--steps 3 --warmup 1 --no-cpu --p50-queries 0 --no-extra $*"
 OUT=$R/gpurun_out/pmc_$TAG
+PASSES=" ${PMC_PASSES:-sq1 sq2 tcp tlb tcc dram} "
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 pass() {
   local name=$1; shift
+  case "$PASSES" in *" $name "*) ;; *) return 0 ;; esac
   timeout -s KILL 150 rocprofv3 --pmc "$@" --output-format csv -d "$OUT/$name" -o run -- python3 "$R/bench.py" $ARGS \
     > "$OUT/$name.log" 2>&1
 }
