@@ -20,12 +20,11 @@ import numpy as np
 import pytest
 
 import bool_ref as br
-import synth_ref as sr
+from seed_cases import N_BIG, N_TIE, big_case, few_case, tie_case
 
 pytestmark = pytest.mark.gpu
 
 VAR = "FUGU_CONJ_HIST_THR"
-N_BIG, N_TIE, N_FEW = 262_144, 100_000, 20_000
 ITEM = 16 * 2048  # lead postings of a full work item (kMaxGroup chunks of kChunk)
 
 
@@ -75,18 +74,6 @@ def same_live(a, b):
     assert np.array_equal(a[0][live].view(np.uint32), b[0][live].view(np.uint32))
 
 
-def big_case():
-    """The corpus of a. and c., its reference, and the batch: the 8 most frequent terms."""
-    from fugu_amd import synth
-    c = synth.corpus(N_BIG)
-    ref = br.Corpus(synth.VOCAB, c.off, c.tok)
-    top = np.argsort(-ref.own.df_text, kind="stable")[:8]
-    rng = np.random.default_rng(20)
-    qs = [[int(t) for t in rng.choice(top, 3, replace=False)] for _ in range(64)]
-    qs += [[int(t) for t in rng.choice(top, 5, replace=False)] for _ in range(16)]
-    return c, ref, top, qs
-
-
 @pytest.fixture(scope="module")
 def big(native, ctx):
     from fugu_amd import synth
@@ -115,16 +102,6 @@ def test_many_items_per_query(native, big, k):
             assert_exact(got[v][0][i], got[v][1][i], got[v][2][i], (w[0][:k], w[1][:k]), (v, k, i, big["qs"][i]))
     print(f"\nk={k}: candidates written on / off: {cand['1']} / {cand['0']}")
     same_live(got["1"], got["0"])
-
-
-def tie_case():
-    """100,000 docs of six tokens, the query terms 1, 2, 3 once each: every match scores the same."""
-    rng = np.random.default_rng(7)
-    tok = np.empty((N_TIE, 6), np.uint32)
-    tok[:, :3] = [1, 2, 3]
-    tok[:, 3:] = rng.integers(10, 5000, (N_TIE, 3))
-    off = (np.arange(N_TIE + 1, dtype=np.uint64) * np.uint64(6))
-    return off, tok.reshape(-1), 5000, [[1, 2, 3], [1, 2], [3, 1, 2]]
 
 
 @pytest.mark.parametrize("k", [10, 100])
@@ -209,26 +186,6 @@ def test_linked_plans(native, ctx, big):
         assert np.array_equal(a, b)
     for ix in shards:
         ix.close()
-
-
-def few_case():
-    """A 20,000-doc corpus with facets and queries of fewer than 100 matches:
-    (Must, MustNot, Should) around a term of 60-99 docs, two Musts the same way,
-    and frequent terms under a rare facet."""
-    from fugu_amd import synth
-    V = 1 << 16
-    c = synth.corpus(N_FEW, V)
-    fo, ft, nf = sr.facet_tokens(N_FEW, 4242)
-    ref = br.Corpus(V, c.off, c.tok, facets=(fo, ft, nf))
-    df = ref.own.df_text
-    top = np.argsort(-df, kind="stable")[:8]
-    rare = [int(t) for t in np.flatnonzero((df >= 60) & (df < 100))[:4]]
-    M, S, X = br.MUST, br.SHOULD, br.MUST_NOT
-    qs = [([t, int(top[7]), int(top[1])], [M, X, S], []) for t in rare]
-    qs += [([t, int(top[0]), int(top[6]), int(top[2])], [M, M, X, S], []) for t in rare]
-    qs += [([int(top[7]), int(top[5])], [M, M], [29 + 7 * a]) for a in range(4)]  # org/acme/teamA/proj0
-    qs += [([int(top[3]), int(top[4]), int(top[6])], [M, M, M], [29 + 7 * a + 1]) for a in range(4)]
-    return c, V, (fo, ft, nf), ref, qs
 
 
 def test_fewer_than_k_matches(native, ctx):
