@@ -196,6 +196,93 @@ std::vector<uint32_t> choose_doctab_terms(const fg_index* ix, uint64_t stride, c
   return ts;
 }
 
+// The terms that get a score-tiered lead copy (DevIndex::bdoc / bpsc / bcmax):
+// df >= N / FUGU_BAND_DIV (default kBandDiv; 0: none) in a snapshot of >=
+// FUGU_BAND_MIN_DOCS docs (default kBandMinDocs), densest first (ties by term
+// id), at most kBandMax and within 1/FUGU_BAND_FRAC (default kBandFrac; 0: no
+// cap) of the snapshot's posting bytes (12 B each; a copy takes 8 B per posting).
+std::vector<uint32_t> choose_band_terms(const fg_index* ix) {
+  std::vector<uint32_t> ts;
+  const uint64_t N = ix->n_docs;
+  uint32_t div = fg::kBandDiv;
+  uint64_t min_docs = fg::kBandMinDocs, frac = fg::kBandFrac;
+  if (const char* e = getenv("FUGU_BAND_DIV"))
+    if (*e) div = (uint32_t)std::max(0l, atol(e));
+  if (const char* e = getenv("FUGU_BAND_MIN_DOCS"))
+    if (*e) min_docs = (uint64_t)std::max(0l, atol(e));
+  if (const char* e = getenv("FUGU_BAND_FRAC"))
+    if (*e) frac = (uint64_t)std::max(0l, atol(e));
+  if (!div || N < min_docs) return ts;
+  auto df = [&](uint32_t t) { return ix->off[t + 1] - ix->off[t]; };
+  for (uint32_t t = 0; t < ix->n_terms; ++t)
+    if (df(t) && df(t) * div >= N && df(t) < 0x80000000ull) ts.push_back(t);
+  std::stable_sort(ts.begin(), ts.end(), [&](uint32_t a, uint32_t b) { return df(a) > df(b); });
+  if (ts.size() > fg::kBandMax) ts.resize(fg::kBandMax);
+  uint64_t left = frac ? 12ull * ix->n_postings / frac : ~0ull;
+  size_t n = 0;
+  while (n < ts.size() && 8 * df(ts[n]) <= left) left -= 8 * df(ts[n++]);
+  ts.resize(n);
+  return ts;
+}
+
+// The tiered copies of `terms` from the build's scores: histograms, the host's
+// cuts, then the stable partition and the copies' chunk maxima (BandJob).
+int build_bands(fg_index* ix, const std::vector<uint32_t>& terms, const float* d_psc, uint32_t* d_bdoc, float* d_bpsc,
+                float* d_bcmax, uint32_t grid_cap) {
+  fg::BandJob bj{};
+  bj.doc = ix->d.doc;
+  bj.psc = d_psc;
+  bj.bdoc = d_bdoc;
+  bj.bpsc = d_bpsc;
+  bj.bcmax = d_bcmax;
+  bj.n = (uint32_t)terms.size();
+  std::vector<uint64_t> map(terms.size()), boffs(terms.size());
+  std::vector<uint32_t> c0s(terms.size());
+  uint64_t boff = 0;
+  for (uint32_t i = 0; i < terms.size(); ++i) {
+    const uint64_t df = ix->off[terms[i] + 1] - ix->off[terms[i]];
+    bj.df[i] = (uint32_t)df;
+    bj.off[i] = ix->off[terms[i]];
+    bj.boff[i] = boffs[i] = boff;
+    c0s[i] = bj.c0[i];
+    bj.c0[i + 1] = bj.c0[i] + (uint32_t)((df + fg::kChunk - 1) / fg::kChunk);
+    boff += df;
+    map[i] = ((uint64_t)terms[i] << 32) | i;
+  }
+  bj.n_chunks = bj.c0[bj.n];
+  const size_t hist_b = 4ull * fg::kBandBins * bj.n, cnt_b = 4ull * fg::kBandTiers * bj.n_chunks;
+  AsyncTmp tmp;
+  if (fgh::dev_malloc_async(&tmp.p, hist_b + cnt_b + 16, kBuildStream) != hipSuccess)
+    return fail(FG_EOOM, "hipMallocAsync(%zu) failed", hist_b + cnt_b);
+  bj.hist = static_cast<uint32_t*>(tmp.p);
+  bj.cnt = bj.hist + (size_t)fg::kBandBins * bj.n;
+  HIPCHK(hipMemsetAsync(bj.hist, 0, hist_b, kBuildStream));
+  HIPCHK(fg::launch_band_hist(bj, grid_cap, kBuildStream));
+  std::vector<uint32_t> h((size_t)fg::kBandBins * bj.n), lo((size_t)(fg::kBandTiers - 1) * bj.n);
+  HIPCHK(hipMemcpyAsync(h.data(), bj.hist, hist_b, hipMemcpyDeviceToHost, kBuildStream));
+  HIPCHK(hipStreamSynchronize(kBuildStream));
+  // FUGU_BAND_SHARES=a:b:c:d (or commas): other cumulative tier shares, in sixteenths, ascending
+  uint32_t shares[fg::kBandTiers - 1];
+  std::copy(fg::kBandShares, fg::kBandShares + fg::kBandTiers - 1, shares);
+  if (const char* e = getenv("FUGU_BAND_SHARES")) {
+    unsigned a[4];
+    if (sscanf(e, "%u%*[,:]%u%*[,:]%u%*[,:]%u", &a[0], &a[1], &a[2], &a[3]) == 4 && a[0] >= 1 && a[0] <= a[1] && a[1] <= a[2] &&
+        a[2] <= a[3] && a[3] <= fg::kBandShareDen)
+      std::copy(a, a + 4, shares);
+  }
+  for (uint32_t i = 0; i < bj.n; ++i) {
+    fg::band_cuts(h.data() + (size_t)i * fg::kBandBins, bj.df[i], bj.lo[i], shares);
+    std::copy(bj.lo[i], bj.lo[i] + fg::kBandTiers - 1, lo.begin() + (size_t)i * (fg::kBandTiers - 1));
+  }
+  HIPCHK(fg::launch_band_copy(bj, grid_cap, kBuildStream));
+  std::sort(map.begin(), map.end());
+  ix->band_map = std::move(map);
+  ix->band_off = std::move(boffs);
+  ix->band_c0 = std::move(c0s);
+  ix->band_lo = std::move(lo);
+  return FG_OK;
+}
+
 // The bounds of a freshly built structure under its build statistics (which
 // are its current ones): the posting scores (k_score, with the block-max per
 // 2048 postings), bucket / term / tile maxima (k_bucket), sub-tile maxima
@@ -220,6 +307,16 @@ int build_bounds(fg_index* ix, const std::vector<uint32_t>& alive) {
   const uint64_t tab8_stride = ((uint64_t)ix->n_docs + 127) & ~127ull;
   std::vector<uint32_t> tabs8 = choose_doctab_terms(ix, tab8_stride, "FUGU_DOCTAB8_DIV", fg::kDocTab8Div, 1);
   const Parts::P p_dtab8 = tabs8.empty() ? Parts::P{} : L.add(tab8_stride * tabs8.size());
+  // ... then the densest terms' score-tiered lead copies
+  std::vector<uint32_t> bands = choose_band_terms(ix);
+  uint64_t band_post = 0, band_chunks = 0;
+  for (uint32_t t : bands) {
+    const uint64_t df = ix->off[t + 1] - ix->off[t];
+    band_post += df;
+    band_chunks += (df + fg::kChunk - 1) / fg::kChunk;
+  }
+  const Parts::P p_bdoc = bands.empty() ? Parts::P{} : L.add(4 * band_post), p_bpsc = bands.empty() ? Parts::P{} : L.add(4 * band_post),
+                 p_bcmax = bands.empty() ? Parts::P{} : L.add(4 * band_chunks);
   size_t total = L.total;
   if (!ix->spool) {
     ix->spool = std::make_shared<fgh::ScorePool>();
@@ -227,10 +324,11 @@ int build_bounds(fg_index* ix, const std::vector<uint32_t>& alive) {
   }
   auto sb = std::make_shared<fgh::ScoreBlock>();
   void* blk = ix->spool->get(total);
-  if (!blk && !(tabs.empty() && tabs8.empty())) {  // (a build never fails for want of the tables)
+  if (!blk && !(tabs.empty() && tabs8.empty() && bands.empty())) {  // (a build never fails for want of the tables)
     (void)hipGetLastError();
     tabs.clear();
     tabs8.clear();
+    bands.clear();
     total = bounds_total;
     blk = ix->spool->get(total);
   }
@@ -274,6 +372,14 @@ int build_bounds(fg_index* ix, const std::vector<uint32_t>& alive) {
   ix->dtab_bytes = 4ull * tab_stride * tabs.size();
   if (g_bt.on)
     fprintf(stderr, "[fg build] score tables: %zu terms, %.1f MiB\n", tabs.size(), (double)ix->dtab_bytes / (double)(1 << 20));
+  uint32_t* d_bdoc = bands.empty() ? nullptr : Parts::at<uint32_t>(blk, p_bdoc);
+  float *d_bpsc = bands.empty() ? nullptr : Parts::at<float>(blk, p_bpsc),
+        *d_bcmax = bands.empty() ? nullptr : Parts::at<float>(blk, p_bcmax);
+  if (d_bdoc)
+    if (int rc = build_bands(ix, bands, d_psc, d_bdoc, d_bpsc, d_bcmax, j.grid_cap)) return rc;
+  ix->band_bytes = bands.empty() ? 0 : 8 * band_post + 4 * band_chunks;
+  if (g_bt.on)
+    fprintf(stderr, "[fg build] tiered lead copies: %zu terms, %.1f MiB\n", bands.size(), (double)ix->band_bytes / (double)(1 << 20));
   j.alive = d_alive;
   j.bmax = d_bmax;
   j.tmaxs = d_tmaxs;
@@ -355,6 +461,9 @@ int build_bounds(fg_index* ix, const std::vector<uint32_t>& alive) {
   ix->d.dtab_stride = (uint32_t)tab_stride;
   ix->d.dtab8 = d_dtab8;
   ix->d.dtab8_stride = (uint32_t)tab8_stride;
+  ix->d.bdoc = d_bdoc;
+  ix->d.bpsc = d_bpsc;
+  ix->d.bcmax = d_bcmax;
   ix->d.alive = d_alive;
   ix->device_bytes = ix->struct_bytes + total;
   return FG_OK;

@@ -434,6 +434,14 @@ struct IndexBounds {
   // the one-byte bound tables (DevIndex::dtab8, in sblock), the same way (doctab8_slot)
   SharedVec<uint64_t> dtab8_map;
   uint64_t dtab8_bytes = 0;
+  // the score-tiered lead copies (DevIndex::bdoc / bpsc / bcmax, in sblock): (term << 32) | copy of each
+  // term that has one, ascending by term (band_slot); per copy its first posting in bdoc / bpsc, its first
+  // chunk in bcmax and its kBandTiers - 1 cuts (fg::band_cuts); their bytes
+  SharedVec<uint64_t> band_map;
+  SharedVec<uint64_t> band_off;
+  SharedVec<uint32_t> band_c0;
+  SharedVec<uint32_t> band_lo;
+  uint64_t band_bytes = 0;
   uint64_t device_bytes = 0;
 };
 
@@ -448,6 +456,28 @@ inline uint32_t doctab_lead() {
 inline uint32_t doctab_slot(const IndexBounds& b, uint32_t t) {
   const auto it = std::lower_bound(b.dtab_map.begin(), b.dtab_map.end(), (uint64_t)t << 32);
   return it != b.dtab_map.end() && (uint32_t)(*it >> 32) == t ? (uint32_t)*it + 1u : 0u;
+}
+
+// the score-tiered copy of local term t: its index + 1, or 0
+inline uint32_t band_slot(const IndexBounds& b, uint32_t t) {
+  const auto it = std::lower_bound(b.band_map.begin(), b.band_map.end(), (uint64_t)t << 32);
+  return it != b.band_map.end() && (uint32_t)(*it >> 32) == t ? (uint32_t)*it + 1u : 0u;
+}
+
+// a plan leads Must-driven queries of >= 2 lists from the lead term's tiered
+// copy: FUGU_BAND_LEAD, read when a plan is made, on unless set to 0
+inline bool band_lead() {
+  const char* e = getenv("FUGU_BAND_LEAD");
+  return !(e && *e) || atol(e) != 0;
+}
+
+// ... only where the other lists' summed maxima (q_ub[1]) are at most FUGU_BAND_UB_RATIO times the lead
+// term's own maximum (default 2; 0: always): the chunk bound is the chunk's best lead score plus that sum,
+// so a query whose other lists outweigh its lead skips little and only loses the doc order of its probes
+inline float band_ub_ratio() {
+  const char* e = getenv("FUGU_BAND_UB_RATIO");
+  const double v = e && *e ? atof(e) : 2.0;
+  return v > 0.0 ? (float)v : 0.0f;
 }
 
 // lead candidates per 128-doc line from which a plan attaches a bound table to
@@ -520,6 +550,7 @@ struct fg_plan {
   fg_index* ix = nullptr;
   // nq: query slots = n_segs x nq_batch (one snapshot: the batch's queries)
   uint32_t nq = 0, k = 0, total_chunks = 0, n_scan = 0, nq_batch = 0, n_segs = 1;
+  uint32_t n_tiered = 0;  // query slots that lead from a score-tiered copy (DevPlan::q_tier; fg_plan_tiered_slots)
   std::vector<fg_index*> segs;  // a multi-snapshot plan's snapshots after ix (retained)
   int mode = FG_MODE_AND;
   fg::DevPlan d{};

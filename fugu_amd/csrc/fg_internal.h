@@ -87,6 +87,59 @@ constexpr uint32_t kDocTabMinDocs = 8192; // a snapshot of fewer docs (a commit'
 #endif
 constexpr uint32_t kDocTab8Div = FG_DOCTAB8_DIV;
 constexpr uint32_t kDocTab8Lead = FG_DOCTAB8_LEAD;
+// Score-tiered lead copies (DevIndex::bdoc / bpsc / bcmax) of the densest terms:
+// a second copy of the term's postings, stably partitioned into kBandTiers tiers
+// by build-time score (docs ascend inside a tier), with the exact maximum of
+// every kChunk postings of the copy.  A conjunction that leads from the copy
+// skips the chunks whose maximum cannot pass the first MaxScore bound, as a
+// single-list query skips by cmax.  A term in >= 1/kBandDiv of the
+// docs (env FUGU_BAND_DIV, 0: none) of a snapshot of >= kBandMinDocs docs (env
+// FUGU_BAND_MIN_DOCS), densest first, at most kBandMax terms and within
+// 1/kBandFrac (env FUGU_BAND_FRAC, 0: no cap) of the snapshot's posting bytes
+// (12 B each, as the rank budget counts them).
+#ifndef FG_BAND_DIV
+#define FG_BAND_DIV 8
+#endif
+constexpr uint32_t kBandDiv = FG_BAND_DIV;
+constexpr uint32_t kBandMinDocs = 8192;
+constexpr uint32_t kBandMax = 64;         // copies per snapshot (BandJob rides in the kernel arguments)
+constexpr uint32_t kBandFrac = 4;
+constexpr uint32_t kBandTiers = 5;
+// tiers 0..i together hold about kBandShares[i] / kBandShareDen of the postings, the best scores first
+// (a tier's chunks span 1 / its share of the doc range a doc-ordered chunk spans, so the probes of a small
+// top tier share fewer lines: 1, 2, 4, 8 sixteenths ran the headline 0.831 ms against the parent's 0.817,
+// 4, 8, 12, 14 ran it 0.748: DESIGN.md §3, profiles/lead_bands/)
+constexpr uint32_t kBandShareDen = 16;
+constexpr uint32_t kBandShares[kBandTiers - 1] = {4, 8, 12, 14};
+// the cuts come from a histogram of the scores' f32 bits >> kBandShift (128 bins per octave)
+constexpr uint32_t kBandShift = 16;
+constexpr uint32_t kBandBins = 1u << 15;  // scores are finite and >= 0: bits < 2^31
+__host__ __device__ inline uint32_t band_bin(uint32_t bits) {
+  const uint32_t b = bits >> kBandShift;
+  return b < kBandBins ? b : kBandBins - 1;
+}
+// The cuts of a term from its histogram h[kBandBins] of df postings: lo[i] is the
+// lowest bin of tiers 0..i, the highest bin b such that the bins >= b hold at
+// least df * kBandShares[i] / kBandShareDen postings (and at least one).  A bin --
+// so every class of equal scores -- lies wholly in one tier.
+// (shares: other cumulative shares than kBandShares, ascending, in 1/kBandShareDen: env FUGU_BAND_SHARES)
+__host__ __device__ inline void band_cuts(const uint32_t* h, uint64_t df, uint32_t* lo /*[kBandTiers - 1]*/,
+                                          const uint32_t* shares = nullptr) {
+  uint64_t cum = 0;
+  uint32_t i = 0;
+  for (uint32_t b = kBandBins; b-- > 0 && i < kBandTiers - 1;) {
+    cum += h[b];
+    while (i < kBandTiers - 1 && cum > 0 && cum * kBandShareDen >= df * (shares ? shares[i] : kBandShares[i])) lo[i++] = b;
+  }
+  while (i < kBandTiers - 1) lo[i++] = 0;
+}
+// ... and the tier of a score under them: the number of cuts above its bin
+__host__ __device__ inline uint32_t band_tier(uint32_t bits, const uint32_t* lo) {
+  const uint32_t b = band_bin(bits);
+  uint32_t t = 0;
+  for (uint32_t i = 0; i < kBandTiers - 1; ++i) t += b < lo[i] ? 1u : 0u;
+  return t;
+}
 constexpr uint32_t kRankChunkWords = 2048;  // k_rank: words (65536 docs) per workgroup
 #ifndef FG_DISJ_GPQ
 #define FG_DISJ_GPQ 64
@@ -350,6 +403,11 @@ struct DevIndex {
                              //     for a posting, 0 where the term is absent.  k_conj reads them through the
                              //     bound fields of clause 1's probe descriptor (kPdBound); which term owns which
                              //     table: fg_index::dtab8_map (host)
+  const uint32_t* bdoc;      // [band postings] the score-tiered copies of the densest terms' doc ids (kBand*):
+                             //     a term's df postings tier by tier, docs ascending inside a tier; which term
+                             //     owns which run: fg_index::band_map (host)
+  const float* bpsc;         // [band postings] ... and their build-time scores, the psc values bit for bit
+  const float* bcmax;        // [band chunks] the largest score of each kChunk postings of a term's copy
   const uint32_t* fdoc;      // [PF] facet postings (doc ids, ascending), CSR by facet term
   const uint64_t* foff;      // [VF+1]
   uint64_t n_esc;
@@ -465,7 +523,8 @@ inline bool probe_uses_table(uint64_t n_docs, uint64_t df, uint64_t lead_df, uin
 // (every array is < 2^47 bytes, so its base below 2^47 covers its end)
 inline bool probe_addr_ok(const DevIndex& ix) {
   for (const void* p : {(const void*)ix.doc, (const void*)ix.psc, (const void*)ix.tfn, (const void*)ix.dir,
-                        (const void*)ix.rank, (const void*)ix.srank, (const void*)ix.dtab, (const void*)ix.dtab8})
+                        (const void*)ix.rank, (const void*)ix.srank, (const void*)ix.dtab, (const void*)ix.dtab8,
+                        (const void*)ix.bdoc, (const void*)ix.bpsc})
     if ((uint64_t)(uintptr_t)p >> 47) return false;
   return true;
 }
@@ -554,6 +613,17 @@ inline bool probe_desc_bound(const DevIndex& ix, ProbeDesc& lead, ProbeDesc& p1,
   return true;
 }
 
+// The lead descriptor of a slot that leads from its term's score-tiered copy
+// (build-time plans only): the doc ids and scores of the copy at posting boff of
+// bdoc / bpsc in place of the doc-ordered list's; sizes, aux and ub stay.  The
+// slot's DevPlan::q_tier word tells the kernel, and where the chunk maxima lie.
+inline void probe_desc_tier(const DevIndex& ix, ProbeDesc& lead, uint64_t boff) {
+  const uint64_t base = (uint64_t)(uintptr_t)(ix.bdoc + boff), sc = (uint64_t)(uintptr_t)(ix.bpsc + boff);
+  lead.base_lo = (uint32_t)base;
+  lead.sc_lo = (uint32_t)sc;
+  lead.hi = (uint32_t)((base >> 32) & 0xFFFFu) | (uint32_t)((sc >> 32) & 0xFFFFu) << 16;
+}
+
 // Facet filters of a planned batch (DevPlan).  Every distinct clause list
 // (filter) gets a doc-indexed mask in HBM built by k_fmask from the facet
 // postings: 2^shift bits per doc (shift 0..3, >= the filter's clause count),
@@ -609,6 +679,9 @@ struct DevPlan {
   const ProbeDesc* q_probe;     // [nq * kMaxTerms] k_conj's probe descriptors, on the slot's own snapshot: entry 0
                                 //     the lead list's, entry i the i-th probed list's (q_terms order) with
                                 //     q_ub[i + 1]; the first qm_terms entries of a k_conj slot are filled
+  const uint32_t* q_tier;       // [nq] a k_conj slot that leads from its lead term's score-tiered copy (entry 0
+                                //     of q_probe points at bdoc / bpsc): 1 + the index in DevIndex::bcmax of the
+                                //     copy's first chunk; 0: the doc-ordered list
   const float* q_wt;            // [nq * kMaxTerms] each clause's BM25 weight, text field (query time)
   const float* q_wn;            // [nq * kMaxTerms] ... and name field
   const float* q_rup;           // [nq * kMaxTerms] factor on the clause's build-time bounds (tmax, bmax,
@@ -627,6 +700,10 @@ struct DevPlan {
                                 // (tfn_name) and bit 1 escaped tf bytes (esc_pos); the kernels are instantiated
                                 // per value (0, 4 = query-time, 7 = query-time with names / escapes)
   uint32_t opts;                // planner settings read when the plan is made: kOptConjHistThr
+  uint32_t xcd_first[9];        // k_conj's multi-list items by XCD, when the planner balanced them by expected
+                                // work (tiered leads: items that mostly skip): XCD x runs the items
+                                // [xcd_first[x], xcd_first[x + 1]) after the n_single first; xcd_first[8] = 0:
+                                // equal counts
   uint32_t n_single;            // k_conj: the first n_single work items belong to single-list queries
   uint32_t n_scan;              // k_scan work items (queries with no text terms), after the total_chunks
                                 // k_conj / k_disj items in work_q / work_c / work_n
@@ -831,6 +908,31 @@ struct DocTab8Job {
   uint32_t df[kDocTabMax];
   uint64_t off[kDocTabMax];
 };
+
+// The score-tiered copies of a build (k_band_*): copy i takes the postings
+// [off[i], off[i] + df[i]) of the snapshot into bdoc / bpsc at boff[i], its
+// chunks are c0[i] .. c0[i + 1] of bcmax.  launch_band_hist fills hist (zeroed:
+// kBandBins per copy) and the host cuts it (band_cuts -> lo); launch_band_copy
+// counts every source chunk's postings per tier (cnt: per copy, tier-major),
+// scans them into first positions, scatters and takes the copy's chunk maxima.
+struct BandJob {
+  const uint32_t* doc;
+  const float* psc;
+  uint32_t* bdoc;
+  float* bpsc;
+  float* bcmax;
+  uint32_t* hist;   // [n * kBandBins] temporary, zeroed
+  uint32_t* cnt;    // [n_chunks * kBandTiers] temporary
+  uint32_t n;       // copies
+  uint32_t n_chunks;
+  uint32_t df[kBandMax];
+  uint32_t c0[kBandMax + 1];
+  uint64_t off[kBandMax];
+  uint64_t boff[kBandMax];
+  uint32_t lo[kBandMax][kBandTiers - 1];
+};
+hipError_t launch_band_hist(const BandJob& j, uint32_t grid_cap, hipStream_t s);
+hipError_t launch_band_copy(const BandJob& j, uint32_t grid_cap, hipStream_t s);
 
 // The forward index of ONE field from positional postings (fg_index_build_positional,
 // DESIGN.md §13; k_fwd_*).  posting p of the snapshot (doc[p], CSR by term in off)

@@ -774,6 +774,34 @@ int fg_index_doctab8_get(const fg_index* ix, uint32_t* n_terms, uint64_t* bytes)
   return FG_OK;
 }
 
+int fg_index_bands_get(const fg_index* ix, uint32_t* n_terms, uint64_t* bytes) {
+  if (!ix) return fail(FG_EINVAL, "bad arguments");
+  if (n_terms) *n_terms = (uint32_t)ix->band_map.size();
+  if (bytes) *bytes = ix->band_bytes;
+  return FG_OK;
+}
+
+int fg_index_band_read(const fg_index* ix, uint32_t term, int source, uint32_t* doc, float* score, uint64_t cap,
+                       float* cmax, uint32_t* cuts, uint64_t* n) {
+  if (!ix || !n) return fail(FG_EINVAL, "bad arguments");
+  *n = 0;
+  term = fgh::local_term(ix, term);
+  if (term >= ix->n_terms) return FG_OK;
+  const uint32_t b = fgh::band_slot(*ix, term);
+  if (!b) return FG_OK;
+  const uint64_t df = ix->off[term + 1] - ix->off[term], nch = (df + fg::kChunk - 1) / fg::kChunk;
+  *n = df;
+  if ((doc || score || cmax) && cap < df) return fail(FG_EINVAL, "%llu postings, room for %llu", (unsigned long long)df, (unsigned long long)cap);
+  HIPCHK(hipSetDevice(ix->dev));
+  const uint32_t* d_doc = source ? ix->d.doc + ix->off[term] : ix->d.bdoc + ix->band_off[b - 1];
+  const float* d_sc = source ? ix->d.psc + ix->off[term] : ix->d.bpsc + ix->band_off[b - 1];
+  if (doc) HIPCHK(hipMemcpy(doc, d_doc, 4 * df, hipMemcpyDeviceToHost));
+  if (score) HIPCHK(hipMemcpy(score, d_sc, 4 * df, hipMemcpyDeviceToHost));
+  if (cmax) HIPCHK(hipMemcpy(cmax, ix->d.bcmax + ix->band_c0[b - 1], 4 * nch, hipMemcpyDeviceToHost));
+  if (cuts) std::copy(ix->band_lo.begin() + (size_t)(b - 1) * (fg::kBandTiers - 1), ix->band_lo.begin() + (size_t)b * (fg::kBandTiers - 1), cuts);
+  return FG_OK;
+}
+
 uint64_t fg_index_df(const fg_index* ix, int field, uint32_t term) {
   if (ix && field == FG_FIELD_FACET) return term < ix->n_fterms ? ix->df_facet[term] : 0;
   if (!ix) return 0;

@@ -813,8 +813,20 @@ __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPl
   // doc sweep, so its L2 holds one doc window of the hot lists.
   const uint32_t nwg = gridDim.x, bid = blockIdx.x;
   const uint32_t xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const uint32_t w = (kSingle ? 0u : pl.n_single) +
-                     (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  uint32_t w = (kSingle ? 0u : pl.n_single) +
+               (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  if (!kSingle && pl.xcd_first[8]) {
+    // stretches of the planner's own (balanced by expected work): the grid holds the
+    // longest one for every XCD, the workgroups past a shorter one end here
+    uint32_t f = 0, e = 0;
+#pragma unroll
+    for (uint32_t x = 0; x < 8; ++x) {
+      f = xcd == x ? pl.xcd_first[x] : f;
+      e = xcd == x ? pl.xcd_first[x + 1] : e;
+    }
+    if ((bid >> 3) >= e - f) return;
+    w = pl.n_single + f + (bid >> 3);
+  }
 
   uint64_t t_start = FG_NOW(), t_probe = 0, t_keys = 0, t_sel = 0, n_app = 0;
   (void)t_start; (void)t_probe; (void)t_keys; (void)t_sel; (void)n_app;
@@ -838,6 +850,8 @@ __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPl
   const float* qwn = pl.q_wn + (size_t)q * kMaxTerms;
   const uint32_t K = pl.k;
   const uint32_t lead_df = pl.q_lead_df[q];
+  // a slot that leads from its term's score-tiered copy (DevPlan::q_tier; uniform)
+  const uint32_t tier = kSingle ? 0u : pl.q_tier[q];
   unsigned long long* gthr = reinterpret_cast<unsigned long long*>(&pl.thresh[ql]);
   // facet filter (uniform per work item): Bool[Must(text), Must(facet union)]
   const uint32_t fslot = pl.f.q_filter[q];
@@ -880,9 +894,27 @@ __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPl
   // maximum) cannot reach the threshold is not loaded.  thr_k is the threshold
   // as every thread last saw it (uniform), so the skip is uniform too.  The
   // build-time chunk maxima scale by the lead's bound factor (DevPlan::q_rup).
-  const float* __restrict__ cmax = ix.cmax + (kSingle ? ix.coff[terms[0]] : 0u);
+  // A tiered lead (score-tiered copy: the chunks of its low tiers hold low
+  // scores only) skips the same way on the copy's chunk maxima plus the bound of
+  // the first MaxScore test, ub0 = q_ub[1] (the lead descriptor's ub) + fmax:
+  // every posting of the chunk has s0 <= bcmax[c], f32 addition and
+  // inflate_bound are monotone and doc 0 gives the largest key of a score, so
+  // a skipped chunk holds only candidates the first bound would drop at this
+  // same threshold.  Such an item waits for the reply of its first exchange, so
+  // it can skip from its first chunk on; one that skipped every chunk holds no
+  // keys and ends after its exchanges (no bins, no candidates).
+  const float* __restrict__ cmax = kSingle ? ix.cmax + ix.coff[terms[0]] : ix.bcmax + (tier ? tier - 1u : 0u);
   const float rup0 = pl.q_rup[(size_t)q * kMaxTerms];
+  const float ub0 = (tier ? pl.q_ub[(size_t)q * kMaxTerms + 1] : 0.0f) + fmax;
   uint64_t thr_k = thr0;
+  bool loaded = false;  // (uniform) some chunk was not skipped
+  uint32_t n_skip = 0;
+  (void)n_skip;
+  if (!kSingle && tier) {
+    if (tid == 0 && pend > sh.thr) sh.thr = pend;
+    __syncthreads();
+    thr_k = sh.thr;
+  }
   // pure conjunctions (the multi-snapshot instantiation too: without deferred
   // probes it fits 128 VGPRs with no scratch, but C4 ran 1.44 -> 1.57 ms,
   // profiles/r04/ab/ab_multi_defer_c4.log)
@@ -892,7 +924,15 @@ __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPl
     const uint32_t c = c0 + cc;
     uint64_t tp0 = FG_NOW(), tp1 = tp0;
     (void)tp0; (void)tp1;
-    if (!kSingle || make_key(inflate_bound(cmax[c] * rup0 + fmax), 0u) >= thr_k) {
+    const bool skip = kSingle ? make_key(inflate_bound(cmax[c] * rup0 + fmax), 0u) < thr_k
+                              : tier != 0 && make_key(inflate_bound(cmax[c] * rup0 + ub0), 0u) < thr_k;
+    if (!kSingle && skip) {
+      // nothing of the item changed: its tail (flush, select, publication) waits for the last chunk
+      ++n_skip;
+      if (cc + 1 < nc) continue;
+    }
+    if (!skip) {
+    loaded = true;
     const uint32_t cnt = min(kChunk, lead_df - c * kChunk);
     // the chunk's doc ids and scores (or payloads) through two resources over the
     // chunk's own window of the lead descriptor's ranges (a list of any length:
@@ -1125,6 +1165,9 @@ __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPl
     }
   }
   if (tid == 0 && pend > sh.thr) sh.thr = pend;
+  uint32_t total = 0;
+  // (a tiered item that skipped all its chunks: no keys, nothing to count or write)
+  if (kSingle || !tier || loaded) {
   // count the item's kept keys (distinct docs of its own lead chunks) into the
   // query's bins, through LDS bins (sh.hist is free once the last select ran)
   {
@@ -1164,7 +1207,8 @@ __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPl
   __syncthreads();
 
   // write the kept keys that still clear the freshest threshold
-  const uint32_t total = flush_candidates(pl, q, sh.buf, sh.n_buf, sh.thr, sh.scratch);
+  total = flush_candidates(pl, q, sh.buf, sh.n_buf, sh.thr, sh.scratch);
+  }
   (void)total;
   FG_STAMP(w, 0, t_start);
   FG_STAMP(w, 1, t_probe);
@@ -1172,7 +1216,7 @@ __global__ __launch_bounds__(kThreads, FG_WAVES) void k_conj(DevIndex ix0, DevPl
   FG_STAMP(w, 3, t_sel);
   FG_STAMP(w, 4, FG_NOW());
   FG_STAMP(w, 5, n_app);
-  FG_STAMP(w, 6, ((uint64_t)nc << 40) | ((uint64_t)m << 32) | q);
+  FG_STAMP(w, 6, ((uint64_t)n_skip << 48) | ((uint64_t)nc << 40) | ((uint64_t)m << 32) | q);  // (bits 48-55: chunks skipped)
   FG_STAMP(w, 7, total);
 #ifdef FG_DIAG
   __syncthreads();
@@ -2620,7 +2664,19 @@ hipError_t launch_conj(const DevIndex& ix, const DevPlan& pl, hipStream_t s) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  if (pl.n_conj > pl.n_single) conj_launch_f<false>(ix, pl, pl.n_conj - pl.n_single, s);
+  if (pl.n_conj > pl.n_single) {
+    uint32_t grid = pl.n_conj - pl.n_single;
+    if (pl.xcd_first[8]) {
+      if (pl.xcd_first[8] != grid) return hipErrorInvalidValue;
+      uint32_t longest = 0;
+      for (uint32_t x = 0; x < 8; ++x) {
+        if (pl.xcd_first[x + 1] < pl.xcd_first[x]) return hipErrorInvalidValue;
+        longest = std::max(longest, pl.xcd_first[x + 1] - pl.xcd_first[x]);
+      }
+      grid = 8 * longest;
+    }
+    conj_launch_f<false>(ix, pl, grid, s);
+  }
   return hipGetLastError();
 }
 
@@ -2824,6 +2880,205 @@ hipError_t launch_doctab8(const DocTab8Job& j, uint32_t grid_cap, hipStream_t s)
   // (p + gridDim.x * kThreads stays below 2^32: df < 2^31, at most 2^15 workgroups per table)
   const uint32_t gx = std::min<uint32_t>((dfmax + kThreads - 1) / kThreads, std::max<uint32_t>(1u, std::min(cap, 0x8000u) / j.n));
   k_dtab8_scatter<<<dim3(gx, j.n), kThreads, 0, s>>>(j);
+  return hipGetLastError();
+}
+
+// Snapshot build: the score-tiered copies of the densest terms (DevIndex::bdoc /
+// bpsc / bcmax, BandJob).  A work item is one kChunk-posting chunk of one copy
+// (chunk ch of the job: copy i with c0[i] <= ch < c0[i + 1]), in steps of the grid.
+//   k_band_hist     the copy's histogram of score bins (band_bin), through an LDS
+//                   window below the chunk's highest bin;
+//   (host)          band_cuts over each histogram -> BandJob::lo;
+//   k_band_count    postings per tier of every SOURCE chunk, cnt[c0[i] * T + t * nch + c];
+//   k_band_scan     one workgroup per copy: exclusive scan of its cnt run, so
+//                   tier-major, chunk-minor: cnt = first position of (tier, chunk);
+//   k_band_scatter  every posting to first position + its rank among the chunk's
+//                   postings of its tier in list order (a lane holds kItems
+//                   consecutive postings): a stable partition, docs ascending
+//                   inside a tier, scores copied bit for bit;
+//   k_band_cmax     the exact maximum of every chunk of the copy.
+// Every store is checked against the copy's length.
+constexpr uint32_t kBandWin = 1024;  // bins in k_band_hist's LDS window (8 octaves)
+
+__device__ inline uint32_t band_copy_of(const BandJob& j, uint32_t ch) {
+  uint32_t i = 0;
+  while (i + 1 < j.n && ch >= j.c0[i + 1]) ++i;
+  return i;
+}
+
+__global__ __launch_bounds__(kThreads) void k_band_hist(BandJob j) {
+  __shared__ uint32_t s_h[kBandWin];
+  __shared__ uint32_t s_top;
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t ch = blockIdx.x; ch < j.n_chunks; ch += gridDim.x) {
+    const uint32_t i = band_copy_of(j, ch), df = j.df[i], p0 = (ch - j.c0[i]) * kChunk;
+    const uint32_t* __restrict__ sc = reinterpret_cast<const uint32_t*>(j.psc) + j.off[i];
+    uint32_t* __restrict__ gh = j.hist + (size_t)i * kBandBins;
+    for (uint32_t b = tid; b < kBandWin; b += kThreads) s_h[b] = 0;
+    if (tid == 0) s_top = 0;
+    __syncthreads();
+    uint32_t bin[kItems], top = 0;
+#pragma unroll
+    for (uint32_t x = 0; x < kItems; ++x) {
+      const uint32_t p = p0 + x * kThreads + tid;
+      bin[x] = p < df ? band_bin(sc[p]) : kInvalid;
+      if (p < df) top = max(top, bin[x]);
+    }
+    atomicMax(&s_top, top);
+    __syncthreads();
+    top = s_top;
+#pragma unroll
+    for (uint32_t x = 0; x < kItems; ++x) {
+      if (bin[x] == kInvalid) continue;
+      const uint32_t d = top - bin[x];
+      if (d < kBandWin) atomicAdd(&s_h[d], 1u);
+      else atomicAdd(&gh[bin[x]], 1u);
+    }
+    __syncthreads();
+    for (uint32_t b = tid; b < kBandWin && b <= top; b += kThreads)
+      if (s_h[b]) atomicAdd(&gh[top - b], s_h[b]);
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void k_band_count(BandJob j) {
+  __shared__ uint32_t s_c[kBandTiers];
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t ch = blockIdx.x; ch < j.n_chunks; ch += gridDim.x) {
+    const uint32_t i = band_copy_of(j, ch), df = j.df[i], c = ch - j.c0[i], p0 = c * kChunk;
+    const uint32_t nch = j.c0[i + 1] - j.c0[i];
+    const uint32_t* __restrict__ sc = reinterpret_cast<const uint32_t*>(j.psc) + j.off[i];
+    if (tid < kBandTiers) s_c[tid] = 0;
+    __syncthreads();
+    const uint32_t lo[kBandTiers - 1] = {j.lo[i][0], j.lo[i][1], j.lo[i][2], j.lo[i][3]};
+    uint32_t n[kBandTiers] = {0, 0, 0, 0, 0};
+#pragma unroll
+    for (uint32_t x = 0; x < kItems; ++x) {
+      const uint32_t p = p0 + x * kThreads + tid;
+      if (p < df) {
+        const uint32_t t = band_tier(sc[p], lo);
+#pragma unroll
+        for (uint32_t u = 0; u < kBandTiers; ++u) n[u] += t == u ? 1u : 0u;
+      }
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < kBandTiers; ++u)
+      if (n[u]) atomicAdd(&s_c[u], n[u]);
+    __syncthreads();
+    if (tid < kBandTiers) j.cnt[(size_t)j.c0[i] * kBandTiers + (size_t)tid * nch + c] = s_c[tid];
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void k_band_scan(BandJob j) {
+  __shared__ uint32_t scratch[8];
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t i = blockIdx.x; i < j.n; i += gridDim.x) {
+    uint32_t* __restrict__ a = j.cnt + (size_t)j.c0[i] * kBandTiers;
+    const uint32_t n = (j.c0[i + 1] - j.c0[i]) * kBandTiers;
+    uint32_t carry = 0;
+    for (uint32_t b = 0; b < n; b += kThreads) {
+      const uint32_t v = b + tid < n ? a[b + tid] : 0u;
+      const uint32_t before = block_exclusive_scan(v, scratch);
+      if (b + tid < n) a[b + tid] = carry + before;
+      if (tid == kThreads - 1) scratch[4] = before + v;
+      __syncthreads();
+      carry += scratch[4];
+      __syncthreads();
+    }
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void k_band_scatter(BandJob j) {
+  __shared__ uint32_t scratch[8];
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t ch = blockIdx.x; ch < j.n_chunks; ch += gridDim.x) {
+    const uint32_t i = band_copy_of(j, ch), df = j.df[i], c = ch - j.c0[i], p0 = c * kChunk + tid * kItems;
+    const uint32_t nch = j.c0[i + 1] - j.c0[i];
+    const uint32_t* __restrict__ sd = j.doc + j.off[i];
+    const uint32_t* __restrict__ sc = reinterpret_cast<const uint32_t*>(j.psc) + j.off[i];
+    uint32_t* __restrict__ od = j.bdoc + j.boff[i];
+    uint32_t* __restrict__ os = reinterpret_cast<uint32_t*>(j.bpsc) + j.boff[i];
+    const uint32_t lo[kBandTiers - 1] = {j.lo[i][0], j.lo[i][1], j.lo[i][2], j.lo[i][3]};
+    // the lane's kItems consecutive postings and their tiers
+    uint32_t d[kItems], s[kItems], t[kItems], n[kBandTiers] = {0, 0, 0, 0, 0};
+#pragma unroll
+    for (uint32_t x = 0; x < kItems; ++x) {
+      const bool in = p0 + x < df;
+      d[x] = in ? sd[p0 + x] : 0u;
+      s[x] = in ? sc[p0 + x] : 0u;
+      t[x] = in ? band_tier(s[x], lo) : kBandTiers;
+#pragma unroll
+      for (uint32_t u = 0; u < kBandTiers; ++u) n[u] += t[x] == u ? 1u : 0u;
+    }
+    // per tier: the first position of (tier, chunk) + the postings of the lanes before
+    uint32_t at[kBandTiers];
+#pragma unroll
+    for (uint32_t u = 0; u < kBandTiers; ++u)
+      at[u] = j.cnt[(size_t)j.c0[i] * kBandTiers + (size_t)u * nch + c] + block_exclusive_scan(n[u], scratch);
+#pragma unroll
+    for (uint32_t x = 0; x < kItems; ++x) {
+#pragma unroll
+      for (uint32_t u = 0; u < kBandTiers; ++u) {
+        if (t[x] != u) continue;
+        const uint32_t o = at[u]++;
+        if (o < df) {
+          od[o] = d[x];
+          os[o] = s[x];
+        }
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void k_band_cmax(BandJob j) {
+  __shared__ uint32_t s_max;
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t ch = blockIdx.x; ch < j.n_chunks; ch += gridDim.x) {
+    const uint32_t i = band_copy_of(j, ch), df = j.df[i], p0 = (ch - j.c0[i]) * kChunk;
+    const uint32_t* __restrict__ sc = reinterpret_cast<const uint32_t*>(j.bpsc) + j.boff[i];
+    if (tid == 0) s_max = 0;
+    __syncthreads();
+    uint32_t mx = 0;  // (scores are >= 0: the f32 bits order as the scores)
+#pragma unroll
+    for (uint32_t x = 0; x < kItems; ++x) {
+      const uint32_t p = p0 + x * kThreads + tid;
+      if (p < df) mx = max(mx, sc[p]);
+    }
+    atomicMax(&s_max, mx);
+    __syncthreads();
+    if (tid == 0) j.bcmax[ch] = __uint_as_float(s_max);
+    __syncthreads();
+  }
+}
+
+static bool band_job_ok(const BandJob& j) {
+  if (j.n == 0 || j.n > kBandMax || j.c0[0] != 0 || j.c0[j.n] != j.n_chunks) return false;
+  for (uint32_t i = 0; i < j.n; ++i)
+    if (j.df[i] == 0 || j.df[i] >= 0x80000000u || j.c0[i + 1] - j.c0[i] != (j.df[i] + kChunk - 1) / kChunk) return false;
+  return true;
+}
+
+hipError_t launch_band_hist(const BandJob& j, uint32_t grid_cap, hipStream_t s) {
+  if (j.n == 0) return hipSuccess;
+  if (!band_job_ok(j)) return hipErrorInvalidValue;
+  const uint32_t cap = grid_cap ? grid_cap : 0x10000u;
+  k_band_hist<<<std::min(j.n_chunks, cap), kThreads, 0, s>>>(j);
+  return hipGetLastError();
+}
+
+hipError_t launch_band_copy(const BandJob& j, uint32_t grid_cap, hipStream_t s) {
+  if (j.n == 0) return hipSuccess;
+  if (!band_job_ok(j)) return hipErrorInvalidValue;
+  const uint32_t cap = grid_cap ? grid_cap : 0x10000u, g = std::min(j.n_chunks, cap);
+  k_band_count<<<g, kThreads, 0, s>>>(j);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  k_band_scan<<<std::min(j.n, cap), kThreads, 0, s>>>(j);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  k_band_scatter<<<g, kThreads, 0, s>>>(j);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  k_band_cmax<<<g, kThreads, 0, s>>>(j);
   return hipGetLastError();
 }
 

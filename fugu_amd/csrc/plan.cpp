@@ -42,6 +42,7 @@ struct WItem { double key; uint32_t q, c, n; };
 struct PlanTables {
   // per query (slot); the q_terms .. q_rup rows hold kMaxTerms entries each
   std::vector<uint32_t> q_m, q_terms, lead, q_filter, ngroup, q_hlo, q_hhi, q_hsh;
+  std::vector<uint32_t> q_tier;  // DevPlan::q_tier: slots that lead from a score-tiered copy
   std::vector<uint32_t> q_pterm, q_ppos;  // phrase queries' (term, offset) rows; empty without phrase_len
   std::vector<uint64_t> thr0;
   std::vector<float> q_ub, q_wt, q_wn, q_rup;
@@ -60,7 +61,7 @@ struct PlanTables {
   void clear() {
     auto all = [](auto&... v) { (v.clear(), ...); };
     all(q_m, q_terms, lead, q_filter, ngroup, q_hlo, q_hhi, q_hsh, thr0, q_ub, q_wt, q_wn, q_rup, f_shift, f_seg, f_woff,
-        f_tab, f_max, ch_f, ch_c, ch_t, ch_s, citems, ditems, scan, phrase, items, q_pterm, q_ppos, q_probe);
+        f_tab, f_max, ch_f, ch_c, ch_t, ch_s, citems, ditems, scan, phrase, items, q_pterm, q_ppos, q_probe, q_tier);
     nf = 0;
   }
 };
@@ -163,9 +164,11 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
   const uint64_t N = ix->n_docs;
   const bool disj = q->mode == FG_MODE_OR;
   const uint32_t tab_lead = fgh::doctab_lead(), tab8_lead = fgh::doctab8_lead();
+  const bool tiers = !qtime && !ix->band_map.empty() && fgh::band_lead();
+  const float tier_ratio = fgh::band_ub_ratio();
   h.clear();
   const size_t nqt = (size_t)nq * fg::kMaxTerms;
-  for (auto* v : {&h.q_m, &h.lead}) v->assign(nq, 0);
+  for (auto* v : {&h.q_m, &h.lead, &h.q_tier}) v->assign(nq, 0);
   h.q_terms.assign(nqt, 0);
   h.thr0.assign(nq, 0);
   for (auto* v : {&h.q_ub, &h.q_wt, &h.q_wn}) v->assign(nqt, 0.0f);
@@ -429,6 +432,14 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
       if (!qtime && !ix->dtab8_map.empty() && mt >= 3 && nm == mt && flt == 0xFFFFFFFFu)
         fg::probe_desc_bound(ix->d, h.q_probe[row], h.q_probe[row + 1], fgh::doctab8_slot(*ix, qt[1]), ix->tmaxs[qt[1]],
                              true, qtime, ix->off[qt[1] + 1] - ix->off[qt[1]], lead_df, tab8_lead);
+      // a query of >= 2 lists on build-time scores leads from its lead term's score-tiered
+      // copy when the term has one: the same postings tier-major, so the sweep runs the
+      // query's best tier first and k_conj skips the chunks the first bound would empty
+      if (tiers && mt >= 2 && (tier_ratio == 0.0f || h.q_ub[row + 1] <= tier_ratio * cm[0]))
+        if (const uint32_t b = fgh::band_slot(*ix, qt[0])) {
+          fg::probe_desc_tier(ix->d, h.q_probe[row], ix->band_off[b - 1]);
+          h.q_tier[i] = 1u + ix->band_c0[b - 1];
+        }
     }
     // one list: its K'-th best alive score (the smallest stored K' >= k) bounds
     // the query's k-th best from below, so k_conj starts from that threshold and
@@ -505,7 +516,7 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
   if (S == 1) return plan_host(ixs[0], q, k, S, hs[0], nq1, qt);  // (used in place: nothing to join)
   J.clear();
   const size_t nq = (size_t)S * nq1, nqt = nq * fg::kMaxTerms;
-  for (auto* v : {&J.q_m, &J.lead, &J.ngroup}) v->resize(nq);
+  for (auto* v : {&J.q_m, &J.lead, &J.ngroup, &J.q_tier}) v->resize(nq);
   J.thr0.resize(nq);
   J.q_terms.resize(nqt);
   for (auto* v : {&J.q_ub, &J.q_wt, &J.q_wn, &J.q_rup}) v->resize(nqt);
@@ -517,6 +528,7 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
     const size_t v0 = pc.slot(p), t0 = v0 * fg::kMaxTerms;
     auto cp = [](auto& dst, const auto& src, size_t at) { std::copy(src.begin(), src.end(), dst.begin() + at); };
     cp(J.q_m, h.q_m, v0); cp(J.lead, h.lead, v0); cp(J.ngroup, h.ngroup, v0); cp(J.thr0, h.thr0, v0);
+    cp(J.q_tier, h.q_tier, v0);
     cp(J.q_terms, h.q_terms, t0);
     cp(J.q_ub, h.q_ub, t0); cp(J.q_wt, h.q_wt, t0); cp(J.q_wn, h.q_wn, t0); cp(J.q_rup, h.q_rup, t0);
     cp(J.q_probe, h.q_probe, t0);
@@ -688,8 +700,38 @@ struct WorkList {
   std::vector<uint32_t> work_q, work_c, work_n;
   std::vector<uint64_t> cand_off;
   uint64_t n_single = 0, n_conj = 0, n_main = 0, n_scan = 0, n_phrase = 0;
+  uint32_t xcd_first[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // DevPlan::xcd_first
   uint64_t count() const { return n_main + n_scan + n_phrase; }
 };
+
+// k_conj's multi-list items (sorted) cut into the 8 XCDs' stretches by expected
+// work when some slot leads from a tiered copy: an item of such a slot's first
+// quarter (its best tiers, up to 1/4 of the postings) weighs 1 as every
+// doc-ordered item does, a later one FUGU_BAND_XCD_WEIGHT (those mostly skip
+// their chunks; 1: equal counts, as without tiers).
+void xcd_stretches(const PlanTables& t, WorkList& w) {
+  std::fill(w.xcd_first, w.xcd_first + 9, 0u);
+  static const double low_w = [] {
+    const char* e = getenv("FUGU_BAND_XCD_WEIGHT");
+    const double v = e && *e ? atof(e) : 1.0;  // (0.5 / 0.25 / 0.1 ran the headline 0.831 -> 0.883 / 0.890 / 0.948 ms)
+    return v > 0.0 && v <= 1.0 ? v : 1.0;
+  }();
+  const size_t n0 = w.n_single, n = t.citems.size() - n0;
+  bool any = false;
+  for (size_t x = n0; x < t.citems.size() && !any; ++x) any = t.q_tier[t.citems[x].q] != 0;
+  if (!any || low_w == 1.0 || n < 64) return;
+  auto weight = [&](const WItem& it) { return t.q_tier[it.q] && it.key >= 0.25 ? low_w : 1.0; };
+  double total = 0.0;
+  for (size_t x = n0; x < t.citems.size(); ++x) total += weight(t.citems[x]);
+  double cum = 0.0;
+  uint32_t xcd = 1;
+  for (size_t x = n0; x < t.citems.size(); ++x) {
+    cum += weight(t.citems[x]);
+    while (xcd < 8 && cum >= total * xcd / 8.0) w.xcd_first[xcd++] = (uint32_t)(x - n0 + 1);
+  }
+  while (xcd < 8) w.xcd_first[xcd++] = (uint32_t)n;
+  w.xcd_first[8] = (uint32_t)n;
+}
 
 int order_items(PlanTables& t, uint32_t nq, uint32_t k, WorkList& w) {
   if (t.f_woff[t.nf] * 4 > (8ull << 30)) return fail(FG_EUNSUPPORTED, "facet masks of this batch exceed 8 GiB");
@@ -706,6 +748,7 @@ int order_items(PlanTables& t, uint32_t nq, uint32_t k, WorkList& w) {
   items.insert(items.end(), t.ditems.begin(), t.ditems.end());
   w.n_single = 0;
   for (const WItem& x : t.citems) w.n_single += single_list(t, x) ? 1 : 0;
+  xcd_stretches(t, w);
   std::stable_sort(t.scan.begin(), t.scan.end(), [](const WItem& a, const WItem& b) { return a.key < b.key; });
   w.n_main = items.size();
   w.n_scan = t.scan.size();
@@ -800,6 +843,7 @@ int stage_and_upload(fg_plan* p, fg_index* const* ixs, PlanTables& t, const Work
   L.in(d.q_thr0, t.thr0.data(), 8ull * nq);
   L.in(d.q_ub, t.q_ub.data(), 4 * nqt);
   L.in(d.q_probe, t.q_probe.data(), sizeof(fg::ProbeDesc) * nqt);
+  L.in(d.q_tier, t.q_tier.data(), 4ull * nq);
   L.in(d.q_wt, t.q_wt.data(), 4 * nqt);
   L.in(d.q_wn, t.q_wn.data(), 4 * nqt);
   L.in(d.q_rup, t.q_rup.data(), 4 * nqt);
@@ -908,6 +952,7 @@ void fill_view(fg_plan* p, fg_index* const* ixs, PlanTables& t, const WorkList& 
   p->d.n_scan = (uint32_t)w.n_scan;
   p->d.n_phrase = (uint32_t)w.n_phrase;
   p->d.n_single = (uint32_t)w.n_single;
+  std::copy(w.xcd_first, w.xcd_first + 9, p->d.xcd_first);
   p->d.k = p->k;
   p->d.seg_nq = S > 1 ? nq1 : 0;
   p->d.n_segs = S;
@@ -923,6 +968,8 @@ void fill_view(fg_plan* p, fg_index* const* ixs, PlanTables& t, const WorkList& 
   // breaks such ties by snapshot)
   p->d.pub_mask = S > 1 ? 0xFFFFFFFF00000000ull : ~0ull;
   p->d.opts = fgh::conj_hist_thr() ? fg::kOptConjHistThr : 0u;
+  p->n_tiered = 0;
+  for (uint32_t v = 0; v < nq; ++v) p->n_tiered += t.q_tier[v] ? 1u : 0u;
   p->h_any.assign(nq1, 0);
   for (uint32_t v = 0; v < nq; ++v)
     if (t.ngroup[v]) p->h_any[v % nq1] = 1;
@@ -988,4 +1035,10 @@ int fg_plan_create(fg_index* ix, const fg_query_batch* q, uint32_t k, fg_plan** 
 
 int fg_plan_create_multi(fg_index* const* ixs, uint32_t n_segs, const fg_query_batch* q, uint32_t k, fg_plan** out) {
   return fgh::plan_create_multi(ixs, n_segs, q, k, out, true, hipStreamPerThread);
+}
+
+int fg_plan_tiered_slots(const fg_plan* p, uint32_t* out) {
+  if (!p || !out) return fail(FG_EINVAL, "bad arguments");
+  *out = p->n_tiered;
+  return FG_OK;
 }

@@ -62,7 +62,9 @@ EXPORTS = (
     "fg_plan_set_peers", "fg_plan_ipc_export", "fg_plan_set_ipc_peers", "fg_plan_reset",
     "fg_count_batch", "fg_count_trace", "fg_index_doctab_get", "fg_index_doctab8_get",
     "fg_index_build_positional", "fg_index_positions_get",
+    "fg_index_bands_get", "fg_index_band_read", "fg_plan_tiered_slots",
 )
+BAND_TIERS = 5  # fugu.h FG_BAND_TIERS
 LADDER_KS = (1, 2, 3, 5, 10, 13, 20, 25, 50, 100, 125, 250, 500, 1000)  # FG_LADDER_LEVELS ranks
 KTH_KS = (1, 10, 20, 100, 1000)  # fg_index_term_kth / fg_index_set_kth_floor ranks
 HIST_BINS = 512  # fugu.h FG_HIST_BINS: score-histogram bins per query
@@ -177,6 +179,10 @@ _sig("fg_index_stats_get", C.c_int, _p, C.POINTER(IndexStats))
 _sig("fg_index_doctab_get", C.c_int, _p, _u32p, _u64p)
 if hasattr(_lib, "fg_index_doctab8_get"):  # (FG_ABI_VERSION did not move with it: an A/B library built before it lacks it)
     _sig("fg_index_doctab8_get", C.c_int, _p, _u32p, _u64p)
+if hasattr(_lib, "fg_index_bands_get"):  # (new symbols, FG_ABI_VERSION stays: an A/B library built before lacks them)
+    _sig("fg_index_bands_get", C.c_int, _p, _u32p, _u64p)
+    _sig("fg_index_band_read", C.c_int, _p, C.c_uint32, C.c_int, _u32p, _f32p, C.c_uint64, _f32p, _u32p, _u64p)
+    _sig("fg_plan_tiered_slots", C.c_int, _p, _u32p)
 _sig("fg_index_df", C.c_uint64, _p, C.c_int, C.c_uint32)
 _sig("fg_index_bm25", C.c_int, _p, C.c_uint32, _f32p, _f32p, _f32p)
 _sig("fg_plan_create", C.c_int, _p, C.POINTER(QueryBatch), C.c_uint32, C.POINTER(_p))
@@ -567,6 +573,29 @@ class Index:
         _check(_lib.fg_index_doctab8_get(self._h, C.byref(n), C.byref(b)))
         return int(n.value), int(b.value)
 
+    def lead_bands(self):
+        """(terms with a score-tiered lead copy, the copies' device bytes): fg_index_bands_get."""
+        n, b = C.c_uint32(0), C.c_uint64(0)
+        if not hasattr(_lib, "fg_index_bands_get"):
+            return 0, 0
+        _check(_lib.fg_index_bands_get(self._h, C.byref(n), C.byref(b)))
+        return int(n.value), int(b.value)
+
+    def band_read(self, term: int, source: bool = False):
+        """fg_index_band_read: (doc u32[df], score f32[df], cmax f32[chunks], cuts u32[BAND_TIERS - 1]) of the
+        term's score-tiered copy -- or, source=True, the doc-ordered list it was made from -- or None when
+        the term has no copy."""
+        n = C.c_uint64(0)
+        _check(_lib.fg_index_band_read(self._h, term, int(source), None, None, 0, None, None, C.byref(n)))
+        df = int(n.value)
+        if df == 0:
+            return None
+        doc, sc = np.zeros(df, np.uint32), np.zeros(df, np.float32)
+        cmax, cuts = np.zeros((df + 2047) // 2048, np.float32), np.zeros(BAND_TIERS - 1, np.uint32)
+        _check(_lib.fg_index_band_read(self._h, term, int(source), _ptr(doc, _u32p), _ptr(sc, _f32p), df,
+                                       _ptr(cmax, _f32p), _ptr(cuts, _u32p), C.byref(n)))
+        return doc, sc, cmax, cuts
+
     def df(self, term: int, field: int = -1) -> int:
         return int(_lib.fg_index_df(self._h, field, term))
 
@@ -783,6 +812,14 @@ class Plan:
         if s.shape != (self.n_batch,):
             raise ValueError(f"scores of {s.shape}, expected ({self.n_batch},)")
         _check(_lib.fg_plan_seed_thr0(self._h, _ptr(s, _f32p), self.n_batch))
+
+    def tiered_slots(self) -> int:
+        """fg_plan_tiered_slots: query slots that lead from a score-tiered copy of their lead term."""
+        n = C.c_uint32(0)
+        if not hasattr(_lib, "fg_plan_tiered_slots"):
+            return 0
+        _check(_lib.fg_plan_tiered_slots(self._h, C.byref(n)))
+        return int(n.value)
 
     def candidate_counts(self):
         cnt = np.zeros(self.n_queries, np.uint32)

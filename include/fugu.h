@@ -293,6 +293,21 @@ int fg_index_doctab_get(const fg_index* ix, uint32_t* n_terms, uint64_t* bytes);
  * it before the exact probe of their second list; shared with its rescores and
  * counted in device_bytes): terms and device bytes.  Either pointer may be NULL. */
 int fg_index_doctab8_get(const fg_index* ix, uint32_t* n_terms, uint64_t* bytes);
+/* The snapshot's score-tiered lead copies (per dense term a second copy of its
+ * postings, stably partitioned into FG_BAND_TIERS tiers by build-time score with
+ * docs ascending inside a tier, and the exact maximum of every 2048 postings of
+ * the copy: conjunctions that lead from one skip the chunks whose maximum cannot
+ * reach their threshold; shared with its rescores and counted in device_bytes):
+ * terms and device bytes.  Either pointer may be NULL. */
+#define FG_BAND_TIERS 5
+int fg_index_bands_get(const fg_index* ix, uint32_t* n_terms, uint64_t* bytes);
+/* The tiered copy of `term` (source = 0), or the doc-ordered list it was made
+ * from (source = 1), read back for checks: *n = the term's postings (0: the term
+ * has no copy, nothing else is written); doc[n] and score[n] (room for cap each),
+ * cmax[ceil(n / 2048)] the copy's chunk maxima, cuts[FG_BAND_TIERS - 1] the lowest
+ * score bin (f32 bits >> 16) of tiers 0..i.  Any of the four may be NULL. */
+int fg_index_band_read(const fg_index* ix, uint32_t term, int source, uint32_t* doc, float* score, uint64_t cap,
+                       float* cmax, uint32_t* cuts, uint64_t* n);
 /* doc_freq of `term` in `field` (tantivy Searcher::doc_freq; FG_FIELD_FACET:
  * a facet term), and the merged (text U name) posting-list length when field < 0. */
 uint64_t fg_index_df(const fg_index* ix, int field, uint32_t term);
@@ -484,6 +499,9 @@ int fg_plan_kernel_ms(fg_plan* p, double* ms_out, uint32_t* n_out);
  * per workgroup (k_conj work items, then k_final queries); FG_EUNSUPPORTED
  * for the stamps in product builds. */
 int fg_plan_diag(fg_plan* p, uint64_t* out, size_t n_words, uint32_t* cand_cnt);
+/* How many of the plan's query slots lead from a score-tiered copy of their
+ * lead term (fg_index_bands_get; env FUGU_BAND_LEAD=0 when the plan is made: none). */
+int fg_plan_tiered_slots(const fg_plan* p, uint32_t* out);
 int fg_plan_destroy(fg_plan* p);
 
 /* Synchronous convenience: plan + execute + copy back.  Host buffers

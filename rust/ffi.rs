@@ -238,6 +238,12 @@ extern "C" {
     pub fn fg_index_stats_get(ix: *const fg_index, out: *mut fg_index_stats) -> c_int;
     pub fn fg_index_doctab_get(ix: *const fg_index, n_terms: *mut u32, bytes: *mut u64) -> c_int;
     pub fn fg_index_doctab8_get(ix: *const fg_index, n_terms: *mut u32, bytes: *mut u64) -> c_int;
+    pub fn fg_index_bands_get(ix: *const fg_index, n_terms: *mut u32, bytes: *mut u64) -> c_int;
+    pub fn fg_index_band_read(
+        ix: *const fg_index, term: u32, source: c_int, doc: *mut u32, score: *mut f32, cap: u64, cmax: *mut f32,
+        cuts: *mut u32, n: *mut u64,
+    ) -> c_int;
+    pub fn fg_plan_tiered_slots(p: *const fg_plan, out: *mut u32) -> c_int;
     pub fn fg_index_df(ix: *const fg_index, field: c_int, term: u32) -> u64;
     pub fn fg_index_bm25(ix: *const fg_index, term: u32, w_text: *mut f32, w_name: *mut f32, cache512: *mut f32)
                          -> c_int;

@@ -52,7 +52,8 @@ def main():
     c_start, c_probe, c_keys, c_sel, c_end = (conj[:, i].astype(np.int64) for i in range(5))
     dur = (c_end - c_start) * us
     t0 = c_start.min()
-    nchk = (conj[:, 6] >> np.uint64(40)).astype(np.int64)
+    nchk = ((conj[:, 6] >> np.uint64(40)) & np.uint64(0xFF)).astype(np.int64)
+    nskip = ((conj[:, 6] >> np.uint64(48)) & np.uint64(0xFF)).astype(np.int64)  # (tiered leads: chunks not loaded)
     # occupancy over time: the tail where fewer than half of the resident
     # workgroup slots (4 per CU x 256 CUs) are busy
     ev = np.concatenate([np.stack([c_start, np.ones_like(c_start)], 1), np.stack([c_end, -np.ones_like(c_end)], 1)])
@@ -65,6 +66,8 @@ def main():
             "tail_us_below_half_slots": tail_us, "max_active_wgs": int(act.max()),
             "work_items": int(len(conj)),
             "chunks": int(nchk.sum()),
+            "chunks_skipped": int(nskip.sum()),
+            "items_all_skipped": int((nskip == nchk).sum()),
             "span_us": round(float((c_end.max() - t0) * us), 1),
             "wg_us": pct(dur),
             "wg_us_sum": round(float(dur.sum()), 1),
