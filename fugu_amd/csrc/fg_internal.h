@@ -262,6 +262,24 @@ __host__ __device__ inline uint32_t qm_pack(uint32_t m, uint32_t nm, uint32_t nx
 // a phrase query's slot (k_phrase): bits 0-7 its distinct terms, 24-31 the phrase's terms
 __host__ __device__ inline uint32_t qm_phrase(uint32_t distinct, uint32_t n) { return distinct | (n << 24); }
 __host__ __device__ inline uint32_t qm_phrase_terms(uint32_t qm) { return qm >> 24; }
+// A slot of k_bphrase (a phrase clause beside other clauses): q_m =
+// qm_phrase(clauses, terms); its DevPlan::q_clause row holds one word per clause
+// in the order of the score sum -- [Must (cost order)][MustNot][Should (clause
+// order)], or without a Must [Should (clause order)][MustNot] -- packed as:
+// bits 0-3 the clause's first entry in the slot's q_terms / q_pterm / q_ppos
+// rows, 4-8 its terms (1: a term clause), 9-10 its occur, 11 a phrase, 16-19 its
+// position in the score sum (its index in the row).
+constexpr uint32_t kClMust = 0, kClShould = 1, kClMustNot = 2;  // cl_occur: fugu.h FG_OCCUR_*
+constexpr uint32_t kClPhrase = 1u << 11;
+__host__ __device__ inline uint32_t cl_pack(uint32_t t0, uint32_t n, uint32_t occur, bool phrase, uint32_t pos) {
+  return t0 | (n << 4) | (occur << 9) | (phrase ? kClPhrase : 0u) | (pos << 16);
+}
+__host__ __device__ inline uint32_t cl_first(uint32_t c) { return c & 15u; }
+__host__ __device__ inline uint32_t cl_terms(uint32_t c) { return (c >> 4) & 31u; }
+__host__ __device__ inline uint32_t cl_occur(uint32_t c) { return (c >> 9) & 3u; }
+// a k_bphrase work item's work_n: the lead chunks of its group, and above them the
+// clause it leads from (a Should-driven query: the pass)
+constexpr uint32_t kBpPassShift = 8;
 
 // Rank words (DevIndex::rank): one u64 per 32 docs, the low half the docs'
 // presence bits, the high half the number of the term's postings before the
@@ -715,6 +733,13 @@ struct DevPlan {
   const uint32_t* q_pterm;      // [nq * kMaxTerms] a phrase's terms as VOCABULARY ids (DevIndex::fwd), the
                                 //     anchor -- the rarest term's first occurrence in the phrase -- first
   const uint32_t* q_ppos;       // [nq * kMaxTerms] ... and their position offsets within the phrase
+  uint32_t n_bphrase;           // k_bphrase work items (queries with a phrase clause beside other clauses:
+                                // fg_phrase_clauses), after the k_phrase items: (query slot, group of kChunk-
+                                // posting chunks of a lead list, the clause led from in work_n's upper bits).
+                                // Such a slot's q_terms / q_pterm / q_ppos rows hold every clause's terms
+                                // (local ids / vocabulary ids / offsets), clause after clause in q_clause's
+                                // order, a phrase's anchor first; q_wt / q_wn [row][c] are clause c's weights
+  const uint32_t* q_clause;     // [nq * kMaxTerms] the clause table (cl_pack); empty without such a slot
   // Multi-snapshot plans (several segments / doc shards / namespaces of one
   // device in ONE launch per kernel): query slot v = s * seg_nq + q is query q
   // of the batch on snapshot segs[s]; every per-query array above is indexed by
@@ -986,6 +1011,7 @@ hipError_t launch_disj(const DevIndex& ix, const DevPlan& pl, hipStream_t s, uin
 hipError_t launch_fmask(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 hipError_t launch_scan(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 hipError_t launch_phrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
+hipError_t launch_bphrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 // out_shard != nullptr: the merged select of a multi-snapshot plan (one list per batch query)
 hipError_t launch_final(const DevPlan& pl, float* out_score, uint32_t* out_doc, uint32_t* out_n, hipStream_t s,
                         uint32_t* out_shard = nullptr);

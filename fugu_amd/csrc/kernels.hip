@@ -2382,6 +2382,211 @@ __global__ __launch_bounds__(kThreads) void k_phrase(DevIndex ix0, DevPlan pl) {
   flush_candidates(pl, q, sh.s.buf, sh.s.n_buf, sh.s.thr, sh.s.scratch);
 }
 
+// ---------------------------------------------------------------- k_bphrase
+// Queries with a phrase clause BESIDE other clauses (term or phrase clauses, any
+// occur; fg_phrase_clauses).  The slot's clause table
+// (DevPlan::q_clause) lists its clauses in the order of the score sum.  A work
+// item is a group of kChunk-posting chunks of ONE lead list: the first term of
+// the clause named in work_n's upper bits.  A query with a Must clause has one
+// lead (the shortest list among its Must clauses' terms) and every Must clause
+// is REQUIRED; a union of Shoulds runs one pass per Should clause j, leading
+// from that clause's list with clause j alone required, and a doc some earlier
+// Should clause i < j matches is left to pass i -- so every hit leaves exactly
+// one pass, with its whole score, and k_final's keys stay unique.  Per chunk:
+//  (a) every lane takes kItems lead docs and drops the deleted ones, those that
+//      lack a term of a required clause and those a MustNot term clause (or, in
+//      pass j, an earlier Should term clause) holds (term_has_doc); survivors
+//      are queued in LDS;
+//  (b) one wave per survivor walks the clause table: the lanes look up one term
+//      of the clause each (posting_pos); a clause with every term present is
+//      scored -- a term clause by tfn_score on its payload (the query-time form,
+//      bit-identical to the build-time scores), a phrase clause by phrase_count
+//      per field on the forward index and field_score, text then name from 0.0
+//      -- and joined as tantivy joins them: (s0 + s1) + (0.0 + s2 + ...) over the
+//      Musts, (0.0 + req) + opt with opt the matching Shoulds from 0.0; a doc
+//      that misses a required clause or matches an excluding one is dropped;
+//  (c) keys go through k_scan's local top-k buffer, threshold word and flush, as
+//      k_phrase's.
+// No score bound prunes in (a): every survivor is verified.
+struct BPhraseShared {
+  ScanShared s;
+  uint64_t queue[kChunk];      // survivors (doc ids)
+  uint32_t n_q;
+  uint32_t cl[kMaxTerms];      // the clause table
+  float cwt[kMaxTerms];        // the clauses' field weights
+  float cwn[kMaxTerms];
+  uint32_t lterm[kMaxTerms];   // the clauses' terms, clause after clause: the snapshot's ids,
+  uint32_t pterm[kMaxTerms];   // ... vocabulary ids (DevIndex::fwd)
+  uint32_t ppos[kMaxTerms];    // ... and offsets in their phrase
+  uint32_t act[kMaxTerms];     // stage (a): 1 the doc must hold the term, 2 must not, 0 not asked
+  uint32_t tmeta[kMaxTerms];   // the terms' probe tables
+  uint32_t tdir[kMaxTerms];
+  uint64_t toff[kMaxTerms];
+};
+
+// phrase_count over the n (vocabulary id, offset) pairs at pterm / ppos (LDS; the anchor first)
+__device__ inline uint32_t phrase_count_at(const uint32_t* __restrict__ fwd, uint64_t b0, uint64_t b1,
+                                           const uint32_t* pterm, const uint32_t* ppos, uint32_t n, uint32_t span) {
+  const uint64_t len = b1 - b0;
+  uint32_t c = 0;
+  if (len > span) {
+    const uint64_t starts = len - span;  // phrase starts p with p + span inside the doc
+    const uint32_t a_pos = ppos[0], a_term = pterm[0];
+    for (uint64_t p = lane_id(); p < starts; p += 64) {
+      if (fwd[b0 + p + a_pos] != a_term) continue;
+      bool ok = true;
+      for (uint32_t j = 1; j < n && ok; ++j) ok = fwd[b0 + p + ppos[j]] == pterm[j];
+      c += ok ? 1u : 0u;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o, 64);
+  return c;
+}
+
+template <bool kMulti>
+__global__ __launch_bounds__(kThreads) void k_bphrase(DevIndex ix0, DevPlan pl) {
+  __shared__ BPhraseShared sh;
+  const uint32_t tid = threadIdx.x, lane = lane_id();
+  const uint32_t w = pl.total_chunks + pl.n_scan + pl.n_phrase + blockIdx.x;  // after the k_phrase items
+  const uint32_t q = pl.work_q[w];
+  const DevIndex ix = kMulti ? seg_index(pl, __builtin_amdgcn_readfirstlane(q / pl.seg_nq)) : ix0;
+  const uint32_t ql = kMulti ? __builtin_amdgcn_readfirstlane(q % pl.seg_nq) : q;
+  const uint32_t chunk0 = pl.work_c[w];
+  const uint32_t nchunk = pl.work_n[w] & ((1u << kBpPassShift) - 1u);
+  const uint32_t K = pl.k;
+  uint64_t* gthr = &pl.thresh[ql];
+  const uint32_t qm = pl.q_m[q];
+  const uint32_t ncl = min(qm_terms(qm), kMaxTerms), nt = min(qm_phrase_terms(qm), kMaxTerms);
+  if (ncl == 0 || nt == 0) return;  // (never planned; uniform)
+  const uint32_t pass = min(pl.work_n[w] >> kBpPassShift, ncl - 1);
+  const size_t row = (size_t)q * kMaxTerms;
+  if (tid < nt) {
+    const uint32_t t = pl.q_terms[row + tid];
+    sh.lterm[tid] = t;
+    sh.pterm[tid] = pl.q_pterm[row + tid];
+    sh.ppos[tid] = pl.q_ppos[row + tid];
+    sh.tmeta[tid] = ix.tmeta[t];
+    sh.tdir[tid] = ix.dir_off[t];
+    sh.toff[tid] = ix.off[t];
+    sh.act[tid] = 0;
+  }
+  if (tid < ncl) {
+    sh.cl[tid] = pl.q_clause[row + tid];
+    sh.cwt[tid] = pl.q_wt[row + tid];
+    sh.cwn[tid] = pl.q_wn[row + tid];
+  }
+  if (tid == 0) {
+    sh.s.n_buf = 0;
+    sh.n_q = 0;
+    sh.s.thr = atomicMax(reinterpret_cast<unsigned long long*>(gthr), 0ull);
+  }
+  __syncthreads();
+  const bool must = cl_occur(sh.cl[0]) == kClMust;  // (the Musts stand first)
+  if (tid < ncl) {
+    const uint32_t c = sh.cl[tid], oc = cl_occur(c), n = cl_terms(c), t0 = cl_first(c);
+    const bool required = must ? oc == kClMust : tid == pass;
+    const bool barred = n == 1 && (oc == kClMustNot || (!must && oc == kClShould && tid < pass));
+    for (uint32_t x = t0; x < min(t0 + n, nt); ++x) sh.act[x] = required ? 1u : barred ? 2u : 0u;
+  }
+  __syncthreads();
+  const uint32_t li = min(cl_first(sh.cl[pass]), nt - 1);  // the lead: the pass clause's first term
+  const uint32_t lead = sh.lterm[li];
+  const uint64_t base = sh.toff[li];
+  const uint32_t df = (uint32_t)(ix.off[lead + 1] - base);
+  const bool name = ix.tfn_name != nullptr && ix.fwd_off_name != nullptr;
+  for (uint32_t c = 0; c < nchunk; ++c) {
+    // (a) the chunk's lead docs that are alive, hold the required clauses' terms and none of the barred ones
+    const uint32_t i0 = (chunk0 + c) * kChunk;
+    for (uint32_t j = 0; j < kItems; ++j) {
+      const uint32_t i = i0 + j * kThreads + tid;
+      bool keep = i < df;
+      uint32_t d = 0;
+      if (keep) {
+        d = ix.doc[base + i];
+        keep = doc_alive(ix, d);
+      }
+      for (uint32_t u = 0; u < nt; ++u) {
+        const uint32_t a = sh.act[u];
+        if (keep && a && u != li) keep = term_has_doc(ix, sh.tmeta[u], sh.toff[u], sh.tdir[u], d) == (a == 1u);
+      }
+      wave_append(keep, (uint64_t)d, sh.queue, &sh.n_q, kChunk);
+    }
+    __syncthreads();
+    // (b), (c) one wave per survivor, kRound survivors between truncations
+    const uint32_t nsv = min(sh.n_q, kChunk);
+    for (uint32_t r0 = 0; r0 < nsv; r0 += kRound) {
+      const uint64_t thr = sh.s.thr;
+      const uint32_t r1 = min(nsv, r0 + kRound);
+      for (uint32_t x = r0 + wave_id(); x < r1; x += kThreads / 64) {
+        const uint32_t d = __builtin_amdgcn_readfirstlane((uint32_t)sh.queue[x]);
+        float req = 0.0f, oth = 0.0f, opt = 0.0f;
+        uint32_t nm = 0;
+        bool any = false, drop = false;
+        for (uint32_t ci = 0; ci < ncl && !drop; ++ci) {
+          const uint32_t cw = sh.cl[ci], oc = cl_occur(cw), n = cl_terms(cw), t0 = min(cl_first(cw), nt - 1);
+          // every term of the clause in the doc? (a lane each); lane 0 holds the first term's posting
+          uint32_t pos = kInvalid;
+          if (lane < n && t0 + lane < nt) pos = posting_pos(ix, sh.lterm[t0 + lane], d);
+          const bool all = __ballot(pos != kInvalid) == (1ull << n) - 1ull;
+          float s = 0.0f;
+          bool on = false;
+          if (all) {
+            const uint64_t p0 = sh.toff[t0] + __builtin_amdgcn_readfirstlane(pos);
+            uint32_t v = ix.tfn[p0];
+            if (ix.tfn_name) v |= (uint32_t)ix.tfn_name[p0] << 16;
+            v = __builtin_amdgcn_readfirstlane(v);
+            const float wt = sh.cwt[ci], wn = sh.cwn[ci];
+            if (!(cw & kClPhrase)) {
+              s = tfn_score(ix, p0, v, wt, wn, ix.cache, ix.cache + 256);
+              on = true;
+            } else {
+              uint32_t span = 0;  // the phrase's largest offset
+              for (uint32_t j = 0; j < n; ++j) span = max(span, sh.ppos[t0 + j]);
+              uint32_t ct = 0, cn = 0;
+              if (v & 0xFFu)
+                ct = phrase_count_at(ix.fwd, ix.fwd_off[d], ix.fwd_off[d + 1], sh.pterm + t0, sh.ppos + t0, n, span);
+              if (name && ((v >> 16) & 0xFFu))
+                cn = phrase_count_at(ix.fwd_name, ix.fwd_off_name[d], ix.fwd_off_name[d + 1], sh.pterm + t0,
+                                     sh.ppos + t0, n, span);
+              if (ct) s += field_score(ct, (v >> 8) & 0xFFu, wt, ix.cache);
+              if (cn) s += field_score(cn, v >> 24, wn, ix.cache + 256);
+              on = (ct | cn) != 0;
+            }
+          }
+          if (oc == kClMust) {
+            if (!on) drop = true;
+            else if (nm == 0) req = s;
+            else if (nm == 1) req = req + s;
+            else oth = oth + s;
+            ++nm;
+          } else if (oc == kClMustNot) {
+            drop = on;
+          } else if (!must && ci <= pass && on != (ci == pass)) {
+            drop = true;  // an earlier pass's doc, or the pass clause does not match
+          } else if (on) {
+            opt = opt + s;
+            any = true;
+          }
+        }
+        float sc = opt;
+        if (must) {
+          if (nm > 1) req = req + oth;
+          sc = 0.0f + req;
+          if (any) sc = sc + opt;
+        }
+        const uint64_t key = make_key(sc, d);
+        wave_append(lane == 0 && !drop && key >= thr, key, sh.s.buf, &sh.s.n_buf, kBufD);
+      }
+      __syncthreads();
+      scan_truncate(sh.s, K, kTrunc, gthr, false, pl.pub_mask, pl, ql);
+    }
+    if (tid == 0) sh.n_q = 0;
+    scan_truncate(sh.s, K, K, gthr, true, pl.pub_mask, pl, ql);
+  }
+  flush_candidates(pl, q, sh.s.buf, sh.s.n_buf, sh.s.thr, sh.s.scratch);
+}
+
 // ---------------------------------------------------------------- k_final
 // Dynamic LDS (80 KB: 2 workgroups per CU): candidate keys, the k winners,
 // the radix histogram.  Keeps 16-B alignment of the dynamic base (no static
@@ -2720,6 +2925,13 @@ hipError_t launch_phrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s) {
   if (pl.n_phrase == 0) return hipSuccess;
   if (pl.segs) k_phrase<true><<<pl.n_phrase, kThreads, 0, s>>>(ix, pl);
   else k_phrase<false><<<pl.n_phrase, kThreads, 0, s>>>(ix, pl);
+  return hipGetLastError();
+}
+
+hipError_t launch_bphrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s) {
+  if (pl.n_bphrase == 0) return hipSuccess;
+  if (pl.segs) k_bphrase<true><<<pl.n_bphrase, kThreads, 0, s>>>(ix, pl);
+  else k_bphrase<false><<<pl.n_bphrase, kThreads, 0, s>>>(ix, pl);
   return hipGetLastError();
 }
 

@@ -2,6 +2,7 @@
 // a batch (plan_host), the pieces joined into one set of tables and work
 // items, the items ordered for the kernels, and ONE workspace laid out, staged
 // and uploaded.  fugu.cpp executes the plans.
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -20,6 +21,10 @@ fgh::Bins fgh::union_bins(uint32_t lo, uint32_t hi) {
 }
 
 namespace {
+
+// fg_phrase_clauses: queries with a phrase clause beside other clauses run on the
+// device (k_bphrase); process-wide, off by default, read when a plan is created
+std::atomic<int> phrase_clauses_on{0};
 
 // stable LSD radix sort of `a` by its bits 32..63 (three 11-bit passes)
 void radix_sort_hi32(std::vector<uint64_t>& a, std::vector<uint64_t>& tmp) {
@@ -44,6 +49,7 @@ struct PlanTables {
   std::vector<uint32_t> q_m, q_terms, lead, q_filter, ngroup, q_hlo, q_hhi, q_hsh;
   std::vector<uint32_t> q_tier;  // DevPlan::q_tier: slots that lead from a score-tiered copy
   std::vector<uint32_t> q_pterm, q_ppos;  // phrase queries' (term, offset) rows; empty without phrase_len
+  std::vector<uint32_t> q_clause;         // DevPlan::q_clause (k_bphrase slots); empty unless fg_phrase_clauses is on
   std::vector<uint64_t> thr0;
   std::vector<float> q_ub, q_wt, q_wn, q_rup;
   std::vector<fg::ProbeDesc> q_probe;  // k_conj slots' probe descriptors (rows as above)
@@ -53,22 +59,146 @@ struct PlanTables {
   std::vector<uint64_t> f_woff;
   std::vector<float> f_tab, f_max;
   std::vector<uint32_t> ch_f, ch_c, ch_t, ch_s;
-  // work items: k_conj's, k_disj's, k_scan's, k_phrase's; items: all of them as
-  // the kernels run them (order_items, joined tables only)
-  std::vector<WItem> citems, ditems, scan, phrase, items;
+  // work items: k_conj's, k_disj's, k_scan's, k_phrase's, k_bphrase's; items: all
+  // of them as the kernels run them (order_items, joined tables only)
+  std::vector<WItem> citems, ditems, scan, phrase, bphrase, items;
   // (a thread's plans reuse one set: assign / push_back into kept capacity, no
   // page faults on fresh arrays -- ~0.2 ms of an 8-snapshot batch's planning)
   void clear() {
     auto all = [](auto&... v) { (v.clear(), ...); };
     all(q_m, q_terms, lead, q_filter, ngroup, q_hlo, q_hhi, q_hsh, thr0, q_ub, q_wt, q_wn, q_rup, f_shift, f_seg, f_woff,
-        f_tab, f_max, ch_f, ch_c, ch_t, ch_s, citems, ditems, scan, phrase, items, q_pterm, q_ppos, q_probe, q_tier);
+        f_tab, f_max, ch_f, ch_c, ch_t, ch_s, citems, ditems, scan, phrase, bphrase, items, q_pterm, q_ppos, q_clause,
+        q_probe, q_tier);
     nf = 0;
   }
 };
 
+// Query i of the batch when it holds a phrase clause beside other clauses and
+// fg_phrase_clauses is on (the clause table was checked by plan_phrase): no facet
+// clauses, a snapshot with positions, else FG_EUNSUPPORTED naming the reason.
+// A Should or MustNot clause with a term the snapshot lacks is dropped, a Must
+// one empties the slot; one Should and no Must is that clause as a Must.  The
+// slot's clause table (fg_internal.h cl_pack) is in the order of the score sum:
+// the Musts by (cost, clause position) -- a term clause's cost df_text + df_name,
+// a phrase clause's the sum over the two fields of its terms' smallest doc count
+// there (PhraseScorer's size hint is its intersection's; a field lacking a term:
+// 0) --, then the MustNots, then the Shoulds in clause order; without a Must the
+// Shoulds, then the MustNots.  q_terms / q_pterm / q_ppos hold the clauses' terms
+// in that order, a phrase's anchor (the first occurrence of its term with the
+// fewest postings) first; q_wt / q_wn [c] clause c's weights (a phrase's:
+// Bm25Weight::for_terms, as plan_phrase's).  Work items (k_bphrase): with a Must,
+// groups of the chunks of the shortest list among the Must clauses' first terms;
+// without, one pass per Should clause over that clause's first term's list; the
+// clause led from rides in the item's count word above kBpPassShift.
+int plan_bool_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t nq_size, uint32_t n_segs,
+                     PlanTables& h) {
+  const uint32_t b = q->q_off[i], e = q->q_off[i + 1];
+  if (q->f_off && q->f_off[i + 1] > q->f_off[i]) return fail(FG_EUNSUPPORTED, "query %u: phrase with facet filters", i);
+  if (!ix->has_positions) return fail(FG_EUNSUPPORTED, "query %u: snapshot built without positions", i);
+  auto len = [&](uint32_t t) { return ix->off[t + 1] - ix->off[t]; };
+  struct Cl { uint32_t at, n, oc, pos, anchor; uint64_t cost; float wt, wn; };
+  Cl cl[fg::kMaxTerms];
+  uint32_t lt[fg::kMaxTerms];  // the query's terms as the snapshot's ids
+  uint32_t ncl = 0, nm = 0, ns = 0;
+  bool must_missing = false;
+  for (uint32_t j = b, pos = 0; j < e; ++pos) {
+    const uint32_t n = q->phrase_len[j];
+    const uint32_t oc = q->occur ? q->occur[j] : (q->mode == FG_MODE_OR ? FG_OCCUR_SHOULD : FG_OCCUR_MUST);
+    if (oc > FG_OCCUR_MUST_NOT) return fail(FG_EINVAL, "query %u: bad occur %u", i, oc);
+    if (n >= 2 && q->phrase_pos[j + n - 1] >= (1u << 30)) return fail(FG_EINVAL, "query %u: phrase offset too large", i);
+    Cl c{j - b, n, oc, pos, 0, 0, 0.0f, 0.0f};
+    bool present = true;
+    uint64_t ct = ~0ull, cn = ~0ull;
+    float it = 0.0f, in = 0.0f;
+    for (uint32_t x = 0; x < n && present; ++x) {
+      const uint32_t t = lt[c.at + x] = fgh::local_term(ix, q->terms[j + x]);
+      present = t < ix->n_terms && ix->off[t + 1] > ix->off[t];
+      if (!present) break;
+      ct = std::min<uint64_t>(ct, ix->df_text[t]);
+      cn = std::min<uint64_t>(cn, ix->df_name[t]);
+      it += ix->idf_text[t];
+      in += ix->idf_name[t];
+      if (len(t) < len(lt[c.at + c.anchor])) c.anchor = x;
+    }
+    j += n;
+    if (!present) {
+      must_missing |= oc == FG_OCCUR_MUST;
+      continue;
+    }
+    if (n == 1) {
+      c.cost = (uint64_t)ix->df_text[lt[c.at]] + ix->df_name[lt[c.at]];
+      c.wt = ix->w_text[lt[c.at]];
+      c.wn = ix->w_name[lt[c.at]];
+    } else {
+      c.cost = ct + cn;
+      c.wt = it * (1.0f + 1.2f);  // (1 + K1), as bm25_weight's
+      c.wn = in * (1.0f + 1.2f);
+    }
+    nm += oc == FG_OCCUR_MUST;
+    ns += oc == FG_OCCUR_SHOULD;
+    cl[ncl++] = c;
+  }
+  if (must_missing || nm + ns == 0) return FG_OK;  // a Must matches nothing, or no positive clause: no hits
+  if (nm == 0 && ns == 1)
+    for (uint32_t c = 0; c < ncl; ++c)
+      if (cl[c].oc == FG_OCCUR_SHOULD) { cl[c].oc = FG_OCCUR_MUST; nm = 1; ns = 0; }
+  // the order of the score sum
+  auto rank = [&](const Cl& c) {
+    if (nm) return c.oc == FG_OCCUR_MUST ? 0 : c.oc == FG_OCCUR_MUST_NOT ? 1 : 2;
+    return c.oc == FG_OCCUR_SHOULD ? 0 : 1;
+  };
+  std::stable_sort(cl, cl + ncl, [&](const Cl& x, const Cl& y) {
+    const int rx = rank(x), ry = rank(y);
+    if (rx != ry) return rx < ry;
+    return nm && rx == 0 && x.cost < y.cost;  // (stable: ties and the other kinds by clause position)
+  });
+  const size_t row = (size_t)i * fg::kMaxTerms;
+  uint32_t first[fg::kMaxTerms], o = 0;
+  for (uint32_t c = 0; c < ncl; ++c) {
+    const Cl& x = cl[c];
+    first[c] = o;
+    for (uint32_t u = 0, at = 1; u < x.n; ++u) {
+      const uint32_t dst = o + (u == x.anchor ? 0 : at++);
+      h.q_terms[row + dst] = lt[x.at + u];
+      h.q_pterm[row + dst] = q->terms[b + x.at + u];
+      h.q_ppos[row + dst] = q->phrase_pos[b + x.at + u];
+    }
+    h.q_clause[row + c] = fg::cl_pack(o, x.n, x.oc, x.n >= 2, c);
+    h.q_wt[row + c] = x.wt;
+    h.q_wn[row + c] = x.wn;
+    o += x.n;
+  }
+  h.q_m[i] = fg::qm_phrase(ncl, o);
+  // the passes: the Must clause with the shortest first list, or every Should clause
+  const uint32_t cdiv = n_segs <= 1 ? 1u : n_segs;
+  const uint32_t per_q = std::max<uint32_t>(
+      1, std::min<uint32_t>(64, std::max<uint32_t>(fg::kConjGroupsPerQuery, 1024 / std::max(nq_size, 1u))) / cdiv);
+  auto lead_len = [&](uint32_t c) { return (uint64_t)len(h.q_terms[row + first[c]]); };
+  uint32_t lo = 0, hi = nm ? 1 : ns;
+  if (nm)
+    for (uint32_t c = 1; c < nm; ++c)
+      if (lead_len(c) < lead_len(lo)) lo = c;
+  if (nm) hi = lo + 1;
+  h.lead[i] = (uint32_t)lead_len(lo);
+  uint32_t total = 0;
+  for (uint32_t c = lo; c < hi; ++c) {
+    const uint32_t nch = (uint32_t)((lead_len(c) + fg::kChunk - 1) / fg::kChunk);
+    if (h.bphrase.size() + nch > 0x7FFFFFFFull)
+      return fail(FG_EUNSUPPORTED, "batch too large (%zu work items)", h.bphrase.size());
+    const uint32_t G = std::min<uint32_t>(fg::kPhraseMaxGroup, std::max<uint32_t>(1, (nch + per_q - 1) / per_q));
+    const uint32_t ng = (nch + G - 1) / G;
+    for (uint32_t g = 0; g < ng; ++g)
+      h.bphrase.push_back(WItem{(g + 0.5) / ng, i, g * G, std::min(G, nch - g * G) | (c << fg::kBpPassShift)});
+    total += ng;
+  }
+  h.ngroup[i] = total;
+  return FG_OK;
+}
+
 // Query i of the batch when it holds a phrase clause (fg_query_batch::phrase_len
 // >= 2; *phrase = 0 otherwise, after checking the clause table): the device
-// subset -- the phrase is the query's only clause, no facet clauses, a snapshot
+// subset -- the phrase is the query's only clause (`beside`, fg_phrase_clauses:
+// other clauses beside it go to plan_bool_phrase), no facet clauses, a snapshot
 // with positions -- or FG_EUNSUPPORTED naming the reason.  The slot's rows:
 // q_terms the phrase's distinct terms (the snapshot's ids), the lead -- the
 // shortest merged list -- first; q_pterm / q_ppos the (vocabulary id, offset)
@@ -77,7 +207,7 @@ struct PlanTables {
 // idfs summed in phrase order from 0.0 (a repeated term each time), times
 // (1 + K1).  Work items (k_phrase): groups of the lead list's chunks, as k_conj's.
 int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t nq_size, uint32_t n_segs,
-                PlanTables& h, int* phrase) {
+                PlanTables& h, int* phrase, bool beside) {
   *phrase = 0;
   const uint32_t b = q->q_off[i], e = q->q_off[i + 1], m = e - b;
   uint32_t n_clauses = 0, n_phr = 0;
@@ -98,7 +228,10 @@ int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_
   }
   if (!n_phr) return FG_OK;
   *phrase = 1;
-  if (n_clauses > 1) return fail(FG_EUNSUPPORTED, "query %u: phrase clause beside other clauses", i);
+  if (n_clauses > 1) {
+    if (!beside) return fail(FG_EUNSUPPORTED, "query %u: phrase clause beside other clauses", i);
+    return plan_bool_phrase(ix, q, i, nq_size, n_segs, h);
+  }
   if (q->f_off && q->f_off[i + 1] > q->f_off[i]) return fail(FG_EUNSUPPORTED, "query %u: phrase with facet filters", i);
   if (!ix->has_positions) return fail(FG_EUNSUPPORTED, "query %u: snapshot built without positions", i);
   if (q->phrase_pos[e - 1] >= (1u << 30)) return fail(FG_EINVAL, "query %u: phrase offset too large", i);
@@ -151,8 +284,9 @@ int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_
 // that batch: plan_pieces plans a snapshot's queries in pieces)
 // qtime: the plan forms its scores at query time (some snapshot's statistics
 // changed since its build: DevPlan::feat), so the descriptors point at payloads
+// beside: fg_phrase_clauses as the plan's creation read it
 int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t n_segs, PlanTables& h,
-              uint32_t nq_size, bool qtime) {
+              uint32_t nq_size, bool qtime, bool beside) {
   if (!ix || !q || (q->n_queries && !q->q_off)) return fail(FG_EINVAL, "bad arguments");
   if (q->n_queries && q->q_off[q->n_queries] > q->q_off[0] && !q->terms) return fail(FG_EINVAL, "q_off without terms");
   if (q->f_off && q->n_queries && q->f_off[q->n_queries] > q->f_off[0] && !q->f_terms)
@@ -178,6 +312,7 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
     if (!q->phrase_pos) return fail(FG_EINVAL, "phrase_len without phrase_pos");
     h.q_pterm.assign(nqt, 0);
     h.q_ppos.assign(nqt, 0);
+    if (beside) h.q_clause.assign(nqt, 0);
   }
 
   // ---- facet filters: one mask per distinct clause list (fg_internal.h DevFilters)
@@ -297,7 +432,7 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
     if (m > fg::kMaxTerms) return fail(FG_EUNSUPPORTED, "query %u has %u terms (> %u)", i, m, fg::kMaxTerms);
     if (q->phrase_len) {
       int phrase = 0;
-      if (int rc = plan_phrase(ix, q, i, nq_size, n_segs, h, &phrase)) return rc;
+      if (int rc = plan_phrase(ix, q, i, nq_size, n_segs, h, &phrase, beside)) return rc;
       if (phrase) continue;
     }
     if (q_nomatch[i]) continue;  // the facet clauses match nothing: no hits
@@ -513,7 +648,8 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
     qt |= !ixs[s]->same_stats;
     if (!fg::probe_addr_ok(ixs[s]->d)) return fail(FG_EUNSUPPORTED, "snapshot %u: device arrays above 2^47", s);
   }
-  if (S == 1) return plan_host(ixs[0], q, k, S, hs[0], nq1, qt);  // (used in place: nothing to join)
+  const bool beside = phrase_clauses_on.load(std::memory_order_relaxed) != 0;  // (read once per plan)
+  if (S == 1) return plan_host(ixs[0], q, k, S, hs[0], nq1, qt, beside);  // (used in place: nothing to join)
   J.clear();
   const size_t nq = (size_t)S * nq1, nqt = nq * fg::kMaxTerms;
   for (auto* v : {&J.q_m, &J.lead, &J.ngroup, &J.q_tier}) v->resize(nq);
@@ -523,6 +659,7 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
   J.q_probe.resize(nqt);
   if (q->phrase_len)
     for (auto* v : {&J.q_pterm, &J.q_ppos}) v->resize(nqt);
+  if (q->phrase_len && beside) J.q_clause.resize(nqt);
   auto put_slot = [&](uint32_t p) {  // piece p's per-query tables into its slots
     const PlanTables& h = hs[p];
     const size_t v0 = pc.slot(p), t0 = v0 * fg::kMaxTerms;
@@ -533,6 +670,7 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
     cp(J.q_ub, h.q_ub, t0); cp(J.q_wt, h.q_wt, t0); cp(J.q_wn, h.q_wn, t0); cp(J.q_rup, h.q_rup, t0);
     cp(J.q_probe, h.q_probe, t0);
     cp(J.q_pterm, h.q_pterm, t0); cp(J.q_ppos, h.q_ppos, t0);  // (empty without phrase_len)
+    cp(J.q_clause, h.q_clause, t0);
   };
   if (par) {
     std::vector<int> rcs(n, FG_OK);
@@ -543,14 +681,14 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
       qp.n_queries = b - a;
       qp.q_off = q->q_off + a;
       if (q->f_off) qp.f_off = q->f_off + a;
-      if ((rcs[p] = plan_host(ixs[p / pc.P], &qp, k, S, hs[p], nq1, qt))) errs[p] = fg_last_error();
+      if ((rcs[p] = plan_host(ixs[p / pc.P], &qp, k, S, hs[p], nq1, qt, beside))) errs[p] = fg_last_error();
       else put_slot(p);
     });
     for (uint32_t p = 0; p < n; ++p)
       if (rcs[p]) return fail(rcs[p], "snapshot %u: %s", p / pc.P, errs[p].c_str());
   } else {
     for (uint32_t s = 0; s < S; ++s) {
-      if (int rc = plan_host(ixs[s], q, k, S, hs[s], nq1, qt)) {
+      if (int rc = plan_host(ixs[s], q, k, S, hs[s], nq1, qt, beside)) {
         const std::string e = fg_last_error();
         return fail(rc, "snapshot %u: %s", s, e.c_str());
       }
@@ -584,6 +722,7 @@ PlanTables& join_pieces(const Pieces& pc, std::vector<PlanTables>& hs, PlanTable
     for (WItem x : h.ditems) { x.q += vb; J.ditems.push_back(x); }
     for (WItem x : h.scan) { x.q += vb; J.scan.push_back(x); }
     for (WItem x : h.phrase) { x.q += vb; J.phrase.push_back(x); }
+    for (WItem x : h.bphrase) { x.q += vb; J.bphrase.push_back(x); }
     J.nf += h.nf;
   }
   // one bin geometry per batch query over the snapshots where it has work
@@ -699,9 +838,9 @@ void sort_sweep(std::vector<WItem>& items, bool conj, const PlanTables& t, uint3
 struct WorkList {
   std::vector<uint32_t> work_q, work_c, work_n;
   std::vector<uint64_t> cand_off;
-  uint64_t n_single = 0, n_conj = 0, n_main = 0, n_scan = 0, n_phrase = 0;
+  uint64_t n_single = 0, n_conj = 0, n_main = 0, n_scan = 0, n_phrase = 0, n_bphrase = 0;
   uint32_t xcd_first[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // DevPlan::xcd_first
-  uint64_t count() const { return n_main + n_scan + n_phrase; }
+  uint64_t count() const { return n_main + n_scan + n_phrase + n_bphrase; }
 };
 
 // k_conj's multi-list items (sorted) cut into the 8 XCDs' stretches by expected
@@ -736,13 +875,13 @@ void xcd_stretches(const PlanTables& t, WorkList& w) {
 int order_items(PlanTables& t, uint32_t nq, uint32_t k, WorkList& w) {
   if (t.f_woff[t.nf] * 4 > (8ull << 30)) return fail(FG_EUNSUPPORTED, "facet masks of this batch exceed 8 GiB");
   if (t.ch_f.size() > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "facet postings of this batch too large");
-  if (t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() > 0x7FFFFFFFull)
+  if (t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() > 0x7FFFFFFFull)
     return fail(FG_EUNSUPPORTED, "batch too large (%zu work items)",
-                t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size());
+                t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size());
   sort_sweep(t.citems, true, t, nq);
   sort_sweep(t.ditems, false, t, nq);
   auto& items = t.items;
-  items.reserve(t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size());
+  items.reserve(t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size());
   items.insert(items.end(), t.citems.begin(), t.citems.end());
   w.n_conj = t.citems.size();
   items.insert(items.end(), t.ditems.begin(), t.ditems.end());
@@ -755,10 +894,14 @@ int order_items(PlanTables& t, uint32_t nq, uint32_t k, WorkList& w) {
   // k_phrase: each query's lead chunks in list order, the queries side by side (a sweep, as k_conj's)
   std::stable_sort(t.phrase.begin(), t.phrase.end(), [](const WItem& a, const WItem& b) { return a.key < b.key; });
   w.n_phrase = t.phrase.size();
-  const uint64_t chunks = w.count();  // work items (k_conj / k_disj, then k_scan, then k_phrase)
+  // k_bphrase: the same sweep (a union's passes side by side)
+  std::stable_sort(t.bphrase.begin(), t.bphrase.end(), [](const WItem& a, const WItem& b) { return a.key < b.key; });
+  w.n_bphrase = t.bphrase.size();
+  const uint64_t chunks = w.count();  // work items (k_conj / k_disj, then k_scan, k_phrase, k_bphrase)
   if (chunks > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "batch too large (%llu work items)", (unsigned long long)chunks);
   items.insert(items.end(), t.scan.begin(), t.scan.end());
   items.insert(items.end(), t.phrase.begin(), t.phrase.end());
+  items.insert(items.end(), t.bphrase.begin(), t.bphrase.end());
   w.work_q.resize(chunks);
   w.work_c.resize(chunks);
   w.work_n.resize(chunks);
@@ -849,6 +992,7 @@ int stage_and_upload(fg_plan* p, fg_index* const* ixs, PlanTables& t, const Work
   L.in(d.q_rup, t.q_rup.data(), 4 * nqt);
   L.in(d.q_pterm, t.q_pterm.data(), 4 * t.q_pterm.size());
   L.in(d.q_ppos, t.q_ppos.data(), 4 * t.q_ppos.size());
+  L.in(d.q_clause, t.q_clause.data(), 4 * t.q_clause.size());
   const size_t o_cache = L.add(4ull * 512 * S);  // (room for S even when fewer distinct caches are stored)
   L.in(d.f.q_filter, t.q_filter.data(), 4ull * nq);
   L.in(d.f.f_shift, t.f_shift.data(), 4ull * nf);
@@ -951,6 +1095,7 @@ void fill_view(fg_plan* p, fg_index* const* ixs, PlanTables& t, const WorkList& 
   p->d.n_conj = (uint32_t)w.n_conj;
   p->d.n_scan = (uint32_t)w.n_scan;
   p->d.n_phrase = (uint32_t)w.n_phrase;
+  p->d.n_bphrase = (uint32_t)w.n_bphrase;
   p->d.n_single = (uint32_t)w.n_single;
   std::copy(w.xcd_first, w.xcd_first + 9, p->d.xcd_first);
   p->d.k = p->k;
@@ -1035,6 +1180,11 @@ int fg_plan_create(fg_index* ix, const fg_query_batch* q, uint32_t k, fg_plan** 
 
 int fg_plan_create_multi(fg_index* const* ixs, uint32_t n_segs, const fg_query_batch* q, uint32_t k, fg_plan** out) {
   return fgh::plan_create_multi(ixs, n_segs, q, k, out, true, hipStreamPerThread);
+}
+
+int fg_phrase_clauses(int on) {
+  if (on < 0) return phrase_clauses_on.load(std::memory_order_relaxed);
+  return phrase_clauses_on.exchange(on != 0 ? 1 : 0, std::memory_order_relaxed);
 }
 
 int fg_plan_tiered_slots(const fg_plan* p, uint32_t* out) {

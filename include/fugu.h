@@ -388,10 +388,23 @@ typedef struct fg_query_batch {
    * clause, the query has no facet clauses, and every snapshot of the plan was
    * built with keep_positions; otherwise FG_EUNSUPPORTED ("phrase clause beside
    * other clauses", "phrase with facet filters", "snapshot built without
-   * positions").  A batch may mix phrase queries with the other shapes. */
+   * positions").  With fg_phrase_clauses(1) a phrase clause may also stand
+   * beside other clauses (below).  A batch may mix phrase queries with the other
+   * shapes. */
   const uint32_t* phrase_len;
   const uint32_t* phrase_pos;
 } fg_query_batch;
+
+/* Queries that hold a phrase clause BESIDE other clauses (term or phrase clauses,
+ * any occur) run on the device (k_bphrase) when on != 0.
+ * Process-wide, off by default, read when a plan is created (fg_plan_create[_multi],
+ * and so fg_search_batch, fg_search_sharded, fg_db_search*).  on: 1 / 0 sets it,
+ * < 0 only asks.  Returns the previous setting.  Off: such a query is
+ * FG_EUNSUPPORTED "phrase clause beside other clauses", as before.  On: the
+ * clauses join as the term clauses of `occur` do (a phrase clause's cost among
+ * the Musts: the sum over the two fields of its terms' smallest doc count there);
+ * such a query still takes no facet clauses and needs snapshots with positions. */
+int fg_phrase_clauses(int on);
 
 /* Plan a batch: host-side query planning (tantivy Weight creation: terms
  * ordered by cost, query/intersection.rs) and upload of the plan to HBM.

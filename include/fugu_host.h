@@ -32,8 +32,12 @@
  * splits into several tokens (`e-mail`, `user@example.com`, `3.14`) or a quoted
  * literal ("new york"), when the phrase is the query's only clause and no facet
  * filter is given (segments built with FUGU_POSITIONS=0 keep no positions and
- * refuse them).  Queries outside the device subset (a phrase beside other
- * clauses or with filters, slop / prefix suffixes on a quoted literal, field:,
+ * refuse them).  With fg_phrase_clauses(1) (fugu.h; process-wide, off by
+ * default) a phrase may also stand beside other clauses (`e-mail server`,
+ * `+e-mail -spam`, `"new york" pizza`: k_bphrase); fg_db_search* then run such
+ * queries as they are.  Queries outside the device subset (a phrase beside other
+ * clauses while that switch is off, a phrase with filters, slop / prefix
+ * suffixes on a quoted literal, field:,
  * boosts, a text query with filters that parse to no facet term) return
  * FG_EUNSUPPORTED: the reference host then runs tantivy; this library never
  * answers them on the CPU.  Empty queries (AllQuery), facet-only queries and
