@@ -72,6 +72,8 @@ int check_batch(const fg_query_batch* q, std::vector<Clauses>& out) {
     if (e - b > fg::kMaxTerms) return fail(FG_EUNSUPPORTED, "query %u has %u terms (> %u)", i, e - b, fg::kMaxTerms);
     c.text = e > b;
     for (uint32_t j = b; j < e; ++j) {
+      if (q->phrase_len && (q->phrase_len[j] & (FG_CLAUSE_ANY | FG_CLAUSE_ALL)) && fg_group_clauses(-1) > 0)
+        return fail(FG_EUNSUPPORTED, "query %u: group clause in a count query", i);
       if (q->phrase_len && q->phrase_len[j] >= 2) return fail(FG_EUNSUPPORTED, "query %u: phrase clause in a count query", i);
       const uint8_t oc = q->occur ? q->occur[j] : (q->mode == FG_MODE_OR ? FG_OCCUR_SHOULD : FG_OCCUR_MUST);
       if (oc > FG_OCCUR_MUST_NOT) return fail(FG_EINVAL, "query %u: bad occur %u", i, (unsigned)oc);

@@ -280,6 +280,17 @@ __host__ __device__ inline uint32_t cl_occur(uint32_t c) { return (c >> 9) & 3u;
 // a k_bphrase work item's work_n: the lead chunks of its group, and above them the
 // clause it leads from (a Should-driven query: the pass)
 constexpr uint32_t kBpPassShift = 8;
+// A slot of k_group (a group clause: fg_group_clauses): q_m and the
+// q_clause row as k_bphrase's (no phrase bit), a group clause marked kClAny (a
+// nested Should-only query) or kClAll (a nested Must-only one) with its members
+// in [cl_first, cl_first + cl_terms) of the slot's q_terms / q_wt / q_wn / q_ub /
+// q_rup rows -- PER MEMBER here: the snapshot's term id, the two field weights,
+// the member's largest current score (its scaled tmaxs) and its bound factor.
+// An all-of group's members stand in (cost, position) order.
+constexpr uint32_t kClAny = 1u << 12, kClAll = 1u << 13;
+// a k_group work item's work_n: the lead chunks of its group, above them the
+// clause it leads from and that clause's member whose list it sweeps (the pass)
+constexpr uint32_t kGrpClauseShift = 8, kGrpMemberShift = 12;
 
 // Rank words (DevIndex::rank): one u64 per 32 docs, the low half the docs'
 // presence bits, the high half the number of the term's postings before the
@@ -740,6 +751,9 @@ struct DevPlan {
                                 // (local ids / vocabulary ids / offsets), clause after clause in q_clause's
                                 // order, a phrase's anchor first; q_wt / q_wn [row][c] are clause c's weights
   const uint32_t* q_clause;     // [nq * kMaxTerms] the clause table (cl_pack); empty without such a slot
+  uint32_t n_group;             // k_group work items (queries with a group clause: fg_group_clauses), after the
+                                // k_bphrase items: (query slot, group of kChunk-posting chunks of a lead list,
+                                // the (clause, member) led from in work_n's upper bits)
   // Multi-snapshot plans (several segments / doc shards / namespaces of one
   // device in ONE launch per kernel): query slot v = s * seg_nq + q is query q
   // of the batch on snapshot segs[s]; every per-query array above is indexed by
@@ -1012,6 +1026,7 @@ hipError_t launch_fmask(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 hipError_t launch_scan(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 hipError_t launch_phrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 hipError_t launch_bphrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
+hipError_t launch_group(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 // out_shard != nullptr: the merged select of a multi-snapshot plan (one list per batch query)
 hipError_t launch_final(const DevPlan& pl, float* out_score, uint32_t* out_doc, uint32_t* out_n, hipStream_t s,
                         uint32_t* out_shard = nullptr);

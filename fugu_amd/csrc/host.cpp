@@ -388,7 +388,15 @@ class DocStore {
 //   `t1 OR t2 OR ...`     every term Should (the same query as `t1 t2 ...`)
 // A term that analyzes to several tokens (`e-mail`, `user@example.com`) and a
 // quoted literal ("new york") are PhraseQuery clauses at slop 0 (parse_clauses).
-// Anything else (mixed AND / OR, parentheses, field:, slop, boosts, ranges, a
+// With fg_group_clauses(1) (fugu.h; off by default) one level of grouping over
+// plain single-token words is in the subset too (parse_group): a
+// parenthesised group where a word may stand -- `(a b)`, `(a OR b)` any-of,
+// `(a AND b)`, `(+a +b)` all-of, bare / `+` / `-` / an operand of the uniform
+// forms -- and mixed infix `a AND b OR c AND d`, where AND binds tighter
+// (tantivy-query-grammar 0.24): Should clauses, an AND-run of several words an
+// all-of group.
+// Anything else (mixed AND / OR and parentheses while that switch is off, field:,
+// slop, boosts, ranges, a
 // query of MustNot clauses only) is FG_EUNSUPPORTED: the reference host runs tantivy.
 // An empty query is AllQuery (src/db/search.rs:115-116), handled by the caller.
 bool is_special(char c) {
@@ -405,11 +413,84 @@ bool is_special(char c) {
 // One clause of a parsed query: a term (one token) or a phrase (several, with
 // each token's position offset from the first: a token the analyzer drops in
 // between leaves a hole -- PhraseQuery::new_with_offset).
+// A group (fg_group_clauses): `terms` are its members, joined any-of (a nested
+// Should-only BooleanQuery) or all-of (a nested Must-only one); every pos is 0.
 struct Clause {
   uint8_t occur = FG_OCCUR_SHOULD;
   std::vector<std::string> terms;
   std::vector<uint32_t> pos;
+  uint8_t group = 0;  // kGroupAny / kGroupAll; 0: a term or a phrase
 };
+constexpr uint8_t kGroupAny = 1, kGroupAll = 2;
+
+bool is_operator_word(std::string_view w) { return w == "AND" || w == "OR" || w == "NOT" || w == "IN" || w == "TO"; }
+
+// A plain word that analyzes to ONE token (a group's member), or `why`
+int group_word(std::string_view w, std::string& tok, std::string& why) {
+  if (is_operator_word(w)) { why = "operator outside the supported forms"; return FG_EUNSUPPORTED; }
+  for (size_t c = 0; c < w.size(); ++c)
+    if (is_special(w[c]) && !(w[c] == '-' && c >= 1)) {
+      why = w[c] == '"' ? "a quoted literal inside a group"
+                        : w[c] == '(' || w[c] == ')' ? "a group inside a group" : "query syntax beyond bare/+/-/AND/OR terms";
+      return FG_EUNSUPPORTED;
+    }
+  std::vector<std::string> toks;
+  std::vector<uint32_t> pos;
+  analyze(w, toks, &pos);
+  if (toks.empty()) { why = "a term analyzes to no token"; return FG_EUNSUPPORTED; }
+  if (toks.size() > 1) { why = "a group member analyzes to several tokens"; return FG_EUNSUPPORTED; }
+  tok = std::move(toks[0]);
+  return FG_OK;
+}
+
+// The inside of a parenthesised group: one uniform form over plain words --
+// `a b c` / `a OR b` any-of, `a AND b` / `+a +b` all-of; one word is that word
+// (cl.group stays 0).  `-`, mixed prefixes, mixed operators: `why`.
+int parse_group(std::string_view body, Clause& cl, std::string& why) {
+  std::vector<std::string_view> ws;
+  for (size_t i = 0; i < body.size();) {
+    while (i < body.size() && (body[i] == ' ' || body[i] == '\t' || body[i] == '\n' || body[i] == '\r')) ++i;
+    const size_t s = i;
+    while (i < body.size() && !(body[i] == ' ' || body[i] == '\t' || body[i] == '\n' || body[i] == '\r')) ++i;
+    if (i > s) ws.push_back(body.substr(s, i - s));
+  }
+  if (ws.empty()) { why = "an empty group"; return FG_EUNSUPPORTED; }
+  auto infix = [&](std::string_view op) {
+    bool ok = ws.size() >= 3 && ws.size() % 2 == 1;
+    for (size_t w = 1; ok && w < ws.size(); w += 2) ok = ws[w] == op;
+    return ok;
+  };
+  std::vector<std::string_view> words;
+  uint8_t kind = kGroupAny;
+  if (infix("AND") || infix("OR")) {
+    kind = ws[1] == "AND" ? kGroupAll : kGroupAny;
+    for (size_t w = 0; w < ws.size(); w += 2) {
+      if (ws[w][0] == '+' || ws[w][0] == '-') { why = "a prefix beside AND / OR inside a group"; return FG_EUNSUPPORTED; }
+      words.push_back(ws[w]);
+    }
+  } else {
+    size_t plus = 0;
+    for (std::string_view w : ws) {
+      if (w.size() > 1 && w[0] == '-') { why = "a MustNot member inside a group"; return FG_EUNSUPPORTED; }
+      const bool p = w.size() > 1 && w[0] == '+';
+      plus += p;
+      words.push_back(p ? w.substr(1) : w);
+    }
+    if (plus && plus != ws.size()) { why = "mixed prefixes inside a group"; return FG_EUNSUPPORTED; }
+    if (plus) kind = kGroupAll;
+    const bool has_and = std::find(words.begin(), words.end(), "AND") != words.end();
+    const bool has_or = std::find(words.begin(), words.end(), "OR") != words.end();
+    if (has_and && has_or) { why = "mixed AND / OR inside a group"; return FG_EUNSUPPORTED; }
+  }
+  for (std::string_view w : words) {
+    std::string tok;
+    if (int rc = group_word(w, tok, why)) return rc;
+    cl.terms.push_back(std::move(tok));
+    cl.pos.push_back(0);
+  }
+  cl.group = cl.terms.size() > 1 ? kind : 0;
+  return FG_OK;
+}
 
 // The clauses of a query.  A literal is a word or a quoted "..." (no `\` or `"`
 // inside, nothing but white space after the closing quote: slop `~` and prefix
@@ -418,7 +499,8 @@ struct Clause {
 // tokens is a phrase, to one a term; to none: FG_EUNSUPPORTED, as before.
 int parse_clauses(std::string_view q, std::vector<Clause>& out, std::string& why) {
   out.clear();
-  struct Item { std::string_view body; bool quoted; bool prefixed; uint8_t occur; };
+  const bool groups = fg_group_clauses(-1) > 0;
+  struct Item { std::string_view body; bool quoted; bool prefixed; uint8_t occur; bool group = false; };
   std::vector<Item> items;
   auto space = [](char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r'; };
   size_t i = 0;
@@ -426,6 +508,25 @@ int parse_clauses(std::string_view q, std::vector<Clause>& out, std::string& why
     while (i < q.size() && space(q[i])) ++i;
     if (i >= q.size()) break;
     size_t s = i;
+    if (groups) {  // a parenthesised group, bare or behind + / -, runs to its closing parenthesis
+      const size_t open = s + ((q[s] == '+' || q[s] == '-') && s + 1 < q.size() ? 1 : 0);
+      if (q[open] == '(') {
+        const size_t close = q.find(')', open + 1);
+        if (close == std::string_view::npos) { why = "unterminated group"; return FG_EUNSUPPORTED; }
+        const std::string_view body = q.substr(open + 1, close - open - 1);
+        if (body.find('(') != std::string_view::npos) { why = "a group inside a group"; return FG_EUNSUPPORTED; }
+        if (body.find('"') != std::string_view::npos) { why = "a quoted literal inside a group"; return FG_EUNSUPPORTED; }
+        if (close + 1 < q.size() && !space(q[close + 1])) {
+          why = "query syntax beyond bare/+/-/AND/OR terms after a group (boost, slop)";
+          return FG_EUNSUPPORTED;
+        }
+        Item it{body, false, open > s, FG_OCCUR_SHOULD, true};
+        if (open > s) it.occur = q[s] == '+' ? FG_OCCUR_MUST : FG_OCCUR_MUST_NOT;
+        items.push_back(it);
+        i = close + 1;
+        continue;
+      }
+    }
     while (i < q.size() && !space(q[i])) {
       if (q[i] == '"') {  // a quoted literal runs to its closing quote, white space included
         const size_t close = q.find('"', i + 1);
@@ -462,8 +563,36 @@ int parse_clauses(std::string_view q, std::vector<Clause>& out, std::string& why
     for (size_t w = 1; ok && w < items.size(); w += 2) ok = is_op(items[w], op);
     return ok;
   };
+  // mixed infix `a AND b OR c AND d` (fg_group_clauses): AND binds tighter, so the
+  // query is the Should clauses of its AND-runs; a run of several plain words is
+  // an all-of group, a single operand stands as it is
+  auto mixed_form = [&]() {
+    bool ok = groups && items.size() >= 3 && items.size() % 2 == 1, a = false, o = false;
+    for (size_t w = 1; ok && w < items.size(); w += 2) {
+      a |= is_op(items[w], "AND");
+      o |= is_op(items[w], "OR");
+      ok = is_op(items[w], "AND") || is_op(items[w], "OR");
+    }
+    return ok && a && o;
+  };
   std::vector<Item> raw;
-  if (binary_form("AND") || binary_form("OR")) {
+  std::vector<std::pair<size_t, size_t>> runs;  // mixed infix: each raw item's AND-run [first, last] in `items`
+  if (mixed_form()) {
+    for (size_t w = 0; w < items.size();) {
+      size_t last = w;
+      while (last + 2 < items.size() && is_op(items[last + 1], "AND")) last += 2;
+      for (size_t x = w; x <= last; x += 2) {
+        if (items[x].prefixed) { why = "query syntax beyond bare/+/-/AND/OR terms"; return FG_EUNSUPPORTED; }
+        if (last > w && items[x].group) { why = "a group inside a group"; return FG_EUNSUPPORTED; }
+        if (last > w && items[x].quoted) { why = "a quoted literal inside a group"; return FG_EUNSUPPORTED; }
+      }
+      Item it = items[w];
+      it.occur = FG_OCCUR_SHOULD;
+      raw.push_back(it);
+      runs.emplace_back(w, last);
+      w = last + 2;
+    }
+  } else if (binary_form("AND") || binary_form("OR")) {
     const uint8_t oc = items[1].body == "AND" ? FG_OCCUR_MUST : FG_OCCUR_SHOULD;
     for (size_t w = 0; w < items.size(); w += 2) {
       Item it = items[w];
@@ -475,8 +604,27 @@ int parse_clauses(std::string_view q, std::vector<Clause>& out, std::string& why
     raw = items;
   }
   bool positive = false;
-  for (const Item& it : raw) {
+  for (size_t r = 0; r < raw.size(); ++r) {
+    const Item& it = raw[r];
     const std::string_view w = it.body;
+    if (it.group || (!runs.empty() && runs[r].second > runs[r].first)) {
+      Clause cl;
+      cl.occur = it.occur;
+      if (it.group) {
+        if (int rc = parse_group(w, cl, why)) return rc;
+      } else {  // an AND-run of plain words
+        for (size_t x = runs[r].first; x <= runs[r].second; x += 2) {
+          std::string tok;
+          if (int rc = group_word(items[x].body, tok, why)) return rc;
+          cl.terms.push_back(std::move(tok));
+          cl.pos.push_back(0);
+        }
+        cl.group = kGroupAll;
+      }
+      positive |= cl.occur != FG_OCCUR_MUST_NOT;
+      out.push_back(std::move(cl));
+      continue;
+    }
     if (!it.quoted) {
       if (w == "AND" || w == "OR" || w == "NOT" || w == "IN" || w == "TO") {
         why = "operator outside the supported forms";
@@ -514,6 +662,10 @@ int parse_query(std::string_view q, std::vector<std::string>& terms, std::vector
   std::vector<Clause> cl;
   if (int rc = parse_clauses(q, cl, why)) return rc;
   for (auto& c : cl) {
+    if (c.group) {
+      why = "a group clause (a nested BooleanQuery)";
+      return FG_EUNSUPPORTED;
+    }
     if (c.terms.size() != 1) {
       why = "a term analyzes to several tokens (PhraseQuery)";
       return FG_EUNSUPPORTED;
@@ -1152,10 +1304,11 @@ int search_hits(fg_db* db, Namespace& ns, const char* query, const std::vector<s
     if (rc) return hfail(rc, "query outside the device subset: " + why);
     for (Clause& c : cls) {
       any_phrase |= c.terms.size() > 1;
+      const uint32_t flag = c.group == kGroupAny ? FG_CLAUSE_ANY : c.group == kGroupAll ? FG_CLAUSE_ALL : 0u;
       for (size_t j = 0; j < c.terms.size(); ++j) {
         terms.push_back(std::move(c.terms[j]));
         occur.push_back(c.occur);
-        plen.push_back(j == 0 ? (uint32_t)c.terms.size() : 0u);
+        plen.push_back(j == 0 ? (uint32_t)c.terms.size() | flag : 0u);
         ppos.push_back(c.pos[j]);
       }
     }
@@ -1236,6 +1389,7 @@ int count_query(Namespace& ns, const char* query, const std::vector<std::string>
     int rc = parse_clauses(qv, cls, why);
     if (rc) return hfail(rc, "query outside the device subset: " + why);
     for (Clause& c : cls) {
+      if (c.group) return hfail(FG_EUNSUPPORTED, "query outside the device subset: group clause in a count query");
       if (c.terms.size() > 1) return hfail(FG_EUNSUPPORTED, "query outside the device subset: phrase clause in a count query");
       terms.push_back(std::move(c.terms[0]));
       occur.push_back(c.occur);
@@ -2786,6 +2940,15 @@ int fg_parse_query_clauses(const char* query, char* out, size_t cap, size_t* len
     if (i) o.push_back('\n');
     o.push_back((char)('0' + cls[i].occur));
     o.push_back(':');
+    if (cls[i].group) {  // "(a | b)" any-of, "(a & b)" all-of
+      o.push_back('(');
+      for (size_t j = 0; j < cls[i].terms.size(); ++j) {
+        if (j) o += cls[i].group == kGroupAny ? " | " : " & ";
+        o += cls[i].terms[j];
+      }
+      o.push_back(')');
+      continue;
+    }
     for (size_t j = 0; j < cls[i].terms.size(); ++j) {
       if (j) o.push_back(' ');
       o += cls[i].terms[j] + "@" + std::to_string(cls[i].pos[j]);

@@ -2587,6 +2587,224 @@ __global__ __launch_bounds__(kThreads) void k_bphrase(DevIndex ix0, DevPlan pl) 
   flush_candidates(pl, q, sh.s.buf, sh.s.n_buf, sh.s.thr, sh.s.scratch);
 }
 
+// ---------------------------------------------------------------- k_group
+// Queries with a group clause (one level of grouping over plain terms: an any-of
+// group is a nested Should-only BooleanQuery, an all-of group a nested Must-only
+// one; fg_group_clauses).  The slot's clause table
+// (DevPlan::q_clause, fg_internal.h kClAny / kClAll) lists its clauses in the
+// order of the score sum, each with its member range in the slot's per-member
+// rows.  A work item is a group of kChunk-posting chunks of ONE lead list: member
+// pm of clause pc (work_n's upper bits), the pass.  The planner's passes:
+//  * a Must that is a term or an all-of group exists: one pass, the shortest list
+//    among those clauses' members (every hit holds it);
+//  * every Must is an any-of group: one pass per member of the first (cheapest)
+//    one; pass (0, pm) leaves a doc that holds a member x < pm to pass (0, x);
+//  * no Must: a pass per Should term clause, per Should all-of group (its
+//    shortest member) and per member of every Should any-of group; pass (pc, pm)
+//    leaves a doc that an earlier Should clause matches, or that holds a member
+//    x < pm of clause pc, to that earlier pass.
+// So every hit leaves exactly one pass, with its whole score, and k_final's keys
+// stay unique.  One LANE per lead doc, kRound docs between truncations: the lane
+// walks the clause table, looks every member up (posting_pos_at: rank words or
+// the bucket directory; the lead member's position is the lane's own), scores
+// the present ones with tfn_score (the query-time form, bit-identical to the
+// build-time scores) and joins them as tantivy does: an any-of group its present
+// members from 0.0 in written order, an all-of group (s0 + s1) + (0.0 + s2 + ...)
+// in (cost, position) order, then the clauses (s0 + s1) + (0.0 + s2 + ...) over the
+// Musts, (0.0 + req) + opt with opt the matching Shoulds from 0.0.  Keys go
+// through k_scan's buffer, threshold word and flush.
+// Pruning (exact): a lead chunk is skipped when the same sum over UPPER bounds --
+// the lead member's min(cmax[chunk] * q_rup, its scaled tmaxs), every other
+// member's scaled tmaxs (q_ub), members and clauses the pass knows absent left
+// out -- is below the item's threshold: every score is >= 0, f32 addition is
+// monotone in both arguments, so the bound is >= the score of every doc of the
+// chunk that this pass can emit, and doc 0 gives the largest key of a score.
+struct GroupShared {
+  ScanShared s;
+  float cache[512];            // the tf caches, text then name
+  uint32_t cl[kMaxTerms];      // the clause table
+  uint32_t tmeta[kMaxTerms];   // per member: the probe tables,
+  uint32_t tdir[kMaxTerms];
+  uint64_t toff[kMaxTerms];
+  float wt[kMaxTerms];         // ... the field weights
+  float wn[kMaxTerms];
+  float ub[kMaxTerms];         // ... and the largest current score
+};
+
+// posting_pos on staged probe metadata
+__device__ inline uint32_t posting_pos_at(const DevIndex& ix, uint32_t meta, uint64_t base, uint32_t dir_off,
+                                          uint32_t d) {
+  const uint32_t slot = meta_slot(meta);
+  if (slot) return rank_pos(rank_word_of(ix, slot, d), d);
+  const uint32_t* __restrict__ dir = ix.dir + dir_off;
+  const uint32_t b = d >> (meta & 0xFFu);
+  uint32_t lo = dir[b], hi = dir[b + 1];
+  const uint32_t end = hi;
+  const uint32_t* __restrict__ di = ix.doc + base;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (di[mid] < d) lo = mid + 1; else hi = mid;
+  }
+  return lo < end && di[lo] == d ? lo : kInvalid;
+}
+
+// member x of the slot in doc d: its score, or absent.  pos: the member's posting when known (the lead), else kInvalid
+__device__ inline bool group_member(const DevIndex& ix, const GroupShared& sh, uint32_t x, uint32_t d, uint32_t pos,
+                                    float& s) {
+  if (pos == kInvalid) pos = posting_pos_at(ix, sh.tmeta[x], sh.toff[x], sh.tdir[x], d);
+  if (pos == kInvalid) return false;
+  const uint64_t p = sh.toff[x] + pos;
+  uint32_t v = ix.tfn[p];
+  if (ix.tfn_name) v |= (uint32_t)ix.tfn_name[p] << 16;
+  s = tfn_score(ix, p, v, sh.wt[x], sh.wn[x], sh.cache, sh.cache + 256);
+  return true;
+}
+
+// The score sum over upper bounds for pass (pc, pm) with the lead member bounded by `lead_ub` (uniform)
+__device__ inline float group_bound(const GroupShared& sh, uint32_t ncl, uint32_t nt, bool must, uint32_t pc,
+                                    uint32_t pm, float lead_ub) {
+  float req = 0.0f, oth = 0.0f, opt = 0.0f;
+  uint32_t nm = 0;
+  for (uint32_t ci = 0; ci < ncl; ++ci) {
+    const uint32_t cw = sh.cl[ci], oc = cl_occur(cw), t0 = cl_first(cw), t1 = min(t0 + cl_terms(cw), nt);
+    if (oc == kClMustNot || (!must && ci < pc)) continue;  // excluding, or absent in this pass's docs
+    float a = 0.0f, b = 0.0f;
+    for (uint32_t x = t0; x < t1; ++x) {
+      const bool lead = ci == pc && x - t0 == pm;
+      if ((cw & kClAny) && ci == pc && x - t0 < pm) continue;  // absent in this pass's docs
+      const float u = lead ? lead_ub : sh.ub[x];
+      if (!(cw & kClAll) || x - t0 < 2) a = x == t0 ? (cw & kClAny ? 0.0f + u : u) : a + u;
+      else b = b + u;
+    }
+    float cb = a;
+    if ((cw & kClAll) && t1 - t0 > 1) cb = 0.0f + (a + b);
+    if (oc == kClMust) {
+      if (nm == 0) req = cb;
+      else if (nm == 1) req = req + cb;
+      else oth = oth + cb;
+      ++nm;
+    } else {
+      opt = opt + cb;
+    }
+  }
+  if (!must) return opt;
+  if (nm > 1) req = req + oth;
+  return (0.0f + req) + opt;
+}
+
+template <bool kMulti>
+__global__ __launch_bounds__(kThreads, 4) void k_group(DevIndex ix0, DevPlan pl) {
+  __shared__ GroupShared sh;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t w = pl.total_chunks + pl.n_scan + pl.n_phrase + pl.n_bphrase + blockIdx.x;  // after the k_bphrase items
+  const uint32_t q = pl.work_q[w];
+  const DevIndex ix = kMulti ? seg_index(pl, __builtin_amdgcn_readfirstlane(q / pl.seg_nq)) : ix0;
+  const uint32_t ql = kMulti ? __builtin_amdgcn_readfirstlane(q % pl.seg_nq) : q;
+  const uint32_t chunk0 = pl.work_c[w];
+  const uint32_t wn = pl.work_n[w];
+  const uint32_t nchunk = wn & ((1u << kGrpClauseShift) - 1u);
+  const uint32_t K = pl.k;
+  uint64_t* gthr = &pl.thresh[ql];
+  const uint32_t qm = pl.q_m[q];
+  const uint32_t ncl = min(qm_terms(qm), kMaxTerms), nt = min(qm_phrase_terms(qm), kMaxTerms);
+  if (ncl == 0 || nt == 0) return;  // (never planned; uniform)
+  const uint32_t pc = min((wn >> kGrpClauseShift) & 15u, ncl - 1);
+  const size_t row = (size_t)q * kMaxTerms;
+  if (tid < nt) {
+    const uint32_t t = pl.q_terms[row + tid];
+    sh.tmeta[tid] = ix.tmeta[t];
+    sh.tdir[tid] = ix.dir_off[t];
+    sh.toff[tid] = ix.off[t];
+    sh.wt[tid] = pl.q_wt[row + tid];
+    sh.wn[tid] = pl.q_wn[row + tid];
+    sh.ub[tid] = pl.q_ub[row + tid];
+  }
+  if (tid < ncl) sh.cl[tid] = pl.q_clause[row + tid];
+  for (uint32_t i = tid; i < 512u; i += kThreads) sh.cache[i] = ix.cache[i];
+  if (tid == 0) {
+    sh.s.n_buf = 0;
+    sh.s.thr = atomicMax(reinterpret_cast<unsigned long long*>(gthr), 0ull);
+  }
+  __syncthreads();
+  const bool must = cl_occur(sh.cl[0]) == kClMust;  // (the Musts stand first)
+  const uint32_t pcw = sh.cl[pc];
+  const uint32_t pm = min((wn >> kGrpMemberShift) & 15u, max(cl_terms(pcw), 1u) - 1u);
+  const uint32_t li = min(cl_first(pcw) + pm, nt - 1);  // the lead: member pm of clause pc
+  const uint32_t lead = pl.q_terms[row + li];
+  const uint64_t base = sh.toff[li];
+  const uint32_t df = (uint32_t)(ix.off[lead + 1] - base);
+  const float* __restrict__ cmax = ix.cmax + ix.coff[lead];
+  const float rup = pl.q_rup[row + li];
+  for (uint32_t c = 0; c < nchunk; ++c) {
+    const uint32_t i0 = (chunk0 + c) * kChunk;
+    if (i0 >= df) break;
+    // the chunk's bound against the threshold (uniform: sh.s.thr is read after a barrier)
+    const float bound = group_bound(sh, ncl, nt, must, pc, pm, fminf(cmax[chunk0 + c] * rup, sh.ub[li]));
+    if (make_key(inflate_bound(bound), 0u) < sh.s.thr) continue;
+    for (uint32_t r0 = 0; r0 < kChunk; r0 += kRound) {
+      const uint64_t thr = sh.s.thr;
+      for (uint32_t j = 0; j < kRound / kThreads; ++j) {
+        const uint32_t i = i0 + r0 + j * kThreads + tid;
+        bool keep = i < df;
+        uint32_t d = 0;
+        if (keep) {
+          d = ix.doc[base + i];
+          keep = doc_alive(ix, d);
+        }
+        float req = 0.0f, oth = 0.0f, opt = 0.0f;
+        uint32_t nm = 0;
+        bool any = false;
+        for (uint32_t ci = 0; ci < ncl && keep; ++ci) {
+          const uint32_t cw = sh.cl[ci], oc = cl_occur(cw), t0 = cl_first(cw), t1 = min(t0 + cl_terms(cw), nt);
+          // the clause in the doc: a term, an any-of group (some member) or an all-of group (every member)
+          float a = 0.0f, b = 0.0f;
+          bool on = (cw & kClAll) != 0;
+          for (uint32_t x = t0; x < t1; ++x) {
+            float s = 0.0f;
+            const bool has = group_member(ix, sh, x, d, ci == pc && x - t0 == pm ? i : kInvalid, s);
+            if (cw & kClAll) {
+              if (!has) { on = false; break; }
+              if (x - t0 < 2) a = x == t0 ? s : a + s;
+              else b = b + s;
+            } else if (has) {
+              if ((cw & kClAny) && ci == pc && x - t0 < pm) keep = false;  // an earlier member's pass has the doc
+              a = on || (cw & kClAny) ? a + s : s;
+              on = true;
+            }
+          }
+          const float cs = (cw & kClAll) && t1 - t0 > 1 ? 0.0f + (a + b) : a;
+          if (oc == kClMust) {
+            if (!on) keep = false;
+            else if (nm == 0) req = cs;
+            else if (nm == 1) req = req + cs;
+            else oth = oth + cs;
+            ++nm;
+          } else if (oc == kClMustNot) {
+            if (on) keep = false;
+          } else if (!must && ci <= pc && on != (ci == pc)) {
+            keep = false;  // an earlier pass's doc, or the pass clause does not match
+          } else if (on) {
+            opt = opt + cs;
+            any = true;
+          }
+        }
+        float sc = opt;
+        if (must) {
+          if (nm > 1) req = req + oth;
+          sc = 0.0f + req;
+          if (any) sc = sc + opt;
+        }
+        const uint64_t key = make_key(sc, d);
+        wave_append(keep && key >= thr, key, sh.s.buf, &sh.s.n_buf, kBufD);
+      }
+      __syncthreads();
+      scan_truncate(sh.s, K, kTrunc, gthr, false, pl.pub_mask, pl, ql);
+    }
+    scan_truncate(sh.s, K, K, gthr, true, pl.pub_mask, pl, ql);
+  }
+  flush_candidates(pl, q, sh.s.buf, sh.s.n_buf, sh.s.thr, sh.s.scratch);
+}
+
 // ---------------------------------------------------------------- k_final
 // Dynamic LDS (80 KB: 2 workgroups per CU): candidate keys, the k winners,
 // the radix histogram.  Keeps 16-B alignment of the dynamic base (no static
@@ -2932,6 +3150,13 @@ hipError_t launch_bphrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s) 
   if (pl.n_bphrase == 0) return hipSuccess;
   if (pl.segs) k_bphrase<true><<<pl.n_bphrase, kThreads, 0, s>>>(ix, pl);
   else k_bphrase<false><<<pl.n_bphrase, kThreads, 0, s>>>(ix, pl);
+  return hipGetLastError();
+}
+
+hipError_t launch_group(const DevIndex& ix, const DevPlan& pl, hipStream_t s) {
+  if (pl.n_group == 0) return hipSuccess;
+  if (pl.segs) k_group<true><<<pl.n_group, kThreads, 0, s>>>(ix, pl);
+  else k_group<false><<<pl.n_group, kThreads, 0, s>>>(ix, pl);
   return hipGetLastError();
 }
 

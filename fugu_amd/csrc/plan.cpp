@@ -25,6 +25,8 @@ namespace {
 // fg_phrase_clauses: queries with a phrase clause beside other clauses run on the
 // device (k_bphrase); process-wide, off by default, read when a plan is created
 std::atomic<int> phrase_clauses_on{0};
+// fg_group_clauses: queries with a group clause run on the device (k_group); the same contract
+std::atomic<int> group_clauses_on{0};
 
 // stable LSD radix sort of `a` by its bits 32..63 (three 11-bit passes)
 void radix_sort_hi32(std::vector<uint64_t>& a, std::vector<uint64_t>& tmp) {
@@ -49,7 +51,8 @@ struct PlanTables {
   std::vector<uint32_t> q_m, q_terms, lead, q_filter, ngroup, q_hlo, q_hhi, q_hsh;
   std::vector<uint32_t> q_tier;  // DevPlan::q_tier: slots that lead from a score-tiered copy
   std::vector<uint32_t> q_pterm, q_ppos;  // phrase queries' (term, offset) rows; empty without phrase_len
-  std::vector<uint32_t> q_clause;         // DevPlan::q_clause (k_bphrase slots); empty unless fg_phrase_clauses is on
+  std::vector<uint32_t> q_clause;         // DevPlan::q_clause (k_bphrase / k_group slots); empty unless fg_phrase_clauses
+                                          // or fg_group_clauses is on
   std::vector<uint64_t> thr0;
   std::vector<float> q_ub, q_wt, q_wn, q_rup;
   std::vector<fg::ProbeDesc> q_probe;  // k_conj slots' probe descriptors (rows as above)
@@ -59,15 +62,15 @@ struct PlanTables {
   std::vector<uint64_t> f_woff;
   std::vector<float> f_tab, f_max;
   std::vector<uint32_t> ch_f, ch_c, ch_t, ch_s;
-  // work items: k_conj's, k_disj's, k_scan's, k_phrase's, k_bphrase's; items: all
+  // work items: k_conj's, k_disj's, k_scan's, k_phrase's, k_bphrase's, k_group's; items: all
   // of them as the kernels run them (order_items, joined tables only)
-  std::vector<WItem> citems, ditems, scan, phrase, bphrase, items;
+  std::vector<WItem> citems, ditems, scan, phrase, bphrase, group, items;
   // (a thread's plans reuse one set: assign / push_back into kept capacity, no
   // page faults on fresh arrays -- ~0.2 ms of an 8-snapshot batch's planning)
   void clear() {
     auto all = [](auto&... v) { (v.clear(), ...); };
     all(q_m, q_terms, lead, q_filter, ngroup, q_hlo, q_hhi, q_hsh, thr0, q_ub, q_wt, q_wn, q_rup, f_shift, f_seg, f_woff,
-        f_tab, f_max, ch_f, ch_c, ch_t, ch_s, citems, ditems, scan, phrase, bphrase, items, q_pterm, q_ppos, q_clause,
+        f_tab, f_max, ch_f, ch_c, ch_t, ch_s, citems, ditems, scan, phrase, bphrase, group, items, q_pterm, q_ppos, q_clause,
         q_probe, q_tier);
     nf = 0;
   }
@@ -195,8 +198,151 @@ int plan_bool_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, ui
   return FG_OK;
 }
 
+// Query i of the batch when it holds a group clause and fg_group_clauses is on
+// (the clause table was checked by plan_phrase; no phrase clause beside it): no
+// facet clauses, else FG_EUNSUPPORTED.  A member the snapshot lacks is absent: an
+// any-of group goes on without it (with none left the group is absent), an all-of
+// group is absent as a whole.  An absent Should or MustNot clause is dropped, an
+// absent Must empties the slot; one Should and no Must is that clause as a Must.
+// A clause's cost: a term's df_text + df_name, an any-of group's the sum of its
+// members' costs, an all-of group's the smallest.  The slot's clause table
+// (fg_internal.h cl_pack | kClAny / kClAll) is in the order of the score sum, as
+// plan_bool_phrase's; the per-member rows q_terms / q_wt / q_wn / q_ub / q_rup
+// hold the clauses' members in that order, an all-of group's by (cost, position).
+// Work items (k_group), each with its pass (clause, member) in the count word:
+//  * a Must that is a term or an all-of group exists: groups of the chunks of
+//    the shortest list among those clauses' members;
+//  * every Must is an any-of group: a pass per member of the first (cheapest);
+//  * no Must: a pass per Should term, per Should all-of group (its shortest
+//    member) and per member of every Should any-of group.
+int plan_group(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t nq_size, uint32_t n_segs,
+               PlanTables& h) {
+  const uint32_t b = q->q_off[i], e = q->q_off[i + 1];
+  if (q->f_off && q->f_off[i + 1] > q->f_off[i]) return fail(FG_EUNSUPPORTED, "query %u: group with facet filters", i);
+  auto len = [&](uint32_t t) { return (uint64_t)(ix->off[t + 1] - ix->off[t]); };
+  struct Mem { uint32_t t; uint64_t cost; };
+  struct Cl { uint32_t at, n, oc, kind; uint64_t cost; };
+  Cl cl[fg::kMaxTerms];
+  Mem mem[fg::kMaxTerms];  // the kept members, a clause's at [at, at + n) in written order
+  uint32_t ncl = 0, nmem = 0, nm = 0, ns = 0;
+  bool must_missing = false;
+  for (uint32_t j = b; j < e;) {
+    const uint32_t raw = q->phrase_len[j], flags = raw & (FG_CLAUSE_ANY | FG_CLAUSE_ALL);
+    const uint32_t n = raw & ~(FG_CLAUSE_ANY | FG_CLAUSE_ALL);
+    const uint32_t oc = q->occur ? q->occur[j] : (q->mode == FG_MODE_OR ? FG_OCCUR_SHOULD : FG_OCCUR_MUST);
+    if (oc > FG_OCCUR_MUST_NOT) return fail(FG_EINVAL, "query %u: bad occur %u", i, oc);
+    Cl c{nmem, 0, oc, flags == FG_CLAUSE_ANY ? fg::kClAny : flags == FG_CLAUSE_ALL ? fg::kClAll : 0u, 0};
+    bool absent = false;
+    for (uint32_t x = 0; x < n; ++x) {
+      const uint32_t t = fgh::local_term(ix, q->terms[j + x]);
+      if (!(t < ix->n_terms && ix->off[t + 1] > ix->off[t])) {
+        absent |= c.kind != fg::kClAny;
+        continue;
+      }
+      mem[nmem + c.n++] = Mem{t, (uint64_t)ix->df_text[t] + ix->df_name[t]};
+    }
+    j += n;
+    if (absent || c.n == 0) {
+      must_missing |= oc == FG_OCCUR_MUST;
+      continue;
+    }
+    Mem* m0 = mem + c.at;
+    if (c.kind == fg::kClAll) {
+      std::stable_sort(m0, m0 + c.n, [](const Mem& x, const Mem& y) { return x.cost < y.cost; });
+      c.cost = m0[0].cost;
+    } else {
+      for (uint32_t x = 0; x < c.n; ++x) c.cost += m0[x].cost;
+    }
+    nmem += c.n;
+    nm += oc == FG_OCCUR_MUST;
+    ns += oc == FG_OCCUR_SHOULD;
+    cl[ncl++] = c;
+  }
+  if (must_missing || nm + ns == 0) return FG_OK;  // a Must matches nothing, or no positive clause: no hits
+  if (nm == 0 && ns == 1)
+    for (uint32_t c = 0; c < ncl; ++c)
+      if (cl[c].oc == FG_OCCUR_SHOULD) { cl[c].oc = FG_OCCUR_MUST; nm = 1; ns = 0; }
+  // the order of the score sum
+  auto rank = [&](const Cl& c) {
+    if (nm) return c.oc == FG_OCCUR_MUST ? 0 : c.oc == FG_OCCUR_MUST_NOT ? 1 : 2;
+    return c.oc == FG_OCCUR_SHOULD ? 0 : 1;
+  };
+  std::stable_sort(cl, cl + ncl, [&](const Cl& x, const Cl& y) {
+    const int rx = rank(x), ry = rank(y);
+    if (rx != ry) return rx < ry;
+    return nm && rx == 0 && x.cost < y.cost;  // (stable: ties and the other kinds by clause position)
+  });
+  const size_t row = (size_t)i * fg::kMaxTerms;
+  uint32_t first[fg::kMaxTerms], o = 0;
+  for (uint32_t c = 0; c < ncl; ++c) {
+    const Cl& x = cl[c];
+    first[c] = o;
+    for (uint32_t u = 0; u < x.n; ++u) {
+      const uint32_t t = mem[x.at + u].t;
+      float rdn, rup;
+      fgh::term_ratio(ix, t, &rdn, &rup);
+      h.q_terms[row + o + u] = t;
+      h.q_wt[row + o + u] = ix->w_text[t];
+      h.q_wn[row + o + u] = ix->w_name[t];
+      h.q_rup[row + o + u] = rup;
+      h.q_ub[row + o + u] = fgh::term_max_scaled(ix, t, rup);
+    }
+    h.q_clause[row + c] = fg::cl_pack(o, x.n, x.oc, false, c) | x.kind;
+    o += x.n;
+  }
+  h.q_m[i] = fg::qm_phrase(ncl, o);
+  // the passes (clause, member)
+  struct Pass { uint32_t c, m; };
+  Pass pass[fg::kMaxTerms];
+  uint32_t np = 0;
+  auto term_of = [&](uint32_t c, uint32_t m) { return h.q_terms[row + first[c] + m]; };
+  auto shortest = [&](uint32_t c) {
+    uint32_t m = 0;
+    for (uint32_t u = 1; u < cl[c].n; ++u)
+      if (len(term_of(c, u)) < len(term_of(c, m))) m = u;
+    return m;
+  };
+  bool driver = false;  // a Must that is a term or an all-of group
+  for (uint32_t c = 0; c < nm; ++c) {
+    if (cl[c].kind == fg::kClAny) continue;
+    const Pass p{c, shortest(c)};
+    if (!driver || len(term_of(p.c, p.m)) < len(term_of(pass[0].c, pass[0].m))) pass[0] = p;
+    driver = true;
+  }
+  if (driver) {
+    np = 1;
+  } else {
+    for (uint32_t c = 0; c < (nm ? 1u : ns); ++c) {
+      if (cl[c].kind == fg::kClAny)
+        for (uint32_t u = 0; u < cl[c].n; ++u) pass[np++] = Pass{c, u};
+      else
+        pass[np++] = Pass{c, shortest(c)};
+    }
+  }
+  const uint32_t cdiv = n_segs <= 1 ? 1u : n_segs;
+  const uint32_t per_q = std::max<uint32_t>(
+      1, std::min<uint32_t>(64, std::max<uint32_t>(fg::kConjGroupsPerQuery, 1024 / std::max(nq_size, 1u))) / cdiv);
+  h.lead[i] = (uint32_t)len(term_of(pass[0].c, pass[0].m));
+  uint32_t total = 0;
+  for (uint32_t x = 0; x < np; ++x) {
+    const uint32_t nch = (uint32_t)((len(term_of(pass[x].c, pass[x].m)) + fg::kChunk - 1) / fg::kChunk);
+    if (h.group.size() + nch > 0x7FFFFFFFull)
+      return fail(FG_EUNSUPPORTED, "batch too large (%zu work items)", h.group.size());
+    const uint32_t G = std::min<uint32_t>(fg::kPhraseMaxGroup, std::max<uint32_t>(1, (nch + per_q - 1) / per_q));
+    const uint32_t ng = (nch + G - 1) / G;
+    for (uint32_t g = 0; g < ng; ++g)
+      h.group.push_back(WItem{(g + 0.5) / ng, i, g * G,
+                              std::min(G, nch - g * G) | (pass[x].c << fg::kGrpClauseShift) |
+                                  (pass[x].m << fg::kGrpMemberShift)});
+    total += ng;
+  }
+  h.ngroup[i] = total;
+  return FG_OK;
+}
+
 // Query i of the batch when it holds a phrase clause (fg_query_batch::phrase_len
-// >= 2; *phrase = 0 otherwise, after checking the clause table): the device
+// >= 2; *phrase = 0 otherwise, after checking the clause table; a group clause,
+// fg_group_clauses, goes to plan_group): the device
 // subset -- the phrase is the query's only clause (`beside`, fg_phrase_clauses:
 // other clauses beside it go to plan_bool_phrase), no facet clauses, a snapshot
 // with positions -- or FG_EUNSUPPORTED naming the reason.  The slot's rows:
@@ -207,12 +353,27 @@ int plan_bool_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, ui
 // idfs summed in phrase order from 0.0 (a repeated term each time), times
 // (1 + K1).  Work items (k_phrase): groups of the lead list's chunks, as k_conj's.
 int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t nq_size, uint32_t n_segs,
-                PlanTables& h, int* phrase, bool beside) {
+                PlanTables& h, int* phrase, bool beside, bool groups) {
   *phrase = 0;
   const uint32_t b = q->q_off[i], e = q->q_off[i + 1], m = e - b;
-  uint32_t n_clauses = 0, n_phr = 0;
+  uint32_t n_clauses = 0, n_phr = 0, n_grp = 0;
   for (uint32_t j = b; j < e;) {
-    const uint32_t n = q->phrase_len[j];
+    uint32_t n = q->phrase_len[j];
+    // a group clause (fg_group_clauses; off: the flags make n a bad phrase_len, as before)
+    const uint32_t kind = groups ? n & (FG_CLAUSE_ANY | FG_CLAUSE_ALL) : 0u;
+    if (kind) {
+      n &= ~(FG_CLAUSE_ANY | FG_CLAUSE_ALL);
+      if (kind == (FG_CLAUSE_ANY | FG_CLAUSE_ALL) || n < 2 || n > e - j)
+        return fail(FG_EINVAL, "query %u: bad phrase_len at term %u", i, j - b);
+      for (uint32_t x = 0; x < n; ++x) {
+        if (x && q->phrase_len[j + x] != 0) return fail(FG_EINVAL, "query %u: phrase_len inside a group must be 0", i);
+        if (q->phrase_pos[j + x] != 0) return fail(FG_EINVAL, "query %u: a group member's offset must be 0", i);
+      }
+      ++n_grp;
+      ++n_clauses;
+      j += n;
+      continue;
+    }
     if (n == 0 || n > e - j) return fail(FG_EINVAL, "query %u: bad phrase_len at term %u", i, j - b);
     for (uint32_t x = 1; x < n; ++x)
       if (q->phrase_len[j + x] != 0) return fail(FG_EINVAL, "query %u: phrase_len inside a phrase must be 0", i);
@@ -225,6 +386,11 @@ int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_
     }
     ++n_clauses;
     j += n;
+  }
+  if (n_grp) {
+    *phrase = 1;
+    if (n_phr) return fail(FG_EUNSUPPORTED, "query %u: group clause beside a phrase clause", i);
+    return plan_group(ix, q, i, nq_size, n_segs, h);
   }
   if (!n_phr) return FG_OK;
   *phrase = 1;
@@ -284,9 +450,9 @@ int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_
 // that batch: plan_pieces plans a snapshot's queries in pieces)
 // qtime: the plan forms its scores at query time (some snapshot's statistics
 // changed since its build: DevPlan::feat), so the descriptors point at payloads
-// beside: fg_phrase_clauses as the plan's creation read it
+// beside, groups: fg_phrase_clauses, fg_group_clauses as the plan's creation read them
 int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t n_segs, PlanTables& h,
-              uint32_t nq_size, bool qtime, bool beside) {
+              uint32_t nq_size, bool qtime, bool beside, bool groups) {
   if (!ix || !q || (q->n_queries && !q->q_off)) return fail(FG_EINVAL, "bad arguments");
   if (q->n_queries && q->q_off[q->n_queries] > q->q_off[0] && !q->terms) return fail(FG_EINVAL, "q_off without terms");
   if (q->f_off && q->n_queries && q->f_off[q->n_queries] > q->f_off[0] && !q->f_terms)
@@ -312,7 +478,7 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
     if (!q->phrase_pos) return fail(FG_EINVAL, "phrase_len without phrase_pos");
     h.q_pterm.assign(nqt, 0);
     h.q_ppos.assign(nqt, 0);
-    if (beside) h.q_clause.assign(nqt, 0);
+    if (beside || groups) h.q_clause.assign(nqt, 0);
   }
 
   // ---- facet filters: one mask per distinct clause list (fg_internal.h DevFilters)
@@ -432,7 +598,7 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
     if (m > fg::kMaxTerms) return fail(FG_EUNSUPPORTED, "query %u has %u terms (> %u)", i, m, fg::kMaxTerms);
     if (q->phrase_len) {
       int phrase = 0;
-      if (int rc = plan_phrase(ix, q, i, nq_size, n_segs, h, &phrase, beside)) return rc;
+      if (int rc = plan_phrase(ix, q, i, nq_size, n_segs, h, &phrase, beside, groups)) return rc;
       if (phrase) continue;
     }
     if (q_nomatch[i]) continue;  // the facet clauses match nothing: no hits
@@ -649,7 +815,8 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
     if (!fg::probe_addr_ok(ixs[s]->d)) return fail(FG_EUNSUPPORTED, "snapshot %u: device arrays above 2^47", s);
   }
   const bool beside = phrase_clauses_on.load(std::memory_order_relaxed) != 0;  // (read once per plan)
-  if (S == 1) return plan_host(ixs[0], q, k, S, hs[0], nq1, qt, beside);  // (used in place: nothing to join)
+  const bool groups = group_clauses_on.load(std::memory_order_relaxed) != 0;
+  if (S == 1) return plan_host(ixs[0], q, k, S, hs[0], nq1, qt, beside, groups);  // (used in place: nothing to join)
   J.clear();
   const size_t nq = (size_t)S * nq1, nqt = nq * fg::kMaxTerms;
   for (auto* v : {&J.q_m, &J.lead, &J.ngroup, &J.q_tier}) v->resize(nq);
@@ -659,7 +826,7 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
   J.q_probe.resize(nqt);
   if (q->phrase_len)
     for (auto* v : {&J.q_pterm, &J.q_ppos}) v->resize(nqt);
-  if (q->phrase_len && beside) J.q_clause.resize(nqt);
+  if (q->phrase_len && (beside || groups)) J.q_clause.resize(nqt);
   auto put_slot = [&](uint32_t p) {  // piece p's per-query tables into its slots
     const PlanTables& h = hs[p];
     const size_t v0 = pc.slot(p), t0 = v0 * fg::kMaxTerms;
@@ -681,14 +848,14 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
       qp.n_queries = b - a;
       qp.q_off = q->q_off + a;
       if (q->f_off) qp.f_off = q->f_off + a;
-      if ((rcs[p] = plan_host(ixs[p / pc.P], &qp, k, S, hs[p], nq1, qt, beside))) errs[p] = fg_last_error();
+      if ((rcs[p] = plan_host(ixs[p / pc.P], &qp, k, S, hs[p], nq1, qt, beside, groups))) errs[p] = fg_last_error();
       else put_slot(p);
     });
     for (uint32_t p = 0; p < n; ++p)
       if (rcs[p]) return fail(rcs[p], "snapshot %u: %s", p / pc.P, errs[p].c_str());
   } else {
     for (uint32_t s = 0; s < S; ++s) {
-      if (int rc = plan_host(ixs[s], q, k, S, hs[s], nq1, qt, beside)) {
+      if (int rc = plan_host(ixs[s], q, k, S, hs[s], nq1, qt, beside, groups)) {
         const std::string e = fg_last_error();
         return fail(rc, "snapshot %u: %s", s, e.c_str());
       }
@@ -723,6 +890,7 @@ PlanTables& join_pieces(const Pieces& pc, std::vector<PlanTables>& hs, PlanTable
     for (WItem x : h.scan) { x.q += vb; J.scan.push_back(x); }
     for (WItem x : h.phrase) { x.q += vb; J.phrase.push_back(x); }
     for (WItem x : h.bphrase) { x.q += vb; J.bphrase.push_back(x); }
+    for (WItem x : h.group) { x.q += vb; J.group.push_back(x); }
     J.nf += h.nf;
   }
   // one bin geometry per batch query over the snapshots where it has work
@@ -838,9 +1006,9 @@ void sort_sweep(std::vector<WItem>& items, bool conj, const PlanTables& t, uint3
 struct WorkList {
   std::vector<uint32_t> work_q, work_c, work_n;
   std::vector<uint64_t> cand_off;
-  uint64_t n_single = 0, n_conj = 0, n_main = 0, n_scan = 0, n_phrase = 0, n_bphrase = 0;
+  uint64_t n_single = 0, n_conj = 0, n_main = 0, n_scan = 0, n_phrase = 0, n_bphrase = 0, n_group = 0;
   uint32_t xcd_first[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // DevPlan::xcd_first
-  uint64_t count() const { return n_main + n_scan + n_phrase + n_bphrase; }
+  uint64_t count() const { return n_main + n_scan + n_phrase + n_bphrase + n_group; }
 };
 
 // k_conj's multi-list items (sorted) cut into the 8 XCDs' stretches by expected
@@ -875,13 +1043,13 @@ void xcd_stretches(const PlanTables& t, WorkList& w) {
 int order_items(PlanTables& t, uint32_t nq, uint32_t k, WorkList& w) {
   if (t.f_woff[t.nf] * 4 > (8ull << 30)) return fail(FG_EUNSUPPORTED, "facet masks of this batch exceed 8 GiB");
   if (t.ch_f.size() > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "facet postings of this batch too large");
-  if (t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() > 0x7FFFFFFFull)
+  if (t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() > 0x7FFFFFFFull)
     return fail(FG_EUNSUPPORTED, "batch too large (%zu work items)",
-                t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size());
+                t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size());
   sort_sweep(t.citems, true, t, nq);
   sort_sweep(t.ditems, false, t, nq);
   auto& items = t.items;
-  items.reserve(t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size());
+  items.reserve(t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size());
   items.insert(items.end(), t.citems.begin(), t.citems.end());
   w.n_conj = t.citems.size();
   items.insert(items.end(), t.ditems.begin(), t.ditems.end());
@@ -897,11 +1065,15 @@ int order_items(PlanTables& t, uint32_t nq, uint32_t k, WorkList& w) {
   // k_bphrase: the same sweep (a union's passes side by side)
   std::stable_sort(t.bphrase.begin(), t.bphrase.end(), [](const WItem& a, const WItem& b) { return a.key < b.key; });
   w.n_bphrase = t.bphrase.size();
-  const uint64_t chunks = w.count();  // work items (k_conj / k_disj, then k_scan, k_phrase, k_bphrase)
+  // k_group: the same sweep
+  std::stable_sort(t.group.begin(), t.group.end(), [](const WItem& a, const WItem& b) { return a.key < b.key; });
+  w.n_group = t.group.size();
+  const uint64_t chunks = w.count();  // work items (k_conj / k_disj, then k_scan, k_phrase, k_bphrase, k_group)
   if (chunks > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "batch too large (%llu work items)", (unsigned long long)chunks);
   items.insert(items.end(), t.scan.begin(), t.scan.end());
   items.insert(items.end(), t.phrase.begin(), t.phrase.end());
   items.insert(items.end(), t.bphrase.begin(), t.bphrase.end());
+  items.insert(items.end(), t.group.begin(), t.group.end());
   w.work_q.resize(chunks);
   w.work_c.resize(chunks);
   w.work_n.resize(chunks);
@@ -1096,6 +1268,7 @@ void fill_view(fg_plan* p, fg_index* const* ixs, PlanTables& t, const WorkList& 
   p->d.n_scan = (uint32_t)w.n_scan;
   p->d.n_phrase = (uint32_t)w.n_phrase;
   p->d.n_bphrase = (uint32_t)w.n_bphrase;
+  p->d.n_group = (uint32_t)w.n_group;
   p->d.n_single = (uint32_t)w.n_single;
   std::copy(w.xcd_first, w.xcd_first + 9, p->d.xcd_first);
   p->d.k = p->k;
@@ -1185,6 +1358,11 @@ int fg_plan_create_multi(fg_index* const* ixs, uint32_t n_segs, const fg_query_b
 int fg_phrase_clauses(int on) {
   if (on < 0) return phrase_clauses_on.load(std::memory_order_relaxed);
   return phrase_clauses_on.exchange(on != 0 ? 1 : 0, std::memory_order_relaxed);
+}
+
+int fg_group_clauses(int on) {
+  if (on < 0) return group_clauses_on.load(std::memory_order_relaxed);
+  return group_clauses_on.exchange(on != 0 ? 1 : 0, std::memory_order_relaxed);
 }
 
 int fg_plan_tiered_slots(const fg_plan* p, uint32_t* out) {

@@ -226,6 +226,28 @@ def parse_query_clauses(query: str):
     return clauses
 
 
+def parse_query_clause_lines(query: str):
+    """fg_parse_query_clauses' lines as they are: "<occur>:term@pos ..." for a term or a phrase,
+    "<occur>:(a | b)" for an any-of group and "<occur>:(a & b)" for an all-of one
+    (native.group_clauses)."""
+    return _string_call(_lib.fg_parse_query_clauses, query.encode()).split("\n")
+
+
+def parse_query_groups(query: str):
+    """[(occur, kind, [term, ...])] with kind "term", "phrase", "any" or "all": the query's
+    clauses with group clauses (native.group_clauses) told apart."""
+    out = []
+    for line in parse_query_clause_lines(query):
+        oc, body = int(line[0]), line[2:]
+        if body.startswith("("):
+            kind = "any" if " | " in body else "all"
+            out.append((oc, kind, body[1:-1].split(" | " if kind == "any" else " & ")))
+        else:
+            toks = [x.rsplit("@", 1)[0] for x in body.split(" ")]
+            out.append((oc, "term" if len(toks) == 1 else "phrase", toks))
+    return out
+
+
 @dataclass
 class ObjectRecord:
     """src/object.rs:8-27: id, text, metadata (JSON object), namespace, explicit

@@ -406,6 +406,28 @@ typedef struct fg_query_batch {
  * such a query still takes no facet clauses and needs snapshots with positions. */
 int fg_phrase_clauses(int on);
 
+/* Group clauses (one level of grouping: a nested BooleanQuery whose members are
+ * plain terms) run on the device (k_group) when on != 0.  The
+ * contract of fg_phrase_clauses: process-wide, off by default, read when a plan
+ * is created; on: 1 / 0 sets it, < 0 only asks; returns the previous setting.
+ * A group is written in phrase_len, in the entry at the clause's first term:
+ * FG_CLAUSE_ANY (the members are all Should: `(a b)`) or FG_CLAUSE_ALL (all
+ * Must: `(a AND b)`) OR-ed onto the member count n, then n-1 entries of 0;
+ * 2 <= n <= the terms the query has left; phrase_pos is 0 for every member; the
+ * clause's occur is its first term's.  An any-of group matches a doc that holds
+ * some member (score: the present members' from 0.0 in written order), an all-of
+ * group one that holds every member (members in (cost, position) order,
+ * (s0 + s1) + (0.0 + s2 + ...)); the query then joins the group as one clause.
+ * Its cost among the Musts: any-of the sum of its members' costs, all-of the
+ * smallest.  A member the snapshot lacks is absent: the any-of group goes on
+ * without it, the all-of group is absent as a whole.  Off: such a phrase_len
+ * value is answered as before (FG_EINVAL "bad phrase_len").  On, outside the
+ * subset (FG_EUNSUPPORTED): "group clause beside a phrase clause", "group with
+ * facet filters", a group in fg_count_batch or fg_model_batch. */
+#define FG_CLAUSE_ANY 0x80000000u
+#define FG_CLAUSE_ALL 0x40000000u
+int fg_group_clauses(int on);
+
 /* Plan a batch: host-side query planning (tantivy Weight creation: terms
  * ordered by cost, query/intersection.rs) and upload of the plan to HBM.
  * Returns FG_EUNSUPPORTED for queries outside the device subset

@@ -35,7 +35,15 @@
  * refuse them).  With fg_phrase_clauses(1) (fugu.h; process-wide, off by
  * default) a phrase may also stand beside other clauses (`e-mail server`,
  * `+e-mail -spam`, `"new york" pizza`: k_bphrase); fg_db_search* then run such
- * queries as they are.  Queries outside the device subset (a phrase beside other
+ * queries as they are.  With fg_group_clauses(1) (fugu.h; process-wide, off by
+ * default) one level of grouping over plain single-token words is in the subset
+ * too (k_group): a parenthesised group where a word may stand -- `(a b)` /
+ * `(a OR b)` any-of, `(a AND b)` / `(+a +b)` all-of; bare, behind `+` / `-`, or
+ * an operand of the uniform AND / OR forms -- and mixed infix `a AND b OR c`,
+ * where AND binds tighter.  fg_parse_query_clauses prints a group as
+ * "<occur>:(a | b)" or "<occur>:(a & b)"; fg_parse_query, fg_parse_query_occur
+ * and the count entry points refuse one.  Queries outside the device subset
+ * (grouping while that switch is off or deeper than one level, a phrase beside other
  * clauses while that switch is off, a phrase with filters, slop / prefix
  * suffixes on a quoted literal, field:,
  * boosts, a text query with filters that parse to no facet term) return

@@ -42,6 +42,8 @@ pub const FG_MODE_OR: c_int = 1;
 pub const FG_OCCUR_MUST: u8 = 0;      // tantivy Occur, per term of a query
 pub const FG_OCCUR_SHOULD: u8 = 1;
 pub const FG_OCCUR_MUST_NOT: u8 = 2;
+pub const FG_CLAUSE_ANY: u32 = 0x8000_0000;  // phrase_len flags of a group clause (fg_group_clauses)
+pub const FG_CLAUSE_ALL: u32 = 0x4000_0000;
 pub const FG_FIELD_TEXT: c_int = 0;
 pub const FG_FIELD_NAME: c_int = 1;
 pub const FG_FIELD_FACET: c_int = 2;
@@ -254,6 +256,7 @@ extern "C" {
 
     // ---- query batches: the searcher.search(.., TopDocs::with_limit(k)) replacement
     pub fn fg_phrase_clauses(on: c_int) -> c_int;
+    pub fn fg_group_clauses(on: c_int) -> c_int;
     pub fn fg_plan_create(ix: *mut fg_index, q: *const fg_query_batch, k: u32, out: *mut *mut fg_plan) -> c_int;
     pub fn fg_plan_create_multi(ixs: *const *mut fg_index, n_segs: u32, q: *const fg_query_batch, k: u32,
                                 out: *mut *mut fg_plan) -> c_int;
