@@ -2254,7 +2254,12 @@ __global__ __launch_bounds__(kThreads) void k_scan(DevIndex ix0, DevPlan pl) {
 //      peers keep their contract; a key below the published k-th is dropped);
 //  (d) pruning: in (a) a survivor whose score bound -- field_score at the lead
 //      posting's own tf, which no phrase count exceeds -- is below the threshold
-//      read at the chunk's start is not queued.
+//      read at the chunk's start is not queued;
+//  (e) a slot with a facet filter (fg_filter_clauses; workgroup-
+//      uniform, as k_scan's): (a) drops a doc whose clause bits are 0, the bound of
+//      (d) and the score of (c) are of the whole score, + f_tab[bits] after the
+//      text-then-name sum (correctly rounded f32 addition rises with either
+//      argument, so the bound stays exact).
 struct PhraseShared {
   ScanShared s;
   uint64_t queue[kChunk];      // survivors: (lead posting's tfn | tfn_name << 16) << 32 | doc
@@ -2305,6 +2310,16 @@ __global__ __launch_bounds__(kThreads) void k_phrase(DevIndex ix0, DevPlan pl) {
   const uint64_t base = ix.off[lead];
   const uint32_t df = pl.q_lead_df[q];
   const float wt = pl.q_wt[row], wn = pl.q_wn[row];
+  // the slot's facet filter (fg_filter_clauses; uniform, as k_scan's): no filter, fmask == nullptr
+  const uint32_t fslot = pl.f.q_filter[q];
+  const uint32_t* fmask = nullptr;
+  uint32_t fshift = 0;
+  const float* ftab = nullptr;
+  if (fslot != kInvalid) {
+    fmask = pl.f.fmask + pl.f.f_woff[fslot];
+    fshift = pl.f.f_shift[fslot];
+    ftab = pl.f.f_tab + (size_t)fslot * 256;
+  }
   if (tid < np) {
     sh.pterm[tid] = pl.q_pterm[row + tid];
     sh.ppos[tid] = pl.q_ppos[row + tid];
@@ -2338,6 +2353,12 @@ __global__ __launch_bounds__(kThreads) void k_phrase(DevIndex ix0, DevPlan pl) {
       }
       for (uint32_t u = 1; u < nd; ++u)
         if (keep) keep = term_has_doc(ix, sh.tmeta[u], sh.toff[u], sh.tdir[u], d);
+      float fs = 0.0f;  // the facet union's score of the doc's matching clauses
+      if (keep && fmask) {
+        const uint32_t fb = filter_bits(fmask, fshift, d);
+        keep = fb != 0;
+        fs = ftab[fb];
+      }
       uint32_t v = 0;
       if (keep) {
         v = ix.tfn[base + i];
@@ -2349,7 +2370,8 @@ __global__ __launch_bounds__(kThreads) void k_phrase(DevIndex ix0, DevPlan pl) {
         float ub = 0.0f;
         if (tt) ub += tt == kTfEsc ? wt : field_score(tt, (v >> 8) & 0xFFu, wt, ix.cache);
         if (tn) ub += tn == kTfEsc ? wn : field_score(tn, v >> 24, wn, ix.cache + 256);
-        keep = make_key(ub, d) >= thr_a;
+        // (with a filter the bound is of the whole score, ub + f_tab[bits], joined as (c) joins them)
+        keep = make_key(fmask ? ub + fs : ub, d) >= thr_a;
       }
       wave_append(keep, ((uint64_t)v << 32) | d, sh.queue, &sh.n_q, kChunk);
     }
@@ -2370,6 +2392,7 @@ __global__ __launch_bounds__(kThreads) void k_phrase(DevIndex ix0, DevPlan pl) {
         float sc = 0.0f;
         if (ct) sc += field_score(ct, (v >> 8) & 0xFFu, wt, ix.cache);
         if (cn) sc += field_score(cn, v >> 24, wn, ix.cache + 256);
+        if (fmask) sc = sc + ftab[filter_bits(fmask, fshift, d)];  // (the queue entry is full: the bits are read again)
         const uint64_t key = make_key(sc, d);
         wave_append(lane == 0 && (ct | cn) != 0 && key >= thr, key, sh.s.buf, &sh.s.n_buf, kBufD);
       }
@@ -2408,6 +2431,9 @@ __global__ __launch_bounds__(kThreads) void k_phrase(DevIndex ix0, DevPlan pl) {
 //  (c) keys go through k_scan's local top-k buffer, threshold word and flush, as
 //      k_phrase's.
 // No score bound prunes in (a): every survivor is verified.
+// A slot with a facet filter (fg_filter_clauses): (a) drops a doc
+// whose clause bits are 0 -- from every pass alike, so a hit still leaves exactly
+// one pass -- and (b) adds f_tab[bits] after the clauses are joined.
 struct BPhraseShared {
   ScanShared s;
   uint64_t queue[kChunk];      // survivors (doc ids)
@@ -2461,6 +2487,16 @@ __global__ __launch_bounds__(kThreads) void k_bphrase(DevIndex ix0, DevPlan pl) 
   if (ncl == 0 || nt == 0) return;  // (never planned; uniform)
   const uint32_t pass = min(pl.work_n[w] >> kBpPassShift, ncl - 1);
   const size_t row = (size_t)q * kMaxTerms;
+  // the slot's facet filter (fg_filter_clauses; uniform, as k_scan's): no filter, fmask == nullptr
+  const uint32_t fslot = pl.f.q_filter[q];
+  const uint32_t* fmask = nullptr;
+  uint32_t fshift = 0;
+  const float* ftab = nullptr;
+  if (fslot != kInvalid) {
+    fmask = pl.f.fmask + pl.f.f_woff[fslot];
+    fshift = pl.f.f_shift[fslot];
+    ftab = pl.f.f_tab + (size_t)fslot * 256;
+  }
   if (tid < nt) {
     const uint32_t t = pl.q_terms[row + tid];
     sh.lterm[tid] = t;
@@ -2510,6 +2546,7 @@ __global__ __launch_bounds__(kThreads) void k_bphrase(DevIndex ix0, DevPlan pl) 
         const uint32_t a = sh.act[u];
         if (keep && a && u != li) keep = term_has_doc(ix, sh.tmeta[u], sh.toff[u], sh.tdir[u], d) == (a == 1u);
       }
+      if (keep && fmask) keep = filter_bits(fmask, fshift, d) != 0;  // outside the filter: never verified
       wave_append(keep, (uint64_t)d, sh.queue, &sh.n_q, kChunk);
     }
     __syncthreads();
@@ -2575,6 +2612,7 @@ __global__ __launch_bounds__(kThreads) void k_bphrase(DevIndex ix0, DevPlan pl) 
           sc = 0.0f + req;
           if (any) sc = sc + opt;
         }
+        if (fmask) sc = sc + ftab[filter_bits(fmask, fshift, d)];
         const uint64_t key = make_key(sc, d);
         wave_append(lane == 0 && !drop && key >= thr, key, sh.s.buf, &sh.s.n_buf, kBufD);
       }
@@ -2619,6 +2657,9 @@ __global__ __launch_bounds__(kThreads) void k_bphrase(DevIndex ix0, DevPlan pl) 
 // out -- is below the item's threshold: every score is >= 0, f32 addition is
 // monotone in both arguments, so the bound is >= the score of every doc of the
 // chunk that this pass can emit, and doc 0 gives the largest key of a score.
+// A slot with a facet filter (fg_filter_clauses): a lane drops a doc
+// whose clause bits are 0 before the member look-ups, adds f_tab[bits] after the
+// join, and the chunk bound is the text bound + f_max, the filter's largest entry.
 struct GroupShared {
   ScanShared s;
   float cache[512];            // the tf caches, text then name
@@ -2710,6 +2751,18 @@ __global__ __launch_bounds__(kThreads, 4) void k_group(DevIndex ix0, DevPlan pl)
   if (ncl == 0 || nt == 0) return;  // (never planned; uniform)
   const uint32_t pc = min((wn >> kGrpClauseShift) & 15u, ncl - 1);
   const size_t row = (size_t)q * kMaxTerms;
+  // the slot's facet filter (fg_filter_clauses; uniform, as k_scan's): no filter, fmask == nullptr
+  const uint32_t fslot = pl.f.q_filter[q];
+  const uint32_t* fmask = nullptr;
+  uint32_t fshift = 0;
+  const float* ftab = nullptr;
+  float fmax = 0.0f;  // the largest facet score: added to every chunk's bound
+  if (fslot != kInvalid) {
+    fmask = pl.f.fmask + pl.f.f_woff[fslot];
+    fshift = pl.f.f_shift[fslot];
+    ftab = pl.f.f_tab + (size_t)fslot * 256;
+    fmax = pl.f.f_max[fslot];
+  }
   if (tid < nt) {
     const uint32_t t = pl.q_terms[row + tid];
     sh.tmeta[tid] = ix.tmeta[t];
@@ -2739,7 +2792,8 @@ __global__ __launch_bounds__(kThreads, 4) void k_group(DevIndex ix0, DevPlan pl)
     const uint32_t i0 = (chunk0 + c) * kChunk;
     if (i0 >= df) break;
     // the chunk's bound against the threshold (uniform: sh.s.thr is read after a barrier)
-    const float bound = group_bound(sh, ncl, nt, must, pc, pm, fminf(cmax[chunk0 + c] * rup, sh.ub[li]));
+    float bound = group_bound(sh, ncl, nt, must, pc, pm, fminf(cmax[chunk0 + c] * rup, sh.ub[li]));
+    if (fmask) bound = bound + fmax;  // (the whole score's bound: the text sum, then the facet union's largest)
     if (make_key(inflate_bound(bound), 0u) < sh.s.thr) continue;
     for (uint32_t r0 = 0; r0 < kChunk; r0 += kRound) {
       const uint64_t thr = sh.s.thr;
@@ -2750,6 +2804,12 @@ __global__ __launch_bounds__(kThreads, 4) void k_group(DevIndex ix0, DevPlan pl)
         if (keep) {
           d = ix.doc[base + i];
           keep = doc_alive(ix, d);
+        }
+        float fs = 0.0f;  // the facet union's score of the doc's matching clauses
+        if (keep && fmask) {
+          const uint32_t fb = filter_bits(fmask, fshift, d);
+          keep = fb != 0;
+          fs = ftab[fb];
         }
         float req = 0.0f, oth = 0.0f, opt = 0.0f;
         uint32_t nm = 0;
@@ -2794,6 +2854,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_group(DevIndex ix0, DevPlan pl)
           sc = 0.0f + req;
           if (any) sc = sc + opt;
         }
+        if (fmask) sc = sc + fs;
         const uint64_t key = make_key(sc, d);
         wave_append(keep && key >= thr, key, sh.s.buf, &sh.s.n_buf, kBufD);
       }

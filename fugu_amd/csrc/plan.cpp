@@ -27,6 +27,8 @@ namespace {
 std::atomic<int> phrase_clauses_on{0};
 // fg_group_clauses: queries with a group clause run on the device (k_group); the same contract
 std::atomic<int> group_clauses_on{0};
+// fg_filter_clauses: phrase, phrase-beside and group queries may carry facet clauses; the same contract
+std::atomic<int> filter_clauses_on{0};
 
 // stable LSD radix sort of `a` by its bits 32..63 (three 11-bit passes)
 void radix_sort_hi32(std::vector<uint64_t>& a, std::vector<uint64_t>& tmp) {
@@ -77,8 +79,10 @@ struct PlanTables {
 };
 
 // Query i of the batch when it holds a phrase clause beside other clauses and
-// fg_phrase_clauses is on (the clause table was checked by plan_phrase): no facet
-// clauses, a snapshot with positions, else FG_EUNSUPPORTED naming the reason.
+// fg_phrase_clauses is on (the clause table was checked by plan_phrase): facet
+// clauses only with `filters` (fg_filter_clauses; the slot's q_filter is set by
+// plan_host, `nomatch`: they match no doc of the snapshot, so no work items), a
+// snapshot with positions, else FG_EUNSUPPORTED naming the reason.
 // A Should or MustNot clause with a term the snapshot lacks is dropped, a Must
 // one empties the slot; one Should and no Must is that clause as a Must.  The
 // slot's clause table (fg_internal.h cl_pack) is in the order of the score sum:
@@ -94,9 +98,10 @@ struct PlanTables {
 // without, one pass per Should clause over that clause's first term's list; the
 // clause led from rides in the item's count word above kBpPassShift.
 int plan_bool_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t nq_size, uint32_t n_segs,
-                     PlanTables& h) {
+                     PlanTables& h, bool filters, bool nomatch) {
   const uint32_t b = q->q_off[i], e = q->q_off[i + 1];
-  if (q->f_off && q->f_off[i + 1] > q->f_off[i]) return fail(FG_EUNSUPPORTED, "query %u: phrase with facet filters", i);
+  if (!filters && q->f_off && q->f_off[i + 1] > q->f_off[i])
+    return fail(FG_EUNSUPPORTED, "query %u: phrase with facet filters", i);
   if (!ix->has_positions) return fail(FG_EUNSUPPORTED, "query %u: snapshot built without positions", i);
   auto len = [&](uint32_t t) { return ix->off[t + 1] - ix->off[t]; };
   struct Cl { uint32_t at, n, oc, pos, anchor; uint64_t cost; float wt, wn; };
@@ -141,7 +146,8 @@ int plan_bool_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, ui
     ns += oc == FG_OCCUR_SHOULD;
     cl[ncl++] = c;
   }
-  if (must_missing || nm + ns == 0) return FG_OK;  // a Must matches nothing, or no positive clause: no hits
+  // a Must matches nothing, no positive clause, or facet clauses that match no doc: no hits
+  if (must_missing || nm + ns == 0 || nomatch) return FG_OK;
   if (nm == 0 && ns == 1)
     for (uint32_t c = 0; c < ncl; ++c)
       if (cl[c].oc == FG_OCCUR_SHOULD) { cl[c].oc = FG_OCCUR_MUST; nm = 1; ns = 0; }
@@ -199,8 +205,9 @@ int plan_bool_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, ui
 }
 
 // Query i of the batch when it holds a group clause and fg_group_clauses is on
-// (the clause table was checked by plan_phrase; no phrase clause beside it): no
-// facet clauses, else FG_EUNSUPPORTED.  A member the snapshot lacks is absent: an
+// (the clause table was checked by plan_phrase; no phrase clause beside it): facet
+// clauses only with `filters` (fg_filter_clauses; `nomatch` as plan_bool_phrase's),
+// else FG_EUNSUPPORTED.  A member the snapshot lacks is absent: an
 // any-of group goes on without it (with none left the group is absent), an all-of
 // group is absent as a whole.  An absent Should or MustNot clause is dropped, an
 // absent Must empties the slot; one Should and no Must is that clause as a Must.
@@ -216,9 +223,10 @@ int plan_bool_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, ui
 //  * no Must: a pass per Should term, per Should all-of group (its shortest
 //    member) and per member of every Should any-of group.
 int plan_group(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t nq_size, uint32_t n_segs,
-               PlanTables& h) {
+               PlanTables& h, bool filters, bool nomatch) {
   const uint32_t b = q->q_off[i], e = q->q_off[i + 1];
-  if (q->f_off && q->f_off[i + 1] > q->f_off[i]) return fail(FG_EUNSUPPORTED, "query %u: group with facet filters", i);
+  if (!filters && q->f_off && q->f_off[i + 1] > q->f_off[i])
+    return fail(FG_EUNSUPPORTED, "query %u: group with facet filters", i);
   auto len = [&](uint32_t t) { return (uint64_t)(ix->off[t + 1] - ix->off[t]); };
   struct Mem { uint32_t t; uint64_t cost; };
   struct Cl { uint32_t at, n, oc, kind; uint64_t cost; };
@@ -258,7 +266,8 @@ int plan_group(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t
     ns += oc == FG_OCCUR_SHOULD;
     cl[ncl++] = c;
   }
-  if (must_missing || nm + ns == 0) return FG_OK;  // a Must matches nothing, or no positive clause: no hits
+  // a Must matches nothing, no positive clause, or facet clauses that match no doc: no hits
+  if (must_missing || nm + ns == 0 || nomatch) return FG_OK;
   if (nm == 0 && ns == 1)
     for (uint32_t c = 0; c < ncl; ++c)
       if (cl[c].oc == FG_OCCUR_SHOULD) { cl[c].oc = FG_OCCUR_MUST; nm = 1; ns = 0; }
@@ -344,8 +353,10 @@ int plan_group(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t
 // >= 2; *phrase = 0 otherwise, after checking the clause table; a group clause,
 // fg_group_clauses, goes to plan_group): the device
 // subset -- the phrase is the query's only clause (`beside`, fg_phrase_clauses:
-// other clauses beside it go to plan_bool_phrase), no facet clauses, a snapshot
-// with positions -- or FG_EUNSUPPORTED naming the reason.  The slot's rows:
+// other clauses beside it go to plan_bool_phrase), facet clauses only with
+// `filters` (fg_filter_clauses; `nomatch`: they match no doc of the snapshot, so
+// the slot gets no work items), a snapshot with positions -- or FG_EUNSUPPORTED
+// naming the reason.  The slot's rows:
 // q_terms the phrase's distinct terms (the snapshot's ids), the lead -- the
 // shortest merged list -- first; q_pterm / q_ppos the (vocabulary id, offset)
 // list, the anchor (the first occurrence of the term with the fewest postings)
@@ -353,7 +364,7 @@ int plan_group(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t
 // idfs summed in phrase order from 0.0 (a repeated term each time), times
 // (1 + K1).  Work items (k_phrase): groups of the lead list's chunks, as k_conj's.
 int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t nq_size, uint32_t n_segs,
-                PlanTables& h, int* phrase, bool beside, bool groups) {
+                PlanTables& h, int* phrase, bool beside, bool groups, bool filters, bool nomatch) {
   *phrase = 0;
   const uint32_t b = q->q_off[i], e = q->q_off[i + 1], m = e - b;
   uint32_t n_clauses = 0, n_phr = 0, n_grp = 0;
@@ -390,20 +401,21 @@ int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_
   if (n_grp) {
     *phrase = 1;
     if (n_phr) return fail(FG_EUNSUPPORTED, "query %u: group clause beside a phrase clause", i);
-    return plan_group(ix, q, i, nq_size, n_segs, h);
+    return plan_group(ix, q, i, nq_size, n_segs, h, filters, nomatch);
   }
   if (!n_phr) return FG_OK;
   *phrase = 1;
   if (n_clauses > 1) {
     if (!beside) return fail(FG_EUNSUPPORTED, "query %u: phrase clause beside other clauses", i);
-    return plan_bool_phrase(ix, q, i, nq_size, n_segs, h);
+    return plan_bool_phrase(ix, q, i, nq_size, n_segs, h, filters, nomatch);
   }
-  if (q->f_off && q->f_off[i + 1] > q->f_off[i]) return fail(FG_EUNSUPPORTED, "query %u: phrase with facet filters", i);
+  if (!filters && q->f_off && q->f_off[i + 1] > q->f_off[i])
+    return fail(FG_EUNSUPPORTED, "query %u: phrase with facet filters", i);
   if (!ix->has_positions) return fail(FG_EUNSUPPORTED, "query %u: snapshot built without positions", i);
   if (q->phrase_pos[e - 1] >= (1u << 30)) return fail(FG_EINVAL, "query %u: phrase offset too large", i);
   const uint8_t oc = q->occur ? q->occur[b] : (q->mode == FG_MODE_OR ? FG_OCCUR_SHOULD : FG_OCCUR_MUST);
   if (oc > FG_OCCUR_MUST_NOT) return fail(FG_EINVAL, "query %u: bad occur %u", i, (unsigned)oc);
-  if (oc == FG_OCCUR_MUST_NOT) return FG_OK;  // no positive clause: no hits
+  if (oc == FG_OCCUR_MUST_NOT || nomatch) return FG_OK;  // no positive clause, or facet clauses that match no doc: no hits
   // the terms in this snapshot; one it lacks: no hits here
   uint32_t lt[fg::kMaxTerms], dist[fg::kMaxTerms], nd = 0;
   float it = 0.0f, in = 0.0f;
@@ -450,9 +462,9 @@ int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_
 // that batch: plan_pieces plans a snapshot's queries in pieces)
 // qtime: the plan forms its scores at query time (some snapshot's statistics
 // changed since its build: DevPlan::feat), so the descriptors point at payloads
-// beside, groups: fg_phrase_clauses, fg_group_clauses as the plan's creation read them
+// beside, groups, filters: fg_phrase_clauses, fg_group_clauses, fg_filter_clauses as the plan's creation read them
 int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t n_segs, PlanTables& h,
-              uint32_t nq_size, bool qtime, bool beside, bool groups) {
+              uint32_t nq_size, bool qtime, bool beside, bool groups, bool filters) {
   if (!ix || !q || (q->n_queries && !q->q_off)) return fail(FG_EINVAL, "bad arguments");
   if (q->n_queries && q->q_off[q->n_queries] > q->q_off[0] && !q->terms) return fail(FG_EINVAL, "q_off without terms");
   if (q->f_off && q->n_queries && q->f_off[q->n_queries] > q->f_off[0] && !q->f_terms)
@@ -598,7 +610,7 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
     if (m > fg::kMaxTerms) return fail(FG_EUNSUPPORTED, "query %u has %u terms (> %u)", i, m, fg::kMaxTerms);
     if (q->phrase_len) {
       int phrase = 0;
-      if (int rc = plan_phrase(ix, q, i, nq_size, n_segs, h, &phrase, beside, groups)) return rc;
+      if (int rc = plan_phrase(ix, q, i, nq_size, n_segs, h, &phrase, beside, groups, filters, q_nomatch[i] != 0)) return rc;
       if (phrase) continue;
     }
     if (q_nomatch[i]) continue;  // the facet clauses match nothing: no hits
@@ -816,7 +828,8 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
   }
   const bool beside = phrase_clauses_on.load(std::memory_order_relaxed) != 0;  // (read once per plan)
   const bool groups = group_clauses_on.load(std::memory_order_relaxed) != 0;
-  if (S == 1) return plan_host(ixs[0], q, k, S, hs[0], nq1, qt, beside, groups);  // (used in place: nothing to join)
+  const bool filters = filter_clauses_on.load(std::memory_order_relaxed) != 0;
+  if (S == 1) return plan_host(ixs[0], q, k, S, hs[0], nq1, qt, beside, groups, filters);  // (used in place: nothing to join)
   J.clear();
   const size_t nq = (size_t)S * nq1, nqt = nq * fg::kMaxTerms;
   for (auto* v : {&J.q_m, &J.lead, &J.ngroup, &J.q_tier}) v->resize(nq);
@@ -848,14 +861,14 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
       qp.n_queries = b - a;
       qp.q_off = q->q_off + a;
       if (q->f_off) qp.f_off = q->f_off + a;
-      if ((rcs[p] = plan_host(ixs[p / pc.P], &qp, k, S, hs[p], nq1, qt, beside, groups))) errs[p] = fg_last_error();
+      if ((rcs[p] = plan_host(ixs[p / pc.P], &qp, k, S, hs[p], nq1, qt, beside, groups, filters))) errs[p] = fg_last_error();
       else put_slot(p);
     });
     for (uint32_t p = 0; p < n; ++p)
       if (rcs[p]) return fail(rcs[p], "snapshot %u: %s", p / pc.P, errs[p].c_str());
   } else {
     for (uint32_t s = 0; s < S; ++s) {
-      if (int rc = plan_host(ixs[s], q, k, S, hs[s], nq1, qt, beside, groups)) {
+      if (int rc = plan_host(ixs[s], q, k, S, hs[s], nq1, qt, beside, groups, filters)) {
         const std::string e = fg_last_error();
         return fail(rc, "snapshot %u: %s", s, e.c_str());
       }
@@ -1363,6 +1376,11 @@ int fg_phrase_clauses(int on) {
 int fg_group_clauses(int on) {
   if (on < 0) return group_clauses_on.load(std::memory_order_relaxed);
   return group_clauses_on.exchange(on != 0 ? 1 : 0, std::memory_order_relaxed);
+}
+
+int fg_filter_clauses(int on) {
+  if (on < 0) return filter_clauses_on.load(std::memory_order_relaxed);
+  return filter_clauses_on.exchange(on != 0 ? 1 : 0, std::memory_order_relaxed);
 }
 
 int fg_plan_tiered_slots(const fg_plan* p, uint32_t* out) {

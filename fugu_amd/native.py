@@ -65,7 +65,7 @@ EXPORTS = (
     "fg_count_batch", "fg_count_trace", "fg_index_doctab_get", "fg_index_doctab8_get",
     "fg_index_build_positional", "fg_index_positions_get",
     "fg_index_bands_get", "fg_index_band_read", "fg_plan_tiered_slots",
-    "fg_phrase_clauses", "fg_group_clauses",
+    "fg_phrase_clauses", "fg_group_clauses", "fg_filter_clauses",
 )
 BAND_TIERS = 5  # fugu.h FG_BAND_TIERS
 LADDER_KS = (1, 2, 3, 5, 10, 13, 20, 25, 50, 100, 125, 250, 500, 1000)  # FG_LADDER_LEVELS ranks
@@ -190,6 +190,8 @@ if hasattr(_lib, "fg_phrase_clauses"):  # (a new symbol, FG_ABI_VERSION stays: a
     _sig("fg_phrase_clauses", C.c_int, C.c_int)
 if hasattr(_lib, "fg_group_clauses"):  # (likewise)
     _sig("fg_group_clauses", C.c_int, C.c_int)
+if hasattr(_lib, "fg_filter_clauses"):  # (likewise)
+    _sig("fg_filter_clauses", C.c_int, C.c_int)
 _sig("fg_index_df", C.c_uint64, _p, C.c_int, C.c_uint32)
 _sig("fg_index_bm25", C.c_int, _p, C.c_uint32, _f32p, _f32p, _f32p)
 _sig("fg_plan_create", C.c_int, _p, C.POINTER(QueryBatch), C.c_uint32, C.POINTER(_p))
@@ -277,6 +279,16 @@ def group_clauses(on: int = -1) -> int:
     if not hasattr(_lib, "fg_group_clauses"):
         raise Unsupported(FG_EUNSUPPORTED, "this libfugu has no fg_group_clauses")
     return int(_lib.fg_group_clauses(int(on)))
+
+
+def filter_clauses(on: int = -1) -> int:
+    """fg_filter_clauses: phrase queries, queries with a phrase clause beside other clauses
+    (phrase_clauses as well) and queries with a group clause (group_clauses as well) may carry
+    facet clauses (f_off / f_terms) when on; process-wide, off by default, read when a plan is
+    created.  on: 1 / 0 sets it, < 0 only asks.  Returns the previous setting."""
+    if not hasattr(_lib, "fg_filter_clauses"):
+        raise Unsupported(FG_EUNSUPPORTED, "this libfugu has no fg_filter_clauses")
+    return int(_lib.fg_filter_clauses(int(on)))
 
 
 def device_count() -> int:

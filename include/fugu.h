@@ -389,7 +389,8 @@ typedef struct fg_query_batch {
    * built with keep_positions; otherwise FG_EUNSUPPORTED ("phrase clause beside
    * other clauses", "phrase with facet filters", "snapshot built without
    * positions").  With fg_phrase_clauses(1) a phrase clause may also stand
-   * beside other clauses (below).  A batch may mix phrase queries with the other
+   * beside other clauses, and with fg_filter_clauses(1) a phrase query may carry
+   * facet clauses (both below).  A batch may mix phrase queries with the other
    * shapes. */
   const uint32_t* phrase_len;
   const uint32_t* phrase_pos;
@@ -403,7 +404,8 @@ typedef struct fg_query_batch {
  * FG_EUNSUPPORTED "phrase clause beside other clauses", as before.  On: the
  * clauses join as the term clauses of `occur` do (a phrase clause's cost among
  * the Musts: the sum over the two fields of its terms' smallest doc count there);
- * such a query still takes no facet clauses and needs snapshots with positions. */
+ * such a query needs snapshots with positions, and takes facet clauses only
+ * with fg_filter_clauses(1) as well ("phrase with facet filters" otherwise). */
 int fg_phrase_clauses(int on);
 
 /* Group clauses (one level of grouping: a nested BooleanQuery whose members are
@@ -423,10 +425,26 @@ int fg_phrase_clauses(int on);
  * without it, the all-of group is absent as a whole.  Off: such a phrase_len
  * value is answered as before (FG_EINVAL "bad phrase_len").  On, outside the
  * subset (FG_EUNSUPPORTED): "group clause beside a phrase clause", "group with
- * facet filters", a group in fg_count_batch or fg_model_batch. */
+ * facet filters" (unless fg_filter_clauses(1) is set as well), a group in
+ * fg_count_batch or fg_model_batch. */
 #define FG_CLAUSE_ANY 0x80000000u
 #define FG_CLAUSE_ALL 0x40000000u
 int fg_group_clauses(int on);
+
+/* Facet clauses (f_off / f_terms, <= FG_MAX_FACET_CLAUSES) on the queries that
+ * k_phrase, k_bphrase and k_group run when on != 0: a phrase
+ * query, a query with a phrase clause beside other clauses (fg_phrase_clauses
+ * as well), a query with a group clause (fg_group_clauses as well).  The
+ * contract of fg_phrase_clauses: process-wide, off by default, read when a plan
+ * is created; on: 1 / 0 sets it, < 0 only asks; returns the previous setting.
+ * The semantics are the term queries': hits = the text query's hits that some
+ * facet clause matches, score = text score + facet union score (the matching
+ * clauses' scores summed from 0.0 in clause order).  A query whose facet clauses
+ * match no doc of a snapshot has no hits there.  Off: such a query is
+ * FG_EUNSUPPORTED "phrase with facet filters" / "group with facet filters", as
+ * before.  fg_count_batch and fg_model_batch refuse phrase and group clauses
+ * either way. */
+int fg_filter_clauses(int on);
 
 /* Plan a batch: host-side query planning (tantivy Weight creation: terms
  * ordered by cost, query/intersection.rs) and upload of the plan to HBM.

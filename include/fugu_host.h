@@ -44,7 +44,8 @@
  * "<occur>:(a | b)" or "<occur>:(a & b)"; fg_parse_query, fg_parse_query_occur
  * and the count entry points refuse one.  Queries outside the device subset
  * (grouping while that switch is off or deeper than one level, a phrase beside other
- * clauses while that switch is off, a phrase with filters, slop / prefix
+ * clauses while that switch is off, a phrase or a group with filters unless
+ * fg_filter_clauses(1) is set (fugu.h; process-wide, off by default), slop / prefix
  * suffixes on a quoted literal, field:,
  * boosts, a text query with filters that parse to no facet term) return
  * FG_EUNSUPPORTED: the reference host then runs tantivy; this library never
