@@ -801,6 +801,20 @@ __host__ __device__ inline uint32_t slot_query(const DevPlan& pl, uint32_t v) {
 //              count[(q0 + i) * n_count + j] += hits.
 // total / count are the whole batch's (zeroed once per call) and sum over the
 // snapshots of a namespace (disjoint docs).
+// With fg_count_clauses a phrase or group clause of a slot is a
+// ROW: one bitmap cbits[r * words .. + words) per distinct clause of the slice
+// (zeroed per pass).  Two more kernels run, and k_cmatch keeps the slots without rows:
+//   k_crow     after k_cfilter: work items (row, kCountChunk postings of a driver
+//              list).  An any-of group drives every present member; an all-of
+//              group its shortest member, the others probed (term_has_doc); a
+//              phrase its rarest distinct term, the other distinct terms probed,
+//              the survivors queued in LDS and verified one wave each against
+//              fwd, then fwd_name (existence only);
+//   k_cjoin    beside k_cmatch, for the slots that hold a row: k_cmatch's list
+//              drivers (kCountText) and row drivers (kCountRow: (slot, row,
+//              kCountWordChunk words), a lane per word) -- when the Musts are rows
+//              only, and for every Should row.  A candidate is tested in the slot's
+//              probed terms, its Must and MustNot rows and its filter row.
 // (constants of their own, not the k_conj tuning macros: count.cpp is compiled once for every variant build)
 constexpr uint32_t kCountItems = 8;                  // k_cmatch: driver postings per lane
 constexpr uint32_t kCountChunk = kThreads * kCountItems;  // ... per work item (2048)
@@ -809,6 +823,13 @@ constexpr uint32_t kCountFacetItems = kCountFacetChunk / kThreads;  // ... per l
 constexpr uint32_t kCountWordChunk = 2048;           // bitmap words per k_ccount workgroup / k_cmatch fill item
 constexpr uint32_t kCountTile = 64;                  // k_cfacet: slots per LDS accumulation round
 constexpr uint32_t kCountText = 0, kCountFacet = 1, kCountFill = 2;  // DevCount::w_kind
+constexpr uint32_t kCountRow = 3;                                    // DevCount::j_kind: a row driver (k_cjoin)
+constexpr uint32_t kRowAny = 0, kRowAll = 1, kRowPhrase = 2;         // row_pack kinds
+// DevCount::row_m: bits 0-7 the row's probed terms, 8-15 a phrase's terms, 16-17 its kind
+__host__ __device__ inline uint32_t row_pack(uint32_t kind, uint32_t probes, uint32_t n) { return probes | (n << 8) | (kind << 16); }
+__host__ __device__ inline uint32_t row_probes(uint32_t rm) { return rm & 0xFFu; }
+__host__ __device__ inline uint32_t row_phrase_terms(uint32_t rm) { return (rm >> 8) & 0xFFu; }
+__host__ __device__ inline uint32_t row_kind(uint32_t rm) { return rm >> 16; }
 struct DevCount {
   uint32_t nq;                  // slots of the slice
   uint32_t q0;                  // batch query of slot 0
@@ -832,6 +853,22 @@ struct DevCount {
   const uint32_t* cc_j;         // [n_cchunks] k_cfacet item -> index in count_terms
   const uint32_t* cc_term;      // [n_cchunks] facet term
   const uint32_t* cc_start;     // [n_cchunks] first posting within the term's list
+  // ---- clause rows (fg_count_clauses); n_ritems == n_jitems == 0 without one
+  uint32_t n_ritems, n_jitems;
+  uint32_t* cbits;              // [n_rows * words] workspace, zeroed per pass
+  const uint32_t* r_row;        // [n_ritems] k_crow item -> row
+  const uint32_t* r_term;       // [n_ritems] driver term (the snapshot's id)
+  const uint32_t* r_start;      // [n_ritems] first posting within the driver list
+  const uint32_t* row_m;        // [n_rows] row_pack(kind, probed terms, phrase terms)
+  const uint32_t* row_terms;    // [n_rows * kMaxTerms] probed terms (the snapshot's ids): every one must hold the doc
+  const uint32_t* row_pterm;    // [n_rows * kMaxTerms] a phrase's terms as VOCABULARY ids (DevIndex::fwd), anchor first
+  const uint32_t* row_ppos;     // [n_rows * kMaxTerms] ... and their position offsets
+  const uint32_t* j_q;          // [n_jitems] k_cjoin item -> slot
+  const uint32_t* j_kind;       // [n_jitems] kCountText / kCountRow
+  const uint32_t* j_term;       // [n_jitems] driver term, or driver row
+  const uint32_t* j_start;      // [n_jitems] first posting within the driver list; kCountRow: first word
+  const uint32_t* q_rm;         // [nq] tested rows | Must rows among them << 16
+  const uint32_t* q_rows;       // [nq * kMaxTerms] tested rows: [Must rows][MustNot rows]
 };
 
 constexpr uint32_t kDiagPerWg = 16;  // u64 stamps per workgroup in diagnostic builds
@@ -1030,8 +1067,10 @@ hipError_t launch_group(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 // out_shard != nullptr: the merged select of a multi-snapshot plan (one list per batch query)
 hipError_t launch_final(const DevPlan& pl, float* out_score, uint32_t* out_doc, uint32_t* out_n, hipStream_t s,
                         uint32_t* out_shard = nullptr);
-// fg_count_batch's four kernels of one pass, back to back on s (a kernel with no items is skipped);
-// ev: 5 events recorded around them, or nullptr
+// fg_count_batch's kernels of one pass, back to back on s (a kernel with no items is skipped): k_cfilter,
+// k_crow, k_cmatch, k_cjoin, k_ccount, k_cfacet; ev: kCountEvents events recorded around them, or nullptr
+// (ev[2] == ev[1] / ev[4] == ev[3]: one event for both slots, when k_crow / k_cjoin have no items)
+constexpr uint32_t kCountEvents = 7;
 hipError_t launch_count(const DevIndex& ix, const DevCount& c, hipStream_t s, hipEvent_t* ev = nullptr);
 hipError_t launch_rank(const uint32_t* doc, const uint64_t* slot_base, const uint32_t* slot_n, uint32_t n_slots,
                        uint32_t n_words, uint64_t* out, hipStream_t s);

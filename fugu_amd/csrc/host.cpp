@@ -1374,7 +1374,8 @@ std::vector<std::string> filter_list(const char* const* filters, uint32_t n) {
 // segments (src/db/facet.rs): the query's hit total and, for every facet term of
 // `cterms` (facet dictionary ids), the matching docs under it -- ONE
 // fg_count_batch call.  query NULL / blank: AllQuery.  The query is parsed and
-// the filters built as search_hits does; a phrase clause is FG_EUNSUPPORTED.
+// the filters built as search_hits does; a phrase or group clause is
+// FG_EUNSUPPORTED unless fg_count_clauses is on (then mapped as search_hits does).
 int count_query(Namespace& ns, const char* query, const std::vector<std::string>& filters,
                 const std::vector<uint32_t>& cterms, uint64_t* total, std::vector<uint64_t>& counts) {
   *total = 0;
@@ -1382,17 +1383,28 @@ int count_query(Namespace& ns, const char* query, const std::vector<std::string>
   const std::string_view qv = query ? query : "";
   std::vector<std::string> terms;
   std::vector<uint8_t> occur;
+  std::vector<uint32_t> plen, ppos;  // fg_query_batch::phrase_len / phrase_pos
+  bool any_phrase = false;
   const bool empty_text = blank(qv);
   if (!empty_text) {
     std::vector<Clause> cls;
     std::string why;
     int rc = parse_clauses(qv, cls, why);
     if (rc) return hfail(rc, "query outside the device subset: " + why);
+    const bool rows = fg_count_clauses(-1) > 0;  // phrase and group clauses are counted
     for (Clause& c : cls) {
-      if (c.group) return hfail(FG_EUNSUPPORTED, "query outside the device subset: group clause in a count query");
-      if (c.terms.size() > 1) return hfail(FG_EUNSUPPORTED, "query outside the device subset: phrase clause in a count query");
-      terms.push_back(std::move(c.terms[0]));
-      occur.push_back(c.occur);
+      if (!rows) {
+        if (c.group) return hfail(FG_EUNSUPPORTED, "query outside the device subset: group clause in a count query");
+        if (c.terms.size() > 1) return hfail(FG_EUNSUPPORTED, "query outside the device subset: phrase clause in a count query");
+      }
+      any_phrase |= c.terms.size() > 1;
+      const uint32_t flag = c.group == kGroupAny ? FG_CLAUSE_ANY : c.group == kGroupAll ? FG_CLAUSE_ALL : 0u;
+      for (size_t j = 0; j < c.terms.size(); ++j) {  // as search_hits writes them
+        terms.push_back(std::move(c.terms[j]));
+        occur.push_back(c.occur);
+        plen.push_back(j == 0 ? (uint32_t)c.terms.size() | flag : 0u);
+        ppos.push_back(c.pos[j]);
+      }
     }
   }
   std::vector<std::string> clauses;
@@ -1420,6 +1432,10 @@ int count_query(Namespace& ns, const char* query, const std::vector<std::string>
   const uint32_t q_off[2] = {0, (uint32_t)ids.size()};
   const uint32_t f_off[2] = {0, (uint32_t)fids.size()};
   fg_query_batch qb{1, q_off, ids.data(), FG_MODE_AND, fids.empty() ? nullptr : f_off, fids.data(), occur.data()};
+  if (any_phrase) {
+    qb.phrase_len = plen.data();
+    qb.phrase_pos = ppos.data();
+  }
   int rc = fg_count_batch(segs.data(), (uint32_t)segs.size(), &qb, cterms.data(), (uint32_t)cterms.size(), total,
                           cterms.empty() ? nullptr : counts.data());
   if (rc) return hfail(rc, fg_last_error());

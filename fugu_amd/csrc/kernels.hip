@@ -4432,6 +4432,192 @@ __global__ __launch_bounds__(kThreads) void k_cmatch(DevIndex ix, DevCount c) {
   if (cb) atomicOr(&m[cw], cb);
 }
 
+// ---- clause rows (fg_count_clauses)
+// A lane's `live` docs of d[] (ascending) into bitmap `bits`: those of one word in one atomic OR, as k_cmatch's
+__device__ inline void count_or_merged(uint32_t* __restrict__ bits, const uint32_t (&d)[kCountItems], uint32_t live) {
+  uint32_t cw = kInvalid, cb = 0;
+#pragma unroll
+  for (uint32_t r = 0; r < kCountItems; ++r)
+    if ((live >> r) & 1u) {
+      const uint32_t w = d[r] >> 5, b = 1u << (d[r] & 31u);
+      if (w != cw) {
+        if (cb) atomicOr(&bits[cw], cb);
+        cw = w;
+        cb = 0;
+      }
+      cb |= b;
+    }
+  if (cb) atomicOr(&bits[cw], cb);
+}
+
+// A lane's kCountItems consecutive postings of list[st .. st + cnt) (k_cmatch's layout); returns the live mask
+__device__ inline uint32_t count_load_docs(const uint32_t* __restrict__ list, uint32_t st, uint32_t cnt,
+                                           uint32_t (&d)[kCountItems]) {
+  uint32_t live = 0;
+#pragma unroll
+  for (uint32_t r = 0; r < kCountItems; ++r) {
+    const uint32_t p = threadIdx.x * kCountItems + r;
+    d[r] = 0;
+    if (p < cnt) {
+      d[r] = list[st + p];
+      live |= 1u << r;
+    }
+  }
+  return live;
+}
+
+// Does the phrase (pterm / ppos in LDS, anchor first; span = its largest offset)
+// occur in positions [b0, b1) of one field's forward index?  One wave: the lanes
+// stride over the starts, the wave stops at its first hit.  Reads fwd[b0 .. b1)
+// only, and nothing when the field is no longer than the span.
+__device__ inline bool phrase_exists(const uint32_t* __restrict__ fwd, uint64_t b0, uint64_t b1, const uint32_t* pterm,
+                                     const uint32_t* ppos, uint32_t n, uint32_t span) {
+  const uint64_t len = b1 - b0;
+  if (len <= span) return false;
+  const uint64_t starts = len - span;  // starts p with p + span inside the field
+  const uint32_t a_pos = ppos[0], a_term = pterm[0];
+  for (uint64_t p0 = 0; p0 < starts; p0 += 64) {
+    const uint64_t p = p0 + lane_id();
+    bool ok = p < starts && fwd[b0 + p + a_pos] == a_term;
+    for (uint32_t j = 1; j < n && ok; ++j) ok = fwd[b0 + p + ppos[j]] == pterm[j];
+    if (__ballot(ok)) return true;
+  }
+  return false;
+}
+
+// The doc bitmap of every clause row.  A work item is kCountChunk postings of one
+// driver list of the row (k_cmatch's lane layout): the row's probed terms must all
+// hold the doc (none for an any-of group, whose present members all drive).  A
+// group's survivors go out in one atomic OR per bitmap word; a phrase's are queued
+// in LDS (at most the chunk's kCountChunk docs) and verified one wave each
+// against fwd, then fwd_name: existence only, lane 0 sets the bit.
+__global__ __launch_bounds__(kThreads) void k_crow(DevIndex ix, DevCount c) {
+  __shared__ uint32_t queue[kCountChunk];
+  __shared__ uint32_t n_q;
+  __shared__ uint32_t pterm[kMaxTerms], ppos[kMaxTerms];
+  const uint32_t item = blockIdx.x;
+  const uint32_t row = c.r_row[item], t = c.r_term[item], st = c.r_start[item];
+  const uint32_t rm = c.row_m[row], kind = row_kind(rm), np = min(row_probes(rm), kMaxTerms);
+  const uint32_t n = min(row_phrase_terms(rm), kMaxTerms);
+  uint32_t* __restrict__ bits = c.cbits + (size_t)row * c.words;
+  if (kind == kRowPhrase) {
+    if (threadIdx.x < n) {
+      pterm[threadIdx.x] = c.row_pterm[(size_t)row * kMaxTerms + threadIdx.x];
+      ppos[threadIdx.x] = c.row_ppos[(size_t)row * kMaxTerms + threadIdx.x];
+    }
+    if (threadIdx.x == 0) n_q = 0;
+    __syncthreads();
+  }
+  const uint64_t b0 = ix.off[t];
+  const uint32_t len = (uint32_t)(ix.off[t + 1] - b0);
+  const uint32_t cnt = min(len - st, kCountChunk);
+  uint32_t d[kCountItems];
+  uint32_t live = count_load_docs(ix.doc + b0, st, cnt, d);
+  const uint32_t* __restrict__ rt = c.row_terms + (size_t)row * kMaxTerms;
+  for (uint32_t j = 0; j < np; ++j) {
+    const uint32_t u = rt[j];
+    const uint32_t meta = ix.tmeta[u], dir_off = ix.dir_off[u];
+    const uint64_t base = ix.off[u];
+#pragma unroll
+    for (uint32_t r = 0; r < kCountItems; ++r)
+      if ((live >> r) & 1u)
+        if (!term_has_doc(ix, meta, base, dir_off, d[r])) live &= ~(1u << r);
+  }
+  if (kind != kRowPhrase) {
+    count_or_merged(bits, d, live);
+    return;
+  }
+  // the survivors: a lane reserves its places with one LDS atomic (<= cnt <= kCountChunk in all)
+  const uint32_t mine = (uint32_t)__popc(live);
+  uint32_t at = mine ? atomicAdd(&n_q, mine) : 0u;
+#pragma unroll
+  for (uint32_t r = 0; r < kCountItems; ++r)
+    if (((live >> r) & 1u) && at < kCountChunk) queue[at++] = d[r];
+  __syncthreads();
+  uint32_t span = 0;  // the phrase's largest offset
+  for (uint32_t j = 0; j < n; ++j) span = max(span, ppos[j]);
+  const uint32_t nsv = min(n_q, kCountChunk);
+  for (uint32_t x = wave_id(); x < nsv; x += kThreads / 64) {
+    const uint32_t doc = __builtin_amdgcn_readfirstlane(queue[x]);
+    bool hit = phrase_exists(ix.fwd, ix.fwd_off[doc], ix.fwd_off[doc + 1], pterm, ppos, n, span);
+    if (!hit && ix.fwd_off_name)
+      hit = phrase_exists(ix.fwd_name, ix.fwd_off_name[doc], ix.fwd_off_name[doc + 1], pterm, ppos, n, span);
+    if (hit && lane_id() == 0) atomicOr(&bits[doc >> 5], 1u << (doc & 31u));
+  }
+}
+
+// k_cmatch for the slots that hold a clause row.  A list item (kCountText) is
+// k_cmatch's: kCountChunk postings of the slot's shortest Must term or of a
+// Should term.  A row item (kCountRow) is kCountWordChunk words of a driver row --
+// the first Must row when the Musts are rows only, or a Should row -- a lane per
+// word: the slot's Must rows, MustNot rows and filter row join word-wise, then
+// each bit left is probed in the slot's terms (with a row driver: MustNots only).
+// A list item's docs are probed in the terms first, then tested bit by bit in
+// the rows.  One atomic OR per bitmap word either way.
+__global__ __launch_bounds__(kThreads) void k_cjoin(DevIndex ix, DevCount c) {
+  const uint32_t item = blockIdx.x;
+  const uint32_t q = c.j_q[item], kind = c.j_kind[item], st = c.j_start[item], t = c.j_term[item];
+  uint32_t* __restrict__ m = c.match + (size_t)q * c.words;
+  const uint32_t qm = c.q_m[q], nt = min(qm_terms(qm), kMaxTerms), nmust = qm_must(qm);
+  const uint32_t* __restrict__ qt = c.q_terms + (size_t)q * kMaxTerms;
+  const uint32_t rm = c.q_rm[q], nr = min(rm & 0xFFFFu, kMaxTerms), nrmust = rm >> 16;
+  const uint32_t* __restrict__ qr = c.q_rows + (size_t)q * kMaxTerms;
+  const uint32_t flt = c.q_filter[q];
+  const uint32_t* __restrict__ fb = flt != kInvalid ? c.fbits + (size_t)flt * c.words : nullptr;
+  if (kind == kCountRow) {
+    const uint32_t* __restrict__ drv = c.cbits + (size_t)t * c.words;
+    const uint32_t end = st + min(c.words - st, kCountWordChunk);
+    for (uint32_t x = st + threadIdx.x; x < end; x += kThreads) {
+      uint32_t v = drv[x];
+      for (uint32_t j = 0; j < nr && v; ++j) {
+        const uint32_t r = c.cbits[(size_t)qr[j] * c.words + x];
+        v &= j < nrmust ? r : ~r;
+      }
+      if (v && fb) v &= fb[x];
+      for (uint32_t rest = nt ? v : 0u; rest; rest &= rest - 1u) {
+        const uint32_t b = (uint32_t)__ffs((int)rest) - 1u, doc = x * 32u + b;
+        for (uint32_t j = 0; j < nt; ++j) {
+          const uint32_t u = qt[j];
+          if (term_has_doc(ix, ix.tmeta[u], ix.off[u], ix.dir_off[u], doc) != (j < nmust)) {
+            v &= ~(1u << b);
+            break;
+          }
+        }
+      }
+      if (v) atomicOr(&m[x], v);
+    }
+    return;
+  }
+  const uint64_t b0 = ix.off[t];
+  const uint32_t len = (uint32_t)(ix.off[t + 1] - b0);
+  const uint32_t cnt = min(len - st, kCountChunk);
+  uint32_t d[kCountItems];
+  uint32_t live = count_load_docs(ix.doc + b0, st, cnt, d);
+  for (uint32_t j = 0; j < nt; ++j) {
+    const uint32_t u = qt[j];
+    const uint32_t meta = ix.tmeta[u], dir_off = ix.dir_off[u];
+    const uint64_t base = ix.off[u];
+    const bool want = j < nmust;
+#pragma unroll
+    for (uint32_t r = 0; r < kCountItems; ++r)
+      if ((live >> r) & 1u)
+        if (term_has_doc(ix, meta, base, dir_off, d[r]) != want) live &= ~(1u << r);
+  }
+  for (uint32_t j = 0; j < nr; ++j) {
+    const uint32_t* __restrict__ rb = c.cbits + (size_t)qr[j] * c.words;
+    const uint32_t want = j < nrmust ? 1u : 0u;
+#pragma unroll
+    for (uint32_t r = 0; r < kCountItems; ++r)
+      if (((live >> r) & 1u) && ((rb[d[r] >> 5] >> (d[r] & 31u)) & 1u) != want) live &= ~(1u << r);
+  }
+  if (fb) {
+#pragma unroll
+    for (uint32_t r = 0; r < kCountItems; ++r)
+      if (((live >> r) & 1u) && !((fb[d[r] >> 5] >> (d[r] & 31u)) & 1u)) live &= ~(1u << r);
+  }
+  count_or_merged(m, d, live);
+}
+
 // match &= alive, the bits at or past N cleared (k_cfacet then reads finished
 // bitmaps), and the slot's total: popcounts summed per wave, one atomic add per
 // workgroup.  Workgroup = (slot, kCountWordChunk words).
@@ -4500,18 +4686,23 @@ __global__ __launch_bounds__(kThreads) void k_cfacet(DevIndex ix, DevCount c) {
 
 }  // namespace
 
-// ev (or nullptr): 5 events recorded around the four kernels (fg_count_trace)
+// ev (or nullptr): kCountEvents events recorded around the six kernels, in launch order
+// (fg_count_trace, fg_count_clause_trace)
 hipError_t launch_count(const DevIndex& ix, const DevCount& c, hipStream_t s, hipEvent_t* ev) {
   if (ev) (void)hipEventRecord(ev[0], s);
   if (c.n_fchunks) k_cfilter<<<c.n_fchunks, kThreads, 0, s>>>(ix, c);
   if (ev) (void)hipEventRecord(ev[1], s);
+  if (c.n_ritems) k_crow<<<c.n_ritems, kThreads, 0, s>>>(ix, c);
+  if (ev && ev[2] != ev[1]) (void)hipEventRecord(ev[2], s);  // (a pass without clause rows: one event for both slots)
   if (c.n_items) k_cmatch<<<c.n_items, kThreads, 0, s>>>(ix, c);
-  if (ev) (void)hipEventRecord(ev[2], s);
+  if (ev) (void)hipEventRecord(ev[3], s);
+  if (c.n_jitems) k_cjoin<<<c.n_jitems, kThreads, 0, s>>>(ix, c);
+  if (ev && ev[4] != ev[3]) (void)hipEventRecord(ev[4], s);
   const uint32_t wchunks = (c.words + kCountWordChunk - 1) / kCountWordChunk;
   if (c.nq && wchunks) k_ccount<<<c.nq * wchunks, kThreads, 0, s>>>(ix, c, wchunks);
-  if (ev) (void)hipEventRecord(ev[3], s);
+  if (ev) (void)hipEventRecord(ev[5], s);
   if (c.n_cchunks && c.nq) k_cfacet<<<c.n_cchunks, kThreads, 0, s>>>(ix, c);
-  if (ev) (void)hipEventRecord(ev[4], s);
+  if (ev) (void)hipEventRecord(ev[6], s);
   return hipGetLastError();
 }
 

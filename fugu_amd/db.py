@@ -375,7 +375,9 @@ class Database:
     def facet_counts(self, namespace: Optional[str], root: str = "/", query: Optional[str] = None, filters=None):
         """([(facet path, count)], total): the direct children of `root` with a
         nonzero count among the docs matching `query` (None / blank: AllQuery) and
-        `filters`, in encoded-facet order, and the number of matching docs."""
+        `filters`, in encoded-facet order, and the number of matching docs.  A query
+        with a phrase or a group is counted only with native.count_clauses(1) (a group
+        needs native.group_clauses(1) to parse); otherwise it raises Unsupported."""
         farr, nf = _strs(filters)
         total = C.c_uint64(0)
         pairs = _facets_call(lambda buf, cap, ln, cnt, ncap, n: _lib.fg_db_facet_counts(

@@ -65,7 +65,7 @@ EXPORTS = (
     "fg_count_batch", "fg_count_trace", "fg_index_doctab_get", "fg_index_doctab8_get",
     "fg_index_build_positional", "fg_index_positions_get",
     "fg_index_bands_get", "fg_index_band_read", "fg_plan_tiered_slots",
-    "fg_phrase_clauses", "fg_group_clauses", "fg_filter_clauses",
+    "fg_phrase_clauses", "fg_group_clauses", "fg_filter_clauses", "fg_count_clauses", "fg_count_clause_trace",
 )
 BAND_TIERS = 5  # fugu.h FG_BAND_TIERS
 LADDER_KS = (1, 2, 3, 5, 10, 13, 20, 25, 50, 100, 125, 250, 500, 1000)  # FG_LADDER_LEVELS ranks
@@ -192,6 +192,9 @@ if hasattr(_lib, "fg_group_clauses"):  # (likewise)
     _sig("fg_group_clauses", C.c_int, C.c_int)
 if hasattr(_lib, "fg_filter_clauses"):  # (likewise)
     _sig("fg_filter_clauses", C.c_int, C.c_int)
+if hasattr(_lib, "fg_count_clauses"):  # (likewise)
+    _sig("fg_count_clauses", C.c_int, C.c_int)
+    _sig("fg_count_clause_trace", C.c_int, C.c_int, _f64p, _u32p)
 _sig("fg_index_df", C.c_uint64, _p, C.c_int, C.c_uint32)
 _sig("fg_index_bm25", C.c_int, _p, C.c_uint32, _f32p, _f32p, _f32p)
 _sig("fg_plan_create", C.c_int, _p, C.POINTER(QueryBatch), C.c_uint32, C.POINTER(_p))
@@ -289,6 +292,16 @@ def filter_clauses(on: int = -1) -> int:
     if not hasattr(_lib, "fg_filter_clauses"):
         raise Unsupported(FG_EUNSUPPORTED, "this libfugu has no fg_filter_clauses")
     return int(_lib.fg_filter_clauses(int(on)))
+
+
+def count_clauses(on: "int | None" = None) -> int:
+    """fg_count_clauses: count_batch (and the database's facet_counts / facet_tree / facets_json)
+    count queries with phrase and group clauses (k_crow, k_cjoin) when on; process-wide, off by
+    default, read once per count_batch call.  on: 1 / 0 sets it, None (or < 0) only asks.
+    Returns the previous setting."""
+    if not hasattr(_lib, "fg_count_clauses"):
+        raise Unsupported(FG_EUNSUPPORTED, "this libfugu has no fg_count_clauses")
+    return int(_lib.fg_count_clauses(-1 if on is None else int(on)))
 
 
 def device_count() -> int:
@@ -952,6 +965,19 @@ def count_trace(enable: int = -1):
     n = C.c_uint32(0)
     _check(_lib.fg_count_trace(enable, _ptr(ms, _f64p), C.byref(n)))
     return dict(zip(COUNT_KERNELS, ms.tolist())), n.value
+
+
+COUNT_CLAUSE_KERNELS = ("k_crow", "k_cjoin")
+
+
+def count_clause_trace(enable: int = -1):
+    """fg_count_clause_trace: count_trace's contract for the two kernels of phrase and group clauses."""
+    if not hasattr(_lib, "fg_count_clause_trace"):
+        raise Unsupported(FG_EUNSUPPORTED, "this libfugu has no fg_count_clause_trace")
+    ms = np.zeros(2, np.float64)
+    n = C.c_uint32(0)
+    _check(_lib.fg_count_clause_trace(enable, _ptr(ms, _f64p), C.byref(n)))
+    return dict(zip(COUNT_CLAUSE_KERNELS, ms.tolist())), n.value
 
 
 def merge_shards(n_shards: int, n_queries: int, k: int, d_score: int, d_doc: int, d_n: int, d_out_score: int,

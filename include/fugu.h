@@ -426,7 +426,8 @@ int fg_phrase_clauses(int on);
  * value is answered as before (FG_EINVAL "bad phrase_len").  On, outside the
  * subset (FG_EUNSUPPORTED): "group clause beside a phrase clause", "group with
  * facet filters" (unless fg_filter_clauses(1) is set as well), a group in
- * fg_count_batch or fg_model_batch. */
+ * fg_model_batch, and a group in fg_count_batch unless fg_count_clauses(1) is
+ * set (below: that switch alone decides for counts). */
 #define FG_CLAUSE_ANY 0x80000000u
 #define FG_CLAUSE_ALL 0x40000000u
 int fg_group_clauses(int on);
@@ -442,8 +443,9 @@ int fg_group_clauses(int on);
  * clauses' scores summed from 0.0 in clause order).  A query whose facet clauses
  * match no doc of a snapshot has no hits there.  Off: such a query is
  * FG_EUNSUPPORTED "phrase with facet filters" / "group with facet filters", as
- * before.  fg_count_batch and fg_model_batch refuse phrase and group clauses
- * either way. */
+ * before.  fg_model_batch refuses phrase and group clauses either way;
+ * fg_count_batch counts them, with or without facet clauses, under its own
+ * switch fg_count_clauses (below) and consults none of these three. */
 int fg_filter_clauses(int on);
 
 /* Plan a batch: host-side query planning (tantivy Weight creation: terms
@@ -583,7 +585,8 @@ int fg_search_batch(fg_index* ix, const fg_query_batch* q, uint32_t k, float* ou
  * union of their lists (a missing facet term matches nothing); without text
  * terms the union alone, and without clauses AllQuery (every alive doc).  A
  * phrase clause (phrase_len >= 2): FG_EUNSUPPORTED, "phrase clause in a count
- * query".
+ * query", and a group clause while fg_group_clauses is on: "group clause in a
+ * count query" -- unless fg_count_clauses(1) is set (below), which counts both.
  *   out_total[i]               = |match(i)| summed over the snapshots (Count);
  *   out_count[i * n_count + j] = |match(i) & postings(count_terms[j])| summed --
  *     the facet field indexes every ancestor of a doc's facets once per doc, so
@@ -608,6 +611,33 @@ int fg_count_batch(fg_index* const* ixs, uint32_t n_segs, const fg_query_batch* 
  * k_cfacet since the last call, *calls (may be NULL) the fg_count_batch calls timed.
  * Reading resets the sums. */
 int fg_count_trace(int enable, double* ms_out, uint32_t* calls);
+
+/* Phrase and group clauses in fg_count_batch when on != 0.  The
+ * contract of fg_phrase_clauses: process-wide, off by default, on: 1 / 0 sets it,
+ * < 0 only asks; returns the previous setting.  fg_count_batch reads it once per
+ * call.  Off: fg_count_batch answers as before.  On: fg_count_batch alone decides
+ * (it consults none of fg_phrase_clauses, fg_group_clauses, fg_filter_clauses): a
+ * phrase_len entry n >= 2 is a phrase with its phrase_pos offsets, an entry with
+ * FG_CLAUSE_ANY / FG_CLAUSE_ALL a group, both checked by fg_plan_create's rules
+ * and messages ("bad phrase_len at term N", "phrase offsets must increase",
+ * "phrase offset too large"; a phrase on a snapshot built without positions:
+ * FG_EUNSUPPORTED "snapshot built without positions").  Phrases, groups and plain
+ * terms may stand in any mix in one query, under any occur, with or without
+ * facet clauses; FG_MAX_TERMS and FG_MAX_FACET_CLAUSES hold.  The match set is
+ * fg_count_batch's rule over clause doc sets: a term's merged list; a phrase's
+ * docs with the phrase in the text field or in the name field (offsets as given,
+ * repeated terms allowed); an any-of group's union and an all-of group's
+ * intersection of their members' lists.  Per snapshot a phrase with
+ * FG_TERM_MISSING or a term the snapshot lacks is absent, an any-of group drops
+ * such members and is absent with none left, an all-of group with one is absent;
+ * an absent Must clause empties the query there, an absent Should / MustNot
+ * clause is dropped.  Each distinct phrase or group of a slice of the batch
+ * takes one more bitmap (N / 8 bytes) inside the FUGU_COUNT_WS_KB bound.
+ * fg_model_batch keeps refusing both. */
+int fg_count_clauses(int on);
+/* Diagnostic: fg_count_trace's contract for the two kernels of phrase and group
+ * clauses: ms_out[2] (may be NULL) = the summed device ms of k_crow, k_cjoin. */
+int fg_count_clause_trace(int enable, double* ms_out, uint32_t* calls);
 
 /* Cross-shard merge: per-shard top-k lists gathered from
  * n_shards GPUs (RCCL all-gather) merged into the global top-k by (score

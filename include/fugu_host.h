@@ -41,8 +41,11 @@
  * `(a OR b)` any-of, `(a AND b)` / `(+a +b)` all-of; bare, behind `+` / `-`, or
  * an operand of the uniform AND / OR forms -- and mixed infix `a AND b OR c`,
  * where AND binds tighter.  fg_parse_query_clauses prints a group as
- * "<occur>:(a | b)" or "<occur>:(a & b)"; fg_parse_query, fg_parse_query_occur
- * and the count entry points refuse one.  Queries outside the device subset
+ * "<occur>:(a | b)" or "<occur>:(a & b)"; fg_parse_query and fg_parse_query_occur
+ * refuse one, and so do the count entry points (fg_db_facet_counts,
+ * fg_db_facet_tree, fg_db_facets_json) unless fg_count_clauses(1) is set (fugu.h;
+ * process-wide, off by default), with which they count phrase and group queries
+ * as fg_db_search* run them.  Queries outside the device subset
  * (grouping while that switch is off or deeper than one level, a phrase beside other
  * clauses while that switch is off, a phrase or a group with filters unless
  * fg_filter_clauses(1) is set (fugu.h; process-wide, off by default), slop / prefix
@@ -193,8 +196,9 @@ int fg_db_doc_facets(fg_db* db, const char* ns, uint32_t doc, char* out, size_t 
 /* list_facet / get_facets_at (:78-110), and the count the reference left
  * commented out (src/db/search.rs:436-454) over ALL matches: the direct children
  * of root_path ("/" = the top level) among the docs matching `query` (NULL or
- * blank: AllQuery; parsed as fg_db_search_ex parses it; a phrase clause:
- * FG_EUNSUPPORTED) and `filters`; *total (may be NULL) = the matching docs. */
+ * blank: AllQuery; parsed as fg_db_search_ex parses it; a phrase or group
+ * clause: FG_EUNSUPPORTED unless fg_count_clauses(1) is set) and `filters`;
+ * *total (may be NULL) = the matching docs. */
 int fg_db_facet_counts(fg_db* db, const char* ns, const char* query, const char* const* filters, uint32_t n_filters,
                        const char* root_path, char* out_paths, size_t cap, size_t* len, uint64_t* out_counts,
                        uint32_t count_cap, uint32_t* n_out, uint64_t* total);

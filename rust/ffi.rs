@@ -286,6 +286,8 @@ extern "C" {
     pub fn fg_count_batch(ixs: *const *mut fg_index, n_segs: u32, q: *const fg_query_batch, count_terms: *const u32,
                           n_count: u32, out_total: *mut u64, out_count: *mut u64) -> c_int;
     pub fn fg_count_trace(enable: c_int, ms_out: *mut f64, calls: *mut u32) -> c_int;
+    pub fn fg_count_clauses(on: c_int) -> c_int;
+    pub fn fg_count_clause_trace(enable: c_int, ms_out: *mut f64, calls: *mut u32) -> c_int;
     pub fn fg_merge_shards(n_shards: u32, n_queries: u32, k: u32, d_score: *const f32, d_doc: *const u32,
                            d_n: *const u32, d_out_score: *mut f32, d_out_doc: *mut u32, d_out_shard: *mut u32,
                            d_out_n: *mut u32, stream: *mut c_void) -> c_int;
