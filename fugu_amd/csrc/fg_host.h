@@ -607,7 +607,10 @@ struct fg_plan {
 // Diagnostic entry point, not part of include/fugu.h: overwrites the plan's
 // starting thresholds (DevPlan::q_thr0) with the lowest key of score[i] per
 // batch query (0: none), e.g. each query's final k-th score of an earlier run
-// -- the ceiling of what any threshold work can give k_conj
+// -- the ceiling of what any threshold work can give k_conj.  Every top-k
+// kernel starts its work items from it (k_conj, k_disj, k_scan, k_phrase,
+// k_bphrase, k_group), so a seeded plan shows each kernel's pruning at a known
+// threshold; the planner itself sets it for k_conj and k_disj slots only.
 extern "C" int fg_plan_seed_thr0(fg_plan* p, const float* score, uint32_t n);
 
 namespace fgh {

@@ -702,7 +702,7 @@ struct DevPlan {
   const uint32_t* work_c;       // [total_chunks] first chunk of the item's group (k_disj: first tile)
   const uint32_t* work_n;       // [total_chunks] chunks in the item's group (k_disj: tiles)
   const uint64_t* cand_off;     // [nq+1] candidate-list capacity offsets (work items of q * k)
-  const uint64_t* q_thr0;       // [nq] starting threshold key (k_disj: per-term top-K bound), 0 = none
+  const uint64_t* q_thr0;       // [nq] starting threshold key, read by every top-k kernel; 0 = none (planned for k_disj / k_conj slots only: per-term top-K bound)
   const float* q_ub;            // [nq * kMaxTerms] k_conj MaxScore bounds: q_ub[i] = sum over the query's
                                 //     terms j >= i (intersection order) of their scaled tmaxs, i >= 1
   const ProbeDesc* q_probe;     // [nq * kMaxTerms] k_conj's probe descriptors, on the slot's own snapshot: entry 0

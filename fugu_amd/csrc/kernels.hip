@@ -2181,6 +2181,17 @@ __device__ inline void scan_truncate(ScanShared& sh, uint32_t K, uint32_t limit,
   __syncthreads();
 }
 
+// A work item's first threshold (thread 0): the larger of the plan's starting
+// threshold t0 (DevPlan::q_thr0[q]; 0: none, what the planner leaves for these
+// slots; read with the item's other uniform loads, before the branch) and the
+// query's published one.  As k_conj's: the seed is published under pub_mask and
+// goes to the peers.
+__device__ inline uint64_t start_threshold(const DevPlan& pl, uint64_t t0, uint32_t ql, uint64_t* gthr) {
+  const uint64_t g = atomicMax(reinterpret_cast<unsigned long long*>(gthr), (unsigned long long)(t0 & pl.pub_mask));
+  if (t0) peer_thr_max(pl, ql, t0);
+  return g > t0 ? g : t0;
+}
+
 template <bool kMulti>
 __global__ __launch_bounds__(kThreads) void k_scan(DevIndex ix0, DevPlan pl) {
   __shared__ ScanShared sh;
@@ -2192,6 +2203,7 @@ __global__ __launch_bounds__(kThreads) void k_scan(DevIndex ix0, DevPlan pl) {
   const uint32_t tile0 = pl.work_c[w], ntile = pl.work_n[w];
   const uint32_t K = pl.k;
   uint64_t* gthr = &pl.thresh[ql];
+  const uint64_t thr0 = pl.q_thr0[q];  // the plan's starting threshold (0: none)
   const uint32_t fslot = pl.f.q_filter[q];
   const uint32_t* fmask = nullptr;
   uint32_t fshift = 0;
@@ -2205,7 +2217,7 @@ __global__ __launch_bounds__(kThreads) void k_scan(DevIndex ix0, DevPlan pl) {
   }
   if (tid == 0) {
     sh.n_buf = 0;
-    sh.thr = atomicMax(reinterpret_cast<unsigned long long*>(gthr), 0ull);
+    sh.thr = start_threshold(pl, thr0, ql, gthr);
   }
   __syncthreads();
   for (uint32_t t = 0; t < ntile; ++t) {
@@ -2303,6 +2315,7 @@ __global__ __launch_bounds__(kThreads) void k_phrase(DevIndex ix0, DevPlan pl) {
   const uint32_t chunk0 = pl.work_c[w], nchunk = pl.work_n[w];
   const uint32_t K = pl.k;
   uint64_t* gthr = &pl.thresh[ql];
+  const uint64_t thr0 = pl.q_thr0[q];  // the plan's starting threshold (0: none)
   const uint32_t qm = pl.q_m[q];
   const uint32_t nd = min(qm_terms(qm), kMaxTerms), np = min(qm_phrase_terms(qm), kMaxTerms);
   const size_t row = (size_t)q * kMaxTerms;
@@ -2333,7 +2346,7 @@ __global__ __launch_bounds__(kThreads) void k_phrase(DevIndex ix0, DevPlan pl) {
   if (tid == 0) {
     sh.s.n_buf = 0;
     sh.n_q = 0;
-    sh.s.thr = atomicMax(reinterpret_cast<unsigned long long*>(gthr), 0ull);
+    sh.s.thr = start_threshold(pl, thr0, ql, gthr);
   }
   __syncthreads();
   uint32_t span = 0;  // the phrase's largest offset
@@ -2482,6 +2495,7 @@ __global__ __launch_bounds__(kThreads) void k_bphrase(DevIndex ix0, DevPlan pl) 
   const uint32_t nchunk = pl.work_n[w] & ((1u << kBpPassShift) - 1u);
   const uint32_t K = pl.k;
   uint64_t* gthr = &pl.thresh[ql];
+  const uint64_t thr0 = pl.q_thr0[q];  // the plan's starting threshold (0: none)
   const uint32_t qm = pl.q_m[q];
   const uint32_t ncl = min(qm_terms(qm), kMaxTerms), nt = min(qm_phrase_terms(qm), kMaxTerms);
   if (ncl == 0 || nt == 0) return;  // (never planned; uniform)
@@ -2515,7 +2529,13 @@ __global__ __launch_bounds__(kThreads) void k_bphrase(DevIndex ix0, DevPlan pl) 
   if (tid == 0) {
     sh.s.n_buf = 0;
     sh.n_q = 0;
-    sh.s.thr = atomicMax(reinterpret_cast<unsigned long long*>(gthr), 0ull);
+    // Code placement, not logic: reading the seed grew this start-up by 60 bytes modulo the 64-byte
+    // instruction-cache line, and the loops below, the same instructions as before, then ran 0.8 % slower
+    // (49.5 against 49.1 ms in tools/bench_bool_phrase.py).  Four bytes more put them back on the lines they
+    // had; 68 or 196 do the same (profiles/seeded_clauses/bench_pairs.txt).  To be measured again, and dropped
+    // or resized, by whatever next changes the code in front of this kernel's loops.
+    asm volatile("s_nop 0");
+    sh.s.thr = start_threshold(pl, thr0, ql, gthr);
   }
   __syncthreads();
   const bool must = cl_occur(sh.cl[0]) == kClMust;  // (the Musts stand first)
@@ -2746,6 +2766,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_group(DevIndex ix0, DevPlan pl)
   const uint32_t nchunk = wn & ((1u << kGrpClauseShift) - 1u);
   const uint32_t K = pl.k;
   uint64_t* gthr = &pl.thresh[ql];
+  const uint64_t thr0 = pl.q_thr0[q];  // the plan's starting threshold (0: none)
   const uint32_t qm = pl.q_m[q];
   const uint32_t ncl = min(qm_terms(qm), kMaxTerms), nt = min(qm_phrase_terms(qm), kMaxTerms);
   if (ncl == 0 || nt == 0) return;  // (never planned; uniform)
@@ -2776,7 +2797,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_group(DevIndex ix0, DevPlan pl)
   for (uint32_t i = tid; i < 512u; i += kThreads) sh.cache[i] = ix.cache[i];
   if (tid == 0) {
     sh.s.n_buf = 0;
-    sh.s.thr = atomicMax(reinterpret_cast<unsigned long long*>(gthr), 0ull);
+    sh.s.thr = start_threshold(pl, thr0, ql, gthr);
   }
   __syncthreads();
   const bool must = cl_occur(sh.cl[0]) == kClMust;  // (the Musts stand first)

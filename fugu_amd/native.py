@@ -858,7 +858,8 @@ class Plan:
 
     def seed_thresholds(self, score):
         """fg_plan_seed_thr0 (diagnostic): every query starts from the lowest key with
-        score[i] ([n_batch] f32, 0: no starting threshold)."""
+        score[i] ([n_batch] f32, 0: no starting threshold).  Every top-k kernel reads
+        it: k_conj, k_disj, k_scan, k_phrase, k_bphrase and k_group."""
         s = np.ascontiguousarray(score, np.float32)
         if s.shape != (self.n_batch,):
             raise ValueError(f"scores of {s.shape}, expected ({self.n_batch},)")
