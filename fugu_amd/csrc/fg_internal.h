@@ -291,6 +291,9 @@ constexpr uint32_t kClAny = 1u << 12, kClAll = 1u << 13;
 // a k_group work item's work_n: the lead chunks of its group, above them the
 // clause it leads from and that clause's member whose list it sweeps (the pass)
 constexpr uint32_t kGrpClauseShift = 8, kGrpMemberShift = 12;
+// A slot of k_gphrase (a group clause beside a phrase clause: fg_group_phrase_clauses,
+// DESIGN.md §18): q_m, the q_clause row and work_n as k_group's, with phrase clauses
+// (kClPhrase) among the clauses; DevPlan::n_gphrase describes the rows.
 
 // Rank words (DevIndex::rank): one u64 per 32 docs, the low half the docs'
 // presence bits, the high half the number of the term's postings before the
@@ -754,6 +757,15 @@ struct DevPlan {
   uint32_t n_group;             // k_group work items (queries with a group clause: fg_group_clauses), after the
                                 // k_bphrase items: (query slot, group of kChunk-posting chunks of a lead list,
                                 // the (clause, member) led from in work_n's upper bits)
+  uint32_t n_gphrase;           // k_gphrase work items (queries with a group clause AND a phrase clause:
+                                // fg_group_phrase_clauses), after the k_group items, work_n as k_group's.  Such a
+                                // slot's rows hold every clause's terms, clause after clause in q_clause's order:
+                                // q_terms the snapshot's ids; q_wt / q_wn / q_ub / q_rup per member for term
+                                // clauses and group members (as k_group's); a phrase clause (kClPhrase) has
+                                // q_pterm / q_ppos over its rows (the anchor first), its two field weights in
+                                // q_wt / q_wn at its first row, and q_ub = (text weight, name weight, 0, ...) over
+                                // its rows (a field's entry 0.0 where the phrase cannot match in the snapshot), so
+                                // group_bound's sum over a clause's rows bounds the phrase's score
   // Multi-snapshot plans (several segments / doc shards / namespaces of one
   // device in ONE launch per kernel): query slot v = s * seg_nq + q is query q
   // of the batch on snapshot segs[s]; every per-query array above is indexed by
@@ -1064,6 +1076,7 @@ hipError_t launch_scan(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 hipError_t launch_phrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 hipError_t launch_bphrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 hipError_t launch_group(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
+hipError_t launch_gphrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 // out_shard != nullptr: the merged select of a multi-snapshot plan (one list per batch query)
 hipError_t launch_final(const DevPlan& pl, float* out_score, uint32_t* out_doc, uint32_t* out_n, hipStream_t s,
                         uint32_t* out_shard = nullptr);

@@ -2887,6 +2887,233 @@ __global__ __launch_bounds__(kThreads, 4) void k_group(DevIndex ix0, DevPlan pl)
   flush_candidates(pl, q, sh.s.buf, sh.s.n_buf, sh.s.thr, sh.s.scratch);
 }
 
+// ---------------------------------------------------------------- k_gphrase
+// Queries with a group clause BESIDE a phrase clause (fg_group_phrase_clauses,
+// DESIGN.md §18).  The slot's clause table, its per-member rows and its passes
+// are k_group's, with phrase clauses (kClPhrase: q_pterm / q_ppos over the
+// clause's rows, the anchor -- its rarest term -- first) among the clauses; a
+// pass that leads from a phrase sweeps the anchor's list (member 0).  Per lead
+// chunk, kRound docs between truncations:
+//  (a) one LANE per lead doc walks the clause table as k_group's lane does and
+//      scores the term and group clauses (posting_pos_at, tfn_score).  Of a
+//      phrase clause it only asks whether the doc holds every term
+//      (term_has_doc).  One that lacks a term is absent: the doc is dropped for
+//      a Must phrase, kept for a MustNot phrase, gets nothing from a Should
+//      phrase.  When no phrase clause is left open the lane finishes the join
+//      and appends the key itself.  A doc that the other clauses keep and that
+//      holds every term of some phrase clause -- in a pass without a Must also
+//      a Should phrase BEFORE the pass clause: whether it matches decides which
+//      pass owns the doc -- is queued in LDS with its lead posting;
+//  (b) one WAVE per queued doc walks the table again: every lane forms the term
+//      and group scores by the same instructions as (a) (so a score has the same
+//      bits on either path), and the wave counts each phrase on the forward
+//      index (phrase_count_at inside [fwd_off[d], fwd_off[d + 1]), the name field
+//      only where the snapshot has one), field_score per field, text then name
+//      from 0.0; the join is the reference's.
+// A doc leaves with the first (clause, member) pass that matches it, so
+// k_final's keys stay unique; all passes share the query's threshold word.
+// Pruning (exact): k_group's chunk skip, group_bound over the table.  A phrase
+// clause's rows carry (text weight, name weight, 0, ...) as their bounds (0.0 for
+// a field where the phrase cannot match in the snapshot), which group_bound
+// sums as the score sums the two fields: correctly rounded
+// c / (c + x) <= 1 and f32 operations are monotone, so w_t + w_n >= the phrase's
+// score bit for bit.  A pass that leads from a phrase bounds the lead row by the
+// text weight too: cmax bounds the term's score, not the phrase's.  No per-doc
+// bound is applied before a doc is queued.
+struct GPhraseShared {
+  GroupShared g;               // k_group's tables: the clause table and the per-member rows
+  uint32_t pterm[kMaxTerms];   // the phrase clauses' terms as vocabulary ids (DevIndex::fwd)
+  uint32_t ppos[kMaxTerms];    // ... and their offsets in their phrase
+  uint64_t queue[kRound];      // stage (b)'s docs: lead posting << 32 | doc
+  uint32_t n_q;
+};
+
+// The clause table over doc d (the lead list's posting i) for pass (pc, pm): whether the doc is a hit of this pass, and
+// its score.  kWave = false: one lane, a phrase clause whose terms the doc all holds is left open (`open`: the result
+// says only that no other clause drops the doc).  kWave = true: the whole wave on one doc (d, i uniform), phrases counted.
+template <bool kWave>
+__device__ inline bool gphrase_doc(const DevIndex& ix, const GPhraseShared& sh, uint32_t ncl, uint32_t nt, bool must,
+                                   uint32_t pc, uint32_t pm, bool name, uint32_t d, uint32_t i, bool& open, float& sc) {
+  const GroupShared& g = sh.g;
+  float req = 0.0f, oth = 0.0f, opt = 0.0f;
+  uint32_t nm = 0;
+  bool any = false, keep = true;
+  open = false;
+  for (uint32_t ci = 0; ci < ncl && keep; ++ci) {
+    const uint32_t cw = g.cl[ci], oc = cl_occur(cw), t0 = cl_first(cw), t1 = min(t0 + cl_terms(cw), nt);
+    float a = 0.0f, b = 0.0f;
+    bool on = (cw & kClAll) != 0;
+    if (cw & kClPhrase) {
+      on = false;
+      if (!kWave) {
+        bool all = true;
+        for (uint32_t x = t0; x < t1 && all; ++x)
+          if (ci != pc || x != t0) all = term_has_doc(ix, g.tmeta[x], g.toff[x], g.tdir[x], d);
+        if (all) {  // only the positions can tell: stage (b)
+          open = true;
+          continue;
+        }
+      } else {
+        const uint32_t n = t1 - t0, lane = lane_id();
+        uint32_t pos = kInvalid;
+        if (lane < n) {
+          const uint32_t x = t0 + lane;
+          pos = ci == pc && lane == 0 ? i : posting_pos_at(ix, g.tmeta[x], g.toff[x], g.tdir[x], d);
+        }
+        if (n && __ballot(pos != kInvalid) == (1ull << n) - 1ull) {
+          const uint64_t p0 = g.toff[t0] + __builtin_amdgcn_readfirstlane(pos);
+          uint32_t v = ix.tfn[p0];
+          if (ix.tfn_name) v |= (uint32_t)ix.tfn_name[p0] << 16;
+          v = __builtin_amdgcn_readfirstlane(v);
+          uint32_t span = 0;  // the phrase's largest offset
+          for (uint32_t j = t0; j < t1; ++j) span = max(span, sh.ppos[j]);
+          uint32_t ct = 0, cn = 0;
+          if (v & 0xFFu) ct = phrase_count_at(ix.fwd, ix.fwd_off[d], ix.fwd_off[d + 1], sh.pterm + t0, sh.ppos + t0, n, span);
+          if (name && ((v >> 16) & 0xFFu))
+            cn = phrase_count_at(ix.fwd_name, ix.fwd_off_name[d], ix.fwd_off_name[d + 1], sh.pterm + t0, sh.ppos + t0, n,
+                                 span);
+          if (ct) a += field_score(ct, (v >> 8) & 0xFFu, g.wt[t0], g.cache);
+          if (cn) a += field_score(cn, v >> 24, g.wn[t0], g.cache + 256);
+          on = (ct | cn) != 0;
+        }
+      }
+    } else {
+      // a term, an any-of group (some member) or an all-of group (every member), as k_group's lane
+      for (uint32_t x = t0; x < t1; ++x) {
+        float s = 0.0f;
+        const bool has = group_member(ix, g, x, d, ci == pc && x - t0 == pm ? i : kInvalid, s);
+        if (cw & kClAll) {
+          if (!has) { on = false; break; }
+          if (x - t0 < 2) a = x == t0 ? s : a + s;
+          else b = b + s;
+        } else if (has) {
+          if ((cw & kClAny) && ci == pc && x - t0 < pm) keep = false;  // an earlier member's pass has the doc
+          a = on || (cw & kClAny) ? a + s : s;
+          on = true;
+        }
+      }
+    }
+    const float cs = (cw & kClAll) && t1 - t0 > 1 ? 0.0f + (a + b) : a;
+    if (oc == kClMust) {
+      if (!on) keep = false;
+      else if (nm == 0) req = cs;
+      else if (nm == 1) req = req + cs;
+      else oth = oth + cs;
+      ++nm;
+    } else if (oc == kClMustNot) {
+      if (on) keep = false;
+    } else if (!must && ci <= pc && on != (ci == pc)) {
+      keep = false;  // an earlier pass's doc, or the pass clause does not match
+    } else if (on) {
+      opt = opt + cs;
+      any = true;
+    }
+  }
+  sc = opt;
+  if (must) {
+    if (nm > 1) req = req + oth;
+    sc = 0.0f + req;
+    if (any) sc = sc + opt;
+  }
+  return keep;
+}
+
+template <bool kMulti>
+__global__ __launch_bounds__(kThreads, 4) void k_gphrase(DevIndex ix0, DevPlan pl) {
+  __shared__ GPhraseShared sh;
+  const uint32_t tid = threadIdx.x;
+  // after the k_group items
+  const uint32_t w = pl.total_chunks + pl.n_scan + pl.n_phrase + pl.n_bphrase + pl.n_group + blockIdx.x;
+  const uint32_t q = pl.work_q[w];
+  const DevIndex ix = kMulti ? seg_index(pl, __builtin_amdgcn_readfirstlane(q / pl.seg_nq)) : ix0;
+  const uint32_t ql = kMulti ? __builtin_amdgcn_readfirstlane(q % pl.seg_nq) : q;
+  const uint32_t chunk0 = pl.work_c[w];
+  const uint32_t wn = pl.work_n[w];
+  const uint32_t nchunk = wn & ((1u << kGrpClauseShift) - 1u);
+  const uint32_t K = pl.k;
+  uint64_t* gthr = &pl.thresh[ql];
+  const uint64_t thr0 = pl.q_thr0[q];  // the plan's starting threshold (0: none)
+  const uint32_t qm = pl.q_m[q];
+  const uint32_t ncl = min(qm_terms(qm), kMaxTerms), nt = min(qm_phrase_terms(qm), kMaxTerms);
+  if (ncl == 0 || nt == 0) return;  // (never planned; uniform)
+  const uint32_t pc = min((wn >> kGrpClauseShift) & 15u, ncl - 1);
+  const size_t row = (size_t)q * kMaxTerms;
+  if (tid < nt) {
+    const uint32_t t = pl.q_terms[row + tid];
+    sh.g.tmeta[tid] = ix.tmeta[t];
+    sh.g.tdir[tid] = ix.dir_off[t];
+    sh.g.toff[tid] = ix.off[t];
+    sh.g.wt[tid] = pl.q_wt[row + tid];
+    sh.g.wn[tid] = pl.q_wn[row + tid];
+    sh.g.ub[tid] = pl.q_ub[row + tid];
+    sh.pterm[tid] = pl.q_pterm[row + tid];
+    sh.ppos[tid] = pl.q_ppos[row + tid];
+  }
+  if (tid < ncl) sh.g.cl[tid] = pl.q_clause[row + tid];
+  for (uint32_t i = tid; i < 512u; i += kThreads) sh.g.cache[i] = ix.cache[i];
+  if (tid == 0) {
+    sh.g.s.n_buf = 0;
+    sh.n_q = 0;
+    sh.g.s.thr = start_threshold(pl, thr0, ql, gthr);
+  }
+  __syncthreads();
+  const bool must = cl_occur(sh.g.cl[0]) == kClMust;  // (the Musts stand first)
+  const uint32_t pcw = sh.g.cl[pc];
+  const uint32_t pm = min((wn >> kGrpMemberShift) & 15u, max(cl_terms(pcw), 1u) - 1u);
+  const uint32_t li = min(cl_first(pcw) + pm, nt - 1);  // the lead: member pm of clause pc (a phrase: its anchor, pm = 0)
+  const uint32_t lead = pl.q_terms[row + li];
+  const uint64_t base = sh.g.toff[li];
+  const uint32_t df = (uint32_t)(ix.off[lead + 1] - base);
+  const float* __restrict__ cmax = ix.cmax + ix.coff[lead];
+  const float rup = pl.q_rup[row + li];
+  const bool name = ix.tfn_name != nullptr && ix.fwd_off_name != nullptr;
+  for (uint32_t c = 0; c < nchunk; ++c) {
+    const uint32_t i0 = (chunk0 + c) * kChunk;
+    if (i0 >= df) break;
+    // the chunk's bound against the threshold (uniform: the threshold is read after a barrier); a phrase's lead row is
+    // bounded by the phrase's text weight (its row's q_ub), never by the term's chunk maximum
+    const float lead_ub = (pcw & kClPhrase) ? sh.g.ub[li] : fminf(cmax[chunk0 + c] * rup, sh.g.ub[li]);
+    const float bound = group_bound(sh.g, ncl, nt, must, pc, pm, lead_ub);
+    if (make_key(inflate_bound(bound), 0u) < sh.g.s.thr) continue;
+    for (uint32_t r0 = 0; r0 < kChunk; r0 += kRound) {
+      const uint64_t thr = sh.g.s.thr;
+      // (a) a lane per lead doc
+      for (uint32_t j = 0; j < kRound / kThreads; ++j) {
+        const uint32_t i = i0 + r0 + j * kThreads + tid;
+        bool keep = i < df, open = false;
+        uint32_t d = 0;
+        float sc = 0.0f;
+        if (keep) {
+          d = ix.doc[base + i];
+          keep = doc_alive(ix, d);
+        }
+        if (keep) keep = gphrase_doc<false>(ix, sh, ncl, nt, must, pc, pm, name, d, i, open, sc);
+        const uint64_t key = make_key(sc, d);
+        wave_append(keep && !open && key >= thr, key, sh.g.s.buf, &sh.g.s.n_buf, kBufD);
+        wave_append(keep && open, ((uint64_t)i << 32) | d, sh.queue, &sh.n_q, kRound);
+      }
+      __syncthreads();
+      // (b) a wave per queued doc
+      const uint32_t nsv = min(sh.n_q, kRound);
+      for (uint32_t x = wave_id(); x < nsv; x += kThreads / 64) {
+        const uint64_t e = sh.queue[x];
+        const uint32_t d = __builtin_amdgcn_readfirstlane((uint32_t)e);
+        const uint32_t i = __builtin_amdgcn_readfirstlane((uint32_t)(e >> 32));
+        bool open = false;
+        float sc = 0.0f;
+        const bool keep = gphrase_doc<true>(ix, sh, ncl, nt, must, pc, pm, name, d, i, open, sc);
+        const uint64_t key = make_key(sc, d);
+        wave_append(lane_id() == 0 && keep && key >= thr, key, sh.g.s.buf, &sh.g.s.n_buf, kBufD);
+      }
+      __syncthreads();
+      if (tid == 0) sh.n_q = 0;
+      scan_truncate(sh.g.s, K, kTrunc, gthr, false, pl.pub_mask, pl, ql);
+    }
+    scan_truncate(sh.g.s, K, K, gthr, true, pl.pub_mask, pl, ql);
+  }
+  flush_candidates(pl, q, sh.g.s.buf, sh.g.s.n_buf, sh.g.s.thr, sh.g.s.scratch);
+}
+
 // ---------------------------------------------------------------- k_final
 // Dynamic LDS (80 KB: 2 workgroups per CU): candidate keys, the k winners,
 // the radix histogram.  Keeps 16-B alignment of the dynamic base (no static
@@ -3239,6 +3466,13 @@ hipError_t launch_group(const DevIndex& ix, const DevPlan& pl, hipStream_t s) {
   if (pl.n_group == 0) return hipSuccess;
   if (pl.segs) k_group<true><<<pl.n_group, kThreads, 0, s>>>(ix, pl);
   else k_group<false><<<pl.n_group, kThreads, 0, s>>>(ix, pl);
+  return hipGetLastError();
+}
+
+hipError_t launch_gphrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s) {
+  if (pl.n_gphrase == 0) return hipSuccess;
+  if (pl.segs) k_gphrase<true><<<pl.n_gphrase, kThreads, 0, s>>>(ix, pl);
+  else k_gphrase<false><<<pl.n_gphrase, kThreads, 0, s>>>(ix, pl);
   return hipGetLastError();
 }
 

@@ -29,6 +29,9 @@ std::atomic<int> phrase_clauses_on{0};
 std::atomic<int> group_clauses_on{0};
 // fg_filter_clauses: phrase, phrase-beside and group queries may carry facet clauses; the same contract
 std::atomic<int> filter_clauses_on{0};
+// fg_group_phrase_clauses: queries with a group clause beside a phrase clause run on the device (k_gphrase); the
+// same contract
+std::atomic<int> group_phrase_clauses_on{0};
 
 // stable LSD radix sort of `a` by its bits 32..63 (three 11-bit passes)
 void radix_sort_hi32(std::vector<uint64_t>& a, std::vector<uint64_t>& tmp) {
@@ -64,15 +67,15 @@ struct PlanTables {
   std::vector<uint64_t> f_woff;
   std::vector<float> f_tab, f_max;
   std::vector<uint32_t> ch_f, ch_c, ch_t, ch_s;
-  // work items: k_conj's, k_disj's, k_scan's, k_phrase's, k_bphrase's, k_group's; items: all
+  // work items: k_conj's, k_disj's, k_scan's, k_phrase's, k_bphrase's, k_group's, k_gphrase's; items: all
   // of them as the kernels run them (order_items, joined tables only)
-  std::vector<WItem> citems, ditems, scan, phrase, bphrase, group, items;
+  std::vector<WItem> citems, ditems, scan, phrase, bphrase, group, gphrase, items;
   // (a thread's plans reuse one set: assign / push_back into kept capacity, no
   // page faults on fresh arrays -- ~0.2 ms of an 8-snapshot batch's planning)
   void clear() {
     auto all = [](auto&... v) { (v.clear(), ...); };
     all(q_m, q_terms, lead, q_filter, ngroup, q_hlo, q_hhi, q_hsh, thr0, q_ub, q_wt, q_wn, q_rup, f_shift, f_seg, f_woff,
-        f_tab, f_max, ch_f, ch_c, ch_t, ch_s, citems, ditems, scan, phrase, bphrase, group, items, q_pterm, q_ppos, q_clause,
+        f_tab, f_max, ch_f, ch_c, ch_t, ch_s, citems, ditems, scan, phrase, bphrase, group, gphrase, items, q_pterm, q_ppos, q_clause,
         q_probe, q_tier);
     nf = 0;
   }
@@ -349,9 +352,191 @@ int plan_group(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t
   return FG_OK;
 }
 
+// Query i of the batch when it holds a group clause AND a phrase clause and
+// fg_group_phrase_clauses is on (the clause table was checked by plan_phrase;
+// DESIGN.md §18): never with facet clauses, whatever fg_filter_clauses says, and
+// only on a snapshot with positions, else FG_EUNSUPPORTED.  Absence, the costs and
+// the order of the score sum are plan_bool_phrase's for a phrase and plan_group's
+// for a term or a group.  The slot's rows hold the clauses' terms, clause after
+// clause in the clause table's order: a term's or a group member's row as
+// plan_group's (q_terms / q_wt / q_wn / q_ub / q_rup); a phrase's rows q_terms /
+// q_pterm / q_ppos with its anchor first, its two field weights (q_wt / q_wn) at its
+// first row, and q_ub = (text weight, name weight, 0, ...) over its rows -- a field's
+// entry 0.0 when some term of the phrase has no posting in that field here --:
+// k_group's bound sums a clause's q_ub, which bounds the phrase's score by its weights.
+// Work items (k_gphrase), each with its pass (clause, member) in the count word:
+//  * a Must that is a term, a phrase or an all-of group exists: one pass, the
+//    shortest list among the term, the phrase's anchor and the group's shortest member;
+//  * every Must is an any-of group: a pass per member of the first (cheapest);
+//  * no Must: a pass per Should term, per Should phrase (its anchor), per Should
+//    all-of group (its shortest member) and per member of every Should any-of group.
+int plan_group_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t nq_size, uint32_t n_segs,
+                      PlanTables& h, bool nomatch) {
+  const uint32_t b = q->q_off[i], e = q->q_off[i + 1];
+  if (q->f_off && q->f_off[i + 1] > q->f_off[i])
+    return fail(FG_EUNSUPPORTED, "query %u: group and phrase clauses with facet filters", i);
+  if (!ix->has_positions) return fail(FG_EUNSUPPORTED, "query %u: snapshot built without positions", i);
+  auto len = [&](uint32_t t) { return (uint64_t)(ix->off[t + 1] - ix->off[t]); };
+  struct Mem { uint32_t t, vt, pp; uint64_t cost; };  // the snapshot's id, the vocabulary id, the offset in a phrase
+  struct Cl { uint32_t at, n, oc, kind, anchor; uint64_t cost; float wt, wn, ubt, ubn; };
+  Cl cl[fg::kMaxTerms];
+  Mem mem[fg::kMaxTerms];  // the kept members, a clause's at [at, at + n) in written order
+  uint32_t ncl = 0, nmem = 0, nm = 0, ns = 0;
+  bool must_missing = false;
+  for (uint32_t j = b; j < e;) {
+    const uint32_t raw = q->phrase_len[j], flags = raw & (FG_CLAUSE_ANY | FG_CLAUSE_ALL);
+    const uint32_t n = raw & ~(FG_CLAUSE_ANY | FG_CLAUSE_ALL);
+    const uint32_t oc = q->occur ? q->occur[j] : (q->mode == FG_MODE_OR ? FG_OCCUR_SHOULD : FG_OCCUR_MUST);
+    if (oc > FG_OCCUR_MUST_NOT) return fail(FG_EINVAL, "query %u: bad occur %u", i, oc);
+    const bool phrase = !flags && n >= 2;
+    if (phrase && q->phrase_pos[j + n - 1] >= (1u << 30)) return fail(FG_EINVAL, "query %u: phrase offset too large", i);
+    Cl c{nmem, 0, oc, flags == FG_CLAUSE_ANY ? fg::kClAny : flags == FG_CLAUSE_ALL ? fg::kClAll : phrase ? fg::kClPhrase : 0u,
+         0, 0, 0.0f, 0.0f, 0.0f, 0.0f};
+    bool absent = false;
+    uint64_t ct = ~0ull, cn = ~0ull;
+    float it = 0.0f, in = 0.0f;
+    for (uint32_t x = 0; x < n; ++x) {
+      const uint32_t t = fgh::local_term(ix, q->terms[j + x]);
+      if (!(t < ix->n_terms && ix->off[t + 1] > ix->off[t])) {
+        absent |= c.kind != fg::kClAny;
+        if (absent) break;
+        continue;
+      }
+      if (phrase) {
+        ct = std::min<uint64_t>(ct, ix->df_text[t]);
+        cn = std::min<uint64_t>(cn, ix->df_name[t]);
+        it += ix->idf_text[t];
+        in += ix->idf_name[t];
+        if (c.n && len(t) < len(mem[c.at + c.anchor].t)) c.anchor = c.n;
+      }
+      mem[nmem + c.n++] = Mem{t, q->terms[j + x], q->phrase_pos[j + x], (uint64_t)ix->df_text[t] + ix->df_name[t]};
+    }
+    j += n;
+    if (absent || c.n == 0) {
+      must_missing |= oc == FG_OCCUR_MUST;
+      continue;
+    }
+    Mem* m0 = mem + c.at;
+    if (phrase) {
+      c.cost = ct + cn;
+      c.wt = it * (1.0f + 1.2f);  // (1 + K1), as bm25_weight's
+      c.wn = in * (1.0f + 1.2f);
+      c.ubt = ct ? c.wt : 0.0f;
+      c.ubn = cn ? c.wn : 0.0f;
+    } else if (c.kind == fg::kClAll) {
+      std::stable_sort(m0, m0 + c.n, [](const Mem& x, const Mem& y) { return x.cost < y.cost; });
+      c.cost = m0[0].cost;
+    } else {
+      for (uint32_t x = 0; x < c.n; ++x) c.cost += m0[x].cost;
+    }
+    nmem += c.n;
+    nm += oc == FG_OCCUR_MUST;
+    ns += oc == FG_OCCUR_SHOULD;
+    cl[ncl++] = c;
+  }
+  // a Must matches nothing, no positive clause, or facet clauses that match no doc: no hits
+  if (must_missing || nm + ns == 0 || nomatch) return FG_OK;
+  if (nm == 0 && ns == 1)
+    for (uint32_t c = 0; c < ncl; ++c)
+      if (cl[c].oc == FG_OCCUR_SHOULD) { cl[c].oc = FG_OCCUR_MUST; nm = 1; ns = 0; }
+  // the order of the score sum
+  auto rank = [&](const Cl& c) {
+    if (nm) return c.oc == FG_OCCUR_MUST ? 0 : c.oc == FG_OCCUR_MUST_NOT ? 1 : 2;
+    return c.oc == FG_OCCUR_SHOULD ? 0 : 1;
+  };
+  std::stable_sort(cl, cl + ncl, [&](const Cl& x, const Cl& y) {
+    const int rx = rank(x), ry = rank(y);
+    if (rx != ry) return rx < ry;
+    return nm && rx == 0 && x.cost < y.cost;  // (stable: ties and the other kinds by clause position)
+  });
+  const size_t row = (size_t)i * fg::kMaxTerms;
+  uint32_t first[fg::kMaxTerms], o = 0;
+  for (uint32_t c = 0; c < ncl; ++c) {
+    const Cl& x = cl[c];
+    first[c] = o;
+    for (uint32_t u = 0, at = 1; u < x.n; ++u) {
+      const Mem& m = mem[x.at + u];
+      if (x.kind == fg::kClPhrase) {
+        const uint32_t dst = o + (u == x.anchor ? 0 : at++);
+        h.q_terms[row + dst] = m.t;
+        h.q_pterm[row + dst] = m.vt;
+        h.q_ppos[row + dst] = m.pp;
+        continue;
+      }
+      float rdn, rup;
+      fgh::term_ratio(ix, m.t, &rdn, &rup);
+      h.q_terms[row + o + u] = m.t;
+      h.q_wt[row + o + u] = ix->w_text[m.t];
+      h.q_wn[row + o + u] = ix->w_name[m.t];
+      h.q_rup[row + o + u] = rup;
+      h.q_ub[row + o + u] = fgh::term_max_scaled(ix, m.t, rup);
+    }
+    if (x.kind == fg::kClPhrase) {
+      h.q_wt[row + o] = x.wt;
+      h.q_wn[row + o] = x.wn;
+      // the bound (a phrase has >= 2 rows): a field's weight, or 0.0 where some term of the phrase has no posting
+      // in that field of this snapshot (x.ubt / x.ubn: the phrase cannot match there)
+      h.q_ub[row + o] = x.ubt;
+      h.q_ub[row + o + 1] = x.ubn;
+    }
+    h.q_clause[row + c] = fg::cl_pack(o, x.n, x.oc, x.kind == fg::kClPhrase, c) | (x.kind & (fg::kClAny | fg::kClAll));
+    o += x.n;
+  }
+  h.q_m[i] = fg::qm_phrase(ncl, o);
+  // the passes (clause, member)
+  struct Pass { uint32_t c, m; };
+  Pass pass[fg::kMaxTerms];
+  uint32_t np = 0;
+  auto term_of = [&](uint32_t c, uint32_t m) { return h.q_terms[row + first[c] + m]; };
+  auto candidate = [&](uint32_t c) {  // a term, a phrase's anchor (row 0), an all-of group's shortest member
+    uint32_t m = 0;
+    if (cl[c].kind == fg::kClAll)
+      for (uint32_t u = 1; u < cl[c].n; ++u)
+        if (len(term_of(c, u)) < len(term_of(c, m))) m = u;
+    return m;
+  };
+  bool driver = false;  // a Must that is a term, a phrase or an all-of group
+  for (uint32_t c = 0; c < nm; ++c) {
+    if (cl[c].kind == fg::kClAny) continue;
+    const Pass p{c, candidate(c)};
+    if (!driver || len(term_of(p.c, p.m)) < len(term_of(pass[0].c, pass[0].m))) pass[0] = p;
+    driver = true;
+  }
+  if (driver) {
+    np = 1;
+  } else {
+    for (uint32_t c = 0; c < (nm ? 1u : ns); ++c) {
+      if (cl[c].kind == fg::kClAny)
+        for (uint32_t u = 0; u < cl[c].n; ++u) pass[np++] = Pass{c, u};
+      else
+        pass[np++] = Pass{c, candidate(c)};
+    }
+  }
+  const uint32_t cdiv = n_segs <= 1 ? 1u : n_segs;
+  const uint32_t per_q = std::max<uint32_t>(
+      1, std::min<uint32_t>(64, std::max<uint32_t>(fg::kConjGroupsPerQuery, 1024 / std::max(nq_size, 1u))) / cdiv);
+  h.lead[i] = (uint32_t)len(term_of(pass[0].c, pass[0].m));
+  uint32_t total = 0;
+  for (uint32_t x = 0; x < np; ++x) {
+    const uint32_t nch = (uint32_t)((len(term_of(pass[x].c, pass[x].m)) + fg::kChunk - 1) / fg::kChunk);
+    if (h.gphrase.size() + nch > 0x7FFFFFFFull)
+      return fail(FG_EUNSUPPORTED, "batch too large (%zu work items)", h.gphrase.size());
+    const uint32_t G = std::min<uint32_t>(fg::kPhraseMaxGroup, std::max<uint32_t>(1, (nch + per_q - 1) / per_q));
+    const uint32_t ng = (nch + G - 1) / G;
+    for (uint32_t g = 0; g < ng; ++g)
+      h.gphrase.push_back(WItem{(g + 0.5) / ng, i, g * G,
+                                std::min(G, nch - g * G) | (pass[x].c << fg::kGrpClauseShift) |
+                                    (pass[x].m << fg::kGrpMemberShift)});
+    total += ng;
+  }
+  h.ngroup[i] = total;
+  return FG_OK;
+}
+
 // Query i of the batch when it holds a phrase clause (fg_query_batch::phrase_len
 // >= 2; *phrase = 0 otherwise, after checking the clause table; a group clause,
-// fg_group_clauses, goes to plan_group): the device
+// fg_group_clauses, goes to plan_group, one beside a phrase clause, with
+// fg_group_phrase_clauses `gphrase`, to plan_group_phrase): the device
 // subset -- the phrase is the query's only clause (`beside`, fg_phrase_clauses:
 // other clauses beside it go to plan_bool_phrase), facet clauses only with
 // `filters` (fg_filter_clauses; `nomatch`: they match no doc of the snapshot, so
@@ -364,7 +549,7 @@ int plan_group(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t
 // idfs summed in phrase order from 0.0 (a repeated term each time), times
 // (1 + K1).  Work items (k_phrase): groups of the lead list's chunks, as k_conj's.
 int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t nq_size, uint32_t n_segs,
-                PlanTables& h, int* phrase, bool beside, bool groups, bool filters, bool nomatch) {
+                PlanTables& h, int* phrase, bool beside, bool groups, bool filters, bool gphrase, bool nomatch) {
   *phrase = 0;
   const uint32_t b = q->q_off[i], e = q->q_off[i + 1], m = e - b;
   uint32_t n_clauses = 0, n_phr = 0, n_grp = 0;
@@ -400,6 +585,7 @@ int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_
   }
   if (n_grp) {
     *phrase = 1;
+    if (n_phr && gphrase) return plan_group_phrase(ix, q, i, nq_size, n_segs, h, nomatch);
     if (n_phr) return fail(FG_EUNSUPPORTED, "query %u: group clause beside a phrase clause", i);
     return plan_group(ix, q, i, nq_size, n_segs, h, filters, nomatch);
   }
@@ -462,9 +648,10 @@ int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_
 // that batch: plan_pieces plans a snapshot's queries in pieces)
 // qtime: the plan forms its scores at query time (some snapshot's statistics
 // changed since its build: DevPlan::feat), so the descriptors point at payloads
-// beside, groups, filters: fg_phrase_clauses, fg_group_clauses, fg_filter_clauses as the plan's creation read them
+// beside, groups, filters, gphrase: fg_phrase_clauses, fg_group_clauses, fg_filter_clauses, fg_group_phrase_clauses as
+// the plan's creation read them
 int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t n_segs, PlanTables& h,
-              uint32_t nq_size, bool qtime, bool beside, bool groups, bool filters) {
+              uint32_t nq_size, bool qtime, bool beside, bool groups, bool filters, bool gphrase) {
   if (!ix || !q || (q->n_queries && !q->q_off)) return fail(FG_EINVAL, "bad arguments");
   if (q->n_queries && q->q_off[q->n_queries] > q->q_off[0] && !q->terms) return fail(FG_EINVAL, "q_off without terms");
   if (q->f_off && q->n_queries && q->f_off[q->n_queries] > q->f_off[0] && !q->f_terms)
@@ -610,7 +797,7 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
     if (m > fg::kMaxTerms) return fail(FG_EUNSUPPORTED, "query %u has %u terms (> %u)", i, m, fg::kMaxTerms);
     if (q->phrase_len) {
       int phrase = 0;
-      if (int rc = plan_phrase(ix, q, i, nq_size, n_segs, h, &phrase, beside, groups, filters, q_nomatch[i] != 0)) return rc;
+      if (int rc = plan_phrase(ix, q, i, nq_size, n_segs, h, &phrase, beside, groups, filters, gphrase, q_nomatch[i] != 0)) return rc;
       if (phrase) continue;
     }
     if (q_nomatch[i]) continue;  // the facet clauses match nothing: no hits
@@ -829,7 +1016,8 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
   const bool beside = phrase_clauses_on.load(std::memory_order_relaxed) != 0;  // (read once per plan)
   const bool groups = group_clauses_on.load(std::memory_order_relaxed) != 0;
   const bool filters = filter_clauses_on.load(std::memory_order_relaxed) != 0;
-  if (S == 1) return plan_host(ixs[0], q, k, S, hs[0], nq1, qt, beside, groups, filters);  // (used in place: nothing to join)
+  const bool gphrase = group_phrase_clauses_on.load(std::memory_order_relaxed) != 0;
+  if (S == 1) return plan_host(ixs[0], q, k, S, hs[0], nq1, qt, beside, groups, filters, gphrase);  // (used in place: nothing to join)
   J.clear();
   const size_t nq = (size_t)S * nq1, nqt = nq * fg::kMaxTerms;
   for (auto* v : {&J.q_m, &J.lead, &J.ngroup, &J.q_tier}) v->resize(nq);
@@ -861,14 +1049,14 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
       qp.n_queries = b - a;
       qp.q_off = q->q_off + a;
       if (q->f_off) qp.f_off = q->f_off + a;
-      if ((rcs[p] = plan_host(ixs[p / pc.P], &qp, k, S, hs[p], nq1, qt, beside, groups, filters))) errs[p] = fg_last_error();
+      if ((rcs[p] = plan_host(ixs[p / pc.P], &qp, k, S, hs[p], nq1, qt, beside, groups, filters, gphrase))) errs[p] = fg_last_error();
       else put_slot(p);
     });
     for (uint32_t p = 0; p < n; ++p)
       if (rcs[p]) return fail(rcs[p], "snapshot %u: %s", p / pc.P, errs[p].c_str());
   } else {
     for (uint32_t s = 0; s < S; ++s) {
-      if (int rc = plan_host(ixs[s], q, k, S, hs[s], nq1, qt, beside, groups, filters)) {
+      if (int rc = plan_host(ixs[s], q, k, S, hs[s], nq1, qt, beside, groups, filters, gphrase)) {
         const std::string e = fg_last_error();
         return fail(rc, "snapshot %u: %s", s, e.c_str());
       }
@@ -904,6 +1092,7 @@ PlanTables& join_pieces(const Pieces& pc, std::vector<PlanTables>& hs, PlanTable
     for (WItem x : h.phrase) { x.q += vb; J.phrase.push_back(x); }
     for (WItem x : h.bphrase) { x.q += vb; J.bphrase.push_back(x); }
     for (WItem x : h.group) { x.q += vb; J.group.push_back(x); }
+    for (WItem x : h.gphrase) { x.q += vb; J.gphrase.push_back(x); }
     J.nf += h.nf;
   }
   // one bin geometry per batch query over the snapshots where it has work
@@ -1019,9 +1208,9 @@ void sort_sweep(std::vector<WItem>& items, bool conj, const PlanTables& t, uint3
 struct WorkList {
   std::vector<uint32_t> work_q, work_c, work_n;
   std::vector<uint64_t> cand_off;
-  uint64_t n_single = 0, n_conj = 0, n_main = 0, n_scan = 0, n_phrase = 0, n_bphrase = 0, n_group = 0;
+  uint64_t n_single = 0, n_conj = 0, n_main = 0, n_scan = 0, n_phrase = 0, n_bphrase = 0, n_group = 0, n_gphrase = 0;
   uint32_t xcd_first[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // DevPlan::xcd_first
-  uint64_t count() const { return n_main + n_scan + n_phrase + n_bphrase + n_group; }
+  uint64_t count() const { return n_main + n_scan + n_phrase + n_bphrase + n_group + n_gphrase; }
 };
 
 // k_conj's multi-list items (sorted) cut into the 8 XCDs' stretches by expected
@@ -1056,13 +1245,13 @@ void xcd_stretches(const PlanTables& t, WorkList& w) {
 int order_items(PlanTables& t, uint32_t nq, uint32_t k, WorkList& w) {
   if (t.f_woff[t.nf] * 4 > (8ull << 30)) return fail(FG_EUNSUPPORTED, "facet masks of this batch exceed 8 GiB");
   if (t.ch_f.size() > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "facet postings of this batch too large");
-  if (t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() > 0x7FFFFFFFull)
+  if (t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size() > 0x7FFFFFFFull)
     return fail(FG_EUNSUPPORTED, "batch too large (%zu work items)",
-                t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size());
+                t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size());
   sort_sweep(t.citems, true, t, nq);
   sort_sweep(t.ditems, false, t, nq);
   auto& items = t.items;
-  items.reserve(t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size());
+  items.reserve(t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size());
   items.insert(items.end(), t.citems.begin(), t.citems.end());
   w.n_conj = t.citems.size();
   items.insert(items.end(), t.ditems.begin(), t.ditems.end());
@@ -1081,12 +1270,16 @@ int order_items(PlanTables& t, uint32_t nq, uint32_t k, WorkList& w) {
   // k_group: the same sweep
   std::stable_sort(t.group.begin(), t.group.end(), [](const WItem& a, const WItem& b) { return a.key < b.key; });
   w.n_group = t.group.size();
-  const uint64_t chunks = w.count();  // work items (k_conj / k_disj, then k_scan, k_phrase, k_bphrase, k_group)
+  // k_gphrase: the same sweep
+  std::stable_sort(t.gphrase.begin(), t.gphrase.end(), [](const WItem& a, const WItem& b) { return a.key < b.key; });
+  w.n_gphrase = t.gphrase.size();
+  const uint64_t chunks = w.count();  // work items (k_conj / k_disj, then k_scan, k_phrase, k_bphrase, k_group, k_gphrase)
   if (chunks > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "batch too large (%llu work items)", (unsigned long long)chunks);
   items.insert(items.end(), t.scan.begin(), t.scan.end());
   items.insert(items.end(), t.phrase.begin(), t.phrase.end());
   items.insert(items.end(), t.bphrase.begin(), t.bphrase.end());
   items.insert(items.end(), t.group.begin(), t.group.end());
+  items.insert(items.end(), t.gphrase.begin(), t.gphrase.end());
   w.work_q.resize(chunks);
   w.work_c.resize(chunks);
   w.work_n.resize(chunks);
@@ -1282,6 +1475,7 @@ void fill_view(fg_plan* p, fg_index* const* ixs, PlanTables& t, const WorkList& 
   p->d.n_phrase = (uint32_t)w.n_phrase;
   p->d.n_bphrase = (uint32_t)w.n_bphrase;
   p->d.n_group = (uint32_t)w.n_group;
+  p->d.n_gphrase = (uint32_t)w.n_gphrase;
   p->d.n_single = (uint32_t)w.n_single;
   std::copy(w.xcd_first, w.xcd_first + 9, p->d.xcd_first);
   p->d.k = p->k;
@@ -1381,6 +1575,11 @@ int fg_group_clauses(int on) {
 int fg_filter_clauses(int on) {
   if (on < 0) return filter_clauses_on.load(std::memory_order_relaxed);
   return filter_clauses_on.exchange(on != 0 ? 1 : 0, std::memory_order_relaxed);
+}
+
+int fg_group_phrase_clauses(int on) {
+  if (on < 0) return group_phrase_clauses_on.load(std::memory_order_relaxed);
+  return group_phrase_clauses_on.exchange(on != 0 ? 1 : 0, std::memory_order_relaxed);
 }
 
 int fg_plan_tiered_slots(const fg_plan* p, uint32_t* out) {

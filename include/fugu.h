@@ -424,7 +424,8 @@ int fg_phrase_clauses(int on);
  * smallest.  A member the snapshot lacks is absent: the any-of group goes on
  * without it, the all-of group is absent as a whole.  Off: such a phrase_len
  * value is answered as before (FG_EINVAL "bad phrase_len").  On, outside the
- * subset (FG_EUNSUPPORTED): "group clause beside a phrase clause", "group with
+ * subset (FG_EUNSUPPORTED): "group clause beside a phrase clause" (unless
+ * fg_group_phrase_clauses(1) is set as well, below), "group with
  * facet filters" (unless fg_filter_clauses(1) is set as well), a group in
  * fg_model_batch, and a group in fg_count_batch unless fg_count_clauses(1) is
  * set (below: that switch alone decides for counts). */
@@ -447,6 +448,26 @@ int fg_group_clauses(int on);
  * fg_count_batch counts them, with or without facet clauses, under its own
  * switch fg_count_clauses (below) and consults none of these three. */
 int fg_filter_clauses(int on);
+
+/* A group clause BESIDE a phrase clause in one query (`e-mail (server OR host)`,
+ * `"new york" AND (pizza OR pasta)`: the shape fg_group_clauses refuses with
+ * "group clause beside a phrase clause") runs on the device (k_gphrase,
+ * DESIGN.md §18) when on != 0.  The contract of fg_phrase_clauses: process-wide,
+ * off by default, read when a plan is created; on: 1 / 0 sets it, < 0 only
+ * asks; returns the previous setting.  It matters only for a query that holds at
+ * least one group clause and at least one phrase clause while fg_group_clauses
+ * is on (so that the flags parse); fg_phrase_clauses is not consulted.  Off:
+ * every entry point answers as before.  On: every clause gives a doc a score or
+ * "absent" -- a term as everywhere, a phrase as fg_phrase_clauses', a group as
+ * fg_group_clauses' -- and the clauses join as the term clauses of `occur` do,
+ * with those switches' costs among the Musts and their per-snapshot absence
+ * rules; FG_MAX_TERMS holds over all members and phrase terms together; several
+ * phrase and several group clauses may stand in one query.  Still
+ * FG_EUNSUPPORTED: facet clauses on such a query ("group and phrase clauses with
+ * facet filters", whatever fg_filter_clauses says), a snapshot without positions
+ * ("snapshot built without positions"), and fg_model_batch.  fg_count_batch is
+ * untouched (fg_count_clauses). */
+int fg_group_phrase_clauses(int on);
 
 /* Plan a batch: host-side query planning (tantivy Weight creation: terms
  * ordered by cost, query/intersection.rs) and upload of the plan to HBM.

@@ -47,7 +47,9 @@
  * process-wide, off by default), with which they count phrase and group queries
  * as fg_db_search* run them.  Queries outside the device subset
  * (grouping while that switch is off or deeper than one level, a phrase beside other
- * clauses while that switch is off, a phrase or a group with filters unless
+ * clauses while that switch is off, a group beside a phrase -- `e-mail (server OR host)`
+ * -- unless fg_group_phrase_clauses(1) is set as well (fugu.h; process-wide, off by
+ * default: k_gphrase), a phrase or a group with filters unless
  * fg_filter_clauses(1) is set (fugu.h; process-wide, off by default), slop / prefix
  * suffixes on a quoted literal, field:,
  * boosts, a text query with filters that parse to no facet term) return
