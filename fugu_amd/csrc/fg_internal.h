@@ -294,6 +294,11 @@ constexpr uint32_t kGrpClauseShift = 8, kGrpMemberShift = 12;
 // A slot of k_gphrase (a group clause beside a phrase clause: fg_group_phrase_clauses,
 // DESIGN.md §18): q_m, the q_clause row and work_n as k_group's, with phrase clauses
 // (kClPhrase) among the clauses; DevPlan::n_gphrase describes the rows.
+// A slot of k_mgroup (a group with phrase members: fg_group_member_phrases, DESIGN.md
+// §19): the same, a group's MEMBERS being runs of rows -- one row a term, two or
+// more a phrase laid out as a phrase clause's rows.  DevPlan::q_member holds, per
+// clause, the mask of the clause's rows that begin a member (bit r: row cl_first + r);
+// a pass's member (work_n, kGrpMemberShift) counts members, not rows.
 
 // Rank words (DevIndex::rank): one u64 per 32 docs, the low half the docs'
 // presence bits, the high half the number of the term's postings before the
@@ -766,6 +771,13 @@ struct DevPlan {
                                 // q_wt / q_wn at its first row, and q_ub = (text weight, name weight, 0, ...) over
                                 // its rows (a field's entry 0.0 where the phrase cannot match in the snapshot), so
                                 // group_bound's sum over a clause's rows bounds the phrase's score
+  uint32_t n_mgroup;            // k_mgroup work items (queries with a group that holds a phrase member:
+                                // fg_group_member_phrases), after the k_gphrase items, work_n as k_group's with
+                                // the pass's member counted in members.  The rows as k_gphrase's; a phrase
+                                // MEMBER's rows are a phrase clause's (anchor first, q_pterm / q_ppos, the field
+                                // weights at its first row, q_ub = (text weight, name weight, 0, ...))
+  const uint32_t* q_member;     // [nq * kMaxTerms] per clause of such a slot: the mask of its rows that begin a
+                                // member; empty without fg_group_member_phrases
   // Multi-snapshot plans (several segments / doc shards / namespaces of one
   // device in ONE launch per kernel): query slot v = s * seg_nq + q is query q
   // of the batch on snapshot segs[s]; every per-query array above is indexed by
@@ -1077,6 +1089,7 @@ hipError_t launch_phrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 hipError_t launch_bphrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 hipError_t launch_group(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 hipError_t launch_gphrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
+hipError_t launch_mgroup(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 // out_shard != nullptr: the merged select of a multi-snapshot plan (one list per batch query)
 hipError_t launch_final(const DevPlan& pl, float* out_score, uint32_t* out_doc, uint32_t* out_n, hipStream_t s,
                         uint32_t* out_shard = nullptr);

@@ -394,7 +394,9 @@ class DocStore {
 // `(a AND b)`, `(+a +b)` all-of, bare / `+` / `-` / an operand of the uniform
 // forms -- and mixed infix `a AND b OR c AND d`, where AND binds tighter
 // (tantivy-query-grammar 0.24): Should clauses, an AND-run of several words an
-// all-of group.
+// all-of group.  With fg_group_member_phrases(1) as well a group
+// member or an AND-run's operand may be a word of several tokens or a quoted
+// literal: a phrase member (`(e-mail OR email) server`, `e-mail AND server OR host`).
 // Anything else (mixed AND / OR and parentheses while that switch is off, field:,
 // slop, boosts, ranges, a
 // query of MustNot clauses only) is FG_EUNSUPPORTED: the reference host runs tantivy.
@@ -414,7 +416,9 @@ bool is_special(char c) {
 // each token's position offset from the first: a token the analyzer drops in
 // between leaves a hole -- PhraseQuery::new_with_offset).
 // A group (fg_group_clauses): `terms` are its members, joined any-of (a nested
-// Should-only BooleanQuery) or all-of (a nested Must-only one); every pos is 0.
+// Should-only BooleanQuery) or all-of (a nested Must-only one); every pos is 0 --
+// with fg_group_member_phrases a member may be a phrase: a pos 0 begins a member, a
+// pos > 0 continues the member before it (the ABI's rows, fugu.h).
 struct Clause {
   uint8_t occur = FG_OCCUR_SHOULD;
   std::vector<std::string> terms;
@@ -443,15 +447,62 @@ int group_word(std::string_view w, std::string& tok, std::string& why) {
   return FG_OK;
 }
 
+// One member of a group appended to cl: its tokens with their offsets from the first, so an offset 0 begins a
+// member.  `members` (fg_group_member_phrases): a word may analyze to several tokens and a literal may be `quoted`
+// (w is then its inside) -- a phrase member; off, a member is a plain word of one token, as before.
+int group_member(std::string_view w, bool quoted, bool members, Clause& cl, std::string& why) {
+  if (!members) {
+    std::string tok;
+    if (int rc = group_word(w, tok, why)) return rc;
+    cl.terms.push_back(std::move(tok));
+    cl.pos.push_back(0);
+    return FG_OK;
+  }
+  if (!quoted) {
+    if (is_operator_word(w)) { why = "operator outside the supported forms"; return FG_EUNSUPPORTED; }
+    for (size_t c = 0; c < w.size(); ++c)
+      if (is_special(w[c]) && !(w[c] == '-' && c >= 1)) {
+        why = w[c] == '"' ? "query syntax beyond bare/+/-/AND/OR terms and plain quoted phrases (slop, prefix, boost)"
+                          : w[c] == '(' || w[c] == ')' ? "a group inside a group" : "query syntax beyond bare/+/-/AND/OR terms";
+        return FG_EUNSUPPORTED;
+      }
+  } else if (w.find('\\') != std::string_view::npos) {
+    why = "escape inside a quoted literal";
+    return FG_EUNSUPPORTED;
+  }
+  std::vector<std::string> toks;
+  std::vector<uint32_t> pos;
+  analyze(w, toks, &pos);
+  if (toks.empty()) { why = "a term analyzes to no token"; return FG_EUNSUPPORTED; }
+  for (size_t j = 0; j < toks.size(); ++j) {
+    cl.terms.push_back(std::move(toks[j]));
+    cl.pos.push_back(pos[j] - pos[0]);
+  }
+  return FG_OK;
+}
+
 // The inside of a parenthesised group: one uniform form over plain words --
 // `a b c` / `a OR b` any-of, `a AND b` / `+a +b` all-of; one word is that word
 // (cl.group stays 0).  `-`, mixed prefixes, mixed operators: `why`.
-int parse_group(std::string_view body, Clause& cl, std::string& why) {
+// `members` (fg_group_member_phrases): a member may be a word of several tokens or a
+// quoted literal (a quote runs to its closing quote, white space and parentheses
+// included; nothing may follow the closing quote inside its word); a body of one
+// literal is that literal, a term or a phrase clause.
+int parse_group(std::string_view body, Clause& cl, std::string& why, bool members) {
   std::vector<std::string_view> ws;
+  auto blank = [](char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r'; };
   for (size_t i = 0; i < body.size();) {
-    while (i < body.size() && (body[i] == ' ' || body[i] == '\t' || body[i] == '\n' || body[i] == '\r')) ++i;
+    while (i < body.size() && blank(body[i])) ++i;
     const size_t s = i;
-    while (i < body.size() && !(body[i] == ' ' || body[i] == '\t' || body[i] == '\n' || body[i] == '\r')) ++i;
+    while (i < body.size() && !blank(body[i])) {
+      if (members && body[i] == '"') {
+        const size_t close = body.find('"', i + 1);
+        if (close == std::string_view::npos) { why = "unterminated quoted literal"; return FG_EUNSUPPORTED; }
+        i = close + 1;
+      } else {
+        ++i;
+      }
+    }
     if (i > s) ws.push_back(body.substr(s, i - s));
   }
   if (ws.empty()) { why = "an empty group"; return FG_EUNSUPPORTED; }
@@ -483,12 +534,18 @@ int parse_group(std::string_view body, Clause& cl, std::string& why) {
     if (has_and && has_or) { why = "mixed AND / OR inside a group"; return FG_EUNSUPPORTED; }
   }
   for (std::string_view w : words) {
-    std::string tok;
-    if (int rc = group_word(w, tok, why)) return rc;
-    cl.terms.push_back(std::move(tok));
-    cl.pos.push_back(0);
+    bool quoted = false;
+    if (members && !w.empty() && w[0] == '"') {
+      if (w.size() < 2 || w.find('"', 1) != w.size() - 1) {
+        why = "query syntax beyond bare/+/-/AND/OR terms and plain quoted phrases (slop, prefix, boost)";
+        return FG_EUNSUPPORTED;
+      }
+      w = w.substr(1, w.size() - 2);
+      quoted = true;
+    }
+    if (int rc = group_member(w, quoted, members, cl, why)) return rc;
   }
-  cl.group = cl.terms.size() > 1 ? kind : 0;
+  cl.group = words.size() > 1 ? kind : 0;  // (one literal is that literal: a term or a phrase clause)
   return FG_OK;
 }
 
@@ -500,6 +557,7 @@ int parse_group(std::string_view body, Clause& cl, std::string& why) {
 int parse_clauses(std::string_view q, std::vector<Clause>& out, std::string& why) {
   out.clear();
   const bool groups = fg_group_clauses(-1) > 0;
+  const bool members = groups && fg_group_member_phrases(-1) > 0;  // a group may hold phrase members
   struct Item { std::string_view body; bool quoted; bool prefixed; uint8_t occur; bool group = false; };
   std::vector<Item> items;
   auto space = [](char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r'; };
@@ -511,11 +569,22 @@ int parse_clauses(std::string_view q, std::vector<Clause>& out, std::string& why
     if (groups) {  // a parenthesised group, bare or behind + / -, runs to its closing parenthesis
       const size_t open = s + ((q[s] == '+' || q[s] == '-') && s + 1 < q.size() ? 1 : 0);
       if (q[open] == '(') {
-        const size_t close = q.find(')', open + 1);
+        size_t close = q.find(')', open + 1);
+        if (members) {  // a quote runs to its closing quote: a parenthesis inside it is literal
+          bool nested = false;
+          for (close = open + 1; close < q.size() && q[close] != ')'; ++close) {
+            if (q[close] == '(') nested = true;
+            if (q[close] != '"') continue;
+            close = q.find('"', close + 1);
+            if (close == std::string_view::npos) { why = "unterminated quoted literal"; return FG_EUNSUPPORTED; }
+          }
+          if (close >= q.size()) close = std::string_view::npos;
+          else if (nested) { why = "a group inside a group"; return FG_EUNSUPPORTED; }
+        }
         if (close == std::string_view::npos) { why = "unterminated group"; return FG_EUNSUPPORTED; }
         const std::string_view body = q.substr(open + 1, close - open - 1);
-        if (body.find('(') != std::string_view::npos) { why = "a group inside a group"; return FG_EUNSUPPORTED; }
-        if (body.find('"') != std::string_view::npos) { why = "a quoted literal inside a group"; return FG_EUNSUPPORTED; }
+        if (!members && body.find('(') != std::string_view::npos) { why = "a group inside a group"; return FG_EUNSUPPORTED; }
+        if (!members && body.find('"') != std::string_view::npos) { why = "a quoted literal inside a group"; return FG_EUNSUPPORTED; }
         if (close + 1 < q.size() && !space(q[close + 1])) {
           why = "query syntax beyond bare/+/-/AND/OR terms after a group (boost, slop)";
           return FG_EUNSUPPORTED;
@@ -584,7 +653,7 @@ int parse_clauses(std::string_view q, std::vector<Clause>& out, std::string& why
       for (size_t x = w; x <= last; x += 2) {
         if (items[x].prefixed) { why = "query syntax beyond bare/+/-/AND/OR terms"; return FG_EUNSUPPORTED; }
         if (last > w && items[x].group) { why = "a group inside a group"; return FG_EUNSUPPORTED; }
-        if (last > w && items[x].quoted) { why = "a quoted literal inside a group"; return FG_EUNSUPPORTED; }
+        if (last > w && items[x].quoted && !members) { why = "a quoted literal inside a group"; return FG_EUNSUPPORTED; }
       }
       Item it = items[w];
       it.occur = FG_OCCUR_SHOULD;
@@ -611,14 +680,10 @@ int parse_clauses(std::string_view q, std::vector<Clause>& out, std::string& why
       Clause cl;
       cl.occur = it.occur;
       if (it.group) {
-        if (int rc = parse_group(w, cl, why)) return rc;
-      } else {  // an AND-run of plain words
-        for (size_t x = runs[r].first; x <= runs[r].second; x += 2) {
-          std::string tok;
-          if (int rc = group_word(items[x].body, tok, why)) return rc;
-          cl.terms.push_back(std::move(tok));
-          cl.pos.push_back(0);
-        }
+        if (int rc = parse_group(w, cl, why, members)) return rc;
+      } else {  // an AND-run of plain words (fg_group_member_phrases: of literals)
+        for (size_t x = runs[r].first; x <= runs[r].second; x += 2)
+          if (int rc = group_member(items[x].body, items[x].quoted, members, cl, why)) return rc;
         cl.group = kGroupAll;
       }
       positive |= cl.occur != FG_OCCUR_MUST_NOT;
@@ -1397,6 +1462,9 @@ int count_query(Namespace& ns, const char* query, const std::vector<std::string>
         if (c.group) return hfail(FG_EUNSUPPORTED, "query outside the device subset: group clause in a count query");
         if (c.terms.size() > 1) return hfail(FG_EUNSUPPORTED, "query outside the device subset: phrase clause in a count query");
       }
+      // a group with a phrase member (fg_group_member_phrases) is not counted on the device
+      if (c.group && std::any_of(c.pos.begin(), c.pos.end(), [](uint32_t p) { return p != 0; }))
+        return hfail(FG_EUNSUPPORTED, "query outside the device subset: group with phrase members in a count query");
       any_phrase |= c.terms.size() > 1;
       const uint32_t flag = c.group == kGroupAny ? FG_CLAUSE_ANY : c.group == kGroupAll ? FG_CLAUSE_ALL : 0u;
       for (size_t j = 0; j < c.terms.size(); ++j) {  // as search_hits writes them
@@ -2956,11 +3024,14 @@ int fg_parse_query_clauses(const char* query, char* out, size_t cap, size_t* len
     if (i) o.push_back('\n');
     o.push_back((char)('0' + cls[i].occur));
     o.push_back(':');
-    if (cls[i].group) {  // "(a | b)" any-of, "(a & b)" all-of
+    if (cls[i].group) {  // "(a | b)" any-of, "(a & b)" all-of; a phrase member "(e@0 mail@1 | email)"
       o.push_back('(');
+      const std::vector<uint32_t>& pp = cls[i].pos;
       for (size_t j = 0; j < cls[i].terms.size(); ++j) {
-        if (j) o += cls[i].group == kGroupAny ? " | " : " & ";
+        const bool phrase = pp[j] != 0 || (j + 1 < pp.size() && pp[j + 1] != 0);
+        if (j) o += pp[j] != 0 ? " " : cls[i].group == kGroupAny ? " | " : " & ";
         o += cls[i].terms[j];
+        if (phrase) o += "@" + std::to_string(pp[j]);
       }
       o.push_back(')');
       continue;

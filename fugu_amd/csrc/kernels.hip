@@ -3114,6 +3114,303 @@ __global__ __launch_bounds__(kThreads, 4) void k_gphrase(DevIndex ix0, DevPlan p
   flush_candidates(pl, q, sh.g.s.buf, sh.g.s.n_buf, sh.g.s.thr, sh.g.s.scratch);
 }
 
+// ---------------------------------------------------------------- k_mgroup
+// Queries with a group that holds a PHRASE MEMBER (`(e-mail OR email) server`:
+// fg_group_member_phrases).  The slot's clause table, rows and
+// passes are k_gphrase's; a group's members are runs of its rows (sh.mm: per
+// clause, the mask of the rows that begin a member), one row a term, two or more a
+// phrase laid out as a phrase clause's rows.  A pass (pc, pm) sweeps the list of
+// member pm's first row: a term's, or a phrase's anchor's.  Per lead chunk, kRound
+// docs between truncations:
+//  (a) one LANE per lead doc walks clause, member, row.  It scores term members
+//      itself; of a phrase (a member or a clause) it only asks whether the doc
+//      holds every term.  One the doc cannot match is an absent member or clause
+//      and the lane goes on; with no phrase left open it finishes both joins and
+//      appends the key.  A doc that the known parts keep and that holds every
+//      term of some phrase is queued in LDS with its lead posting: also for a
+//      phrase member before the pass member in the pass's any-of group, and for a
+//      Should clause before the pass clause in a pass without a Must -- whether
+//      that phrase matches decides which pass owns the doc;
+//  (b) one WAVE per queued doc redoes the walk: every lane forms the term scores
+//      by the instructions of (a), the wave counts each phrase on the forward
+//      index (the name field only where the snapshot has one).
+// A doc leaves only with the first (clause, member) pass that matches it -- the
+// pass member itself has to match --, so k_final's keys stay unique.
+// Pruning (exact): k_group's chunk skip with mgroup_bound: a phrase member is
+// bounded by its two q_ub rows summed as the score sums the two fields, members
+// combine as the score combines them, and a pass that leads from a phrase bounds
+// the lead by the phrase's weights, never by cmax.
+struct MGroupShared {
+  GroupShared g;               // k_group's tables: the clause table and the per-row tables
+  uint32_t mm[kMaxTerms];      // per clause: the rows that begin a member (bit r: row cl_first + r)
+  uint32_t pterm[kMaxTerms];   // the phrases' terms as vocabulary ids (DevIndex::fwd)
+  uint32_t ppos[kMaxTerms];    // ... and their offsets in their phrase
+  uint64_t queue[kRound];      // stage (b)'s docs: lead posting << 32 | doc
+  uint32_t n_q;
+};
+
+// the end of the member that begins at row x of a clause with rows [t0, t1) and member mask mk
+__device__ inline uint32_t mgroup_member_end(uint32_t mk, uint32_t t0, uint32_t t1, uint32_t x) {
+  const uint32_t rest = (mk >> (x - t0)) >> 1;
+  return rest ? min(x + (uint32_t)__ffs((int)rest), t1) : t1;
+}
+
+// The phrase over rows [r0, r1) (the anchor first) in doc d: 0 absent, 1 it matches (s: its score, text then name
+// from 0.0), 2 the doc holds every term (kWave = false only: the positions can tell).  pos: the anchor's posting when
+// the pass leads from it, else kInvalid.
+template <bool kWave>
+__device__ inline uint32_t mgroup_phrase(const DevIndex& ix, const MGroupShared& sh, uint32_t r0, uint32_t r1, uint32_t pos,
+                                         bool name, uint32_t d, float& s) {
+  const GroupShared& g = sh.g;
+  s = 0.0f;
+  if constexpr (!kWave) {
+    for (uint32_t x = r0; x < r1; ++x)
+      if ((x != r0 || pos == kInvalid) && !term_has_doc(ix, g.tmeta[x], g.toff[x], g.tdir[x], d)) return 0u;
+    return 2u;
+  } else {
+  const uint32_t n = r1 - r0, lane = lane_id();
+  uint32_t p = kInvalid;
+  if (lane < n) {
+    const uint32_t x = r0 + lane;
+    p = lane == 0 && pos != kInvalid ? pos : posting_pos_at(ix, g.tmeta[x], g.toff[x], g.tdir[x], d);
+  }
+  if (n == 0 || __ballot(p != kInvalid) != (1ull << n) - 1ull) return 0u;
+  const uint64_t p0 = g.toff[r0] + __builtin_amdgcn_readfirstlane(p);
+  uint32_t v = ix.tfn[p0];
+  if (ix.tfn_name) v |= (uint32_t)ix.tfn_name[p0] << 16;
+  v = __builtin_amdgcn_readfirstlane(v);
+  uint32_t span = 0;  // the phrase's largest offset
+  for (uint32_t j = r0; j < r1; ++j) span = max(span, sh.ppos[j]);
+  uint32_t ct = 0, cn = 0;
+  if (v & 0xFFu) ct = phrase_count_at(ix.fwd, ix.fwd_off[d], ix.fwd_off[d + 1], sh.pterm + r0, sh.ppos + r0, n, span);
+  if (name && ((v >> 16) & 0xFFu))
+    cn = phrase_count_at(ix.fwd_name, ix.fwd_off_name[d], ix.fwd_off_name[d + 1], sh.pterm + r0, sh.ppos + r0, n, span);
+  if (ct) s += field_score(ct, (v >> 8) & 0xFFu, g.wt[r0], g.cache);
+  if (cn) s += field_score(cn, v >> 24, g.wn[r0], g.cache + 256);
+  return (ct | cn) != 0 ? 1u : 0u;
+  }
+}
+
+// The clause table over doc d (the lead list's posting i) for pass (pc, pm): whether the doc is a hit of this pass, and
+// its score.  kWave = false: one lane; a phrase whose terms the doc all holds is left open (`open`: the result says
+// only that the known parts do not drop the doc).  kWave = true: the whole wave on one doc (d, i uniform), phrases counted.
+template <bool kWave>
+__device__ inline bool mgroup_doc(const DevIndex& ix, const MGroupShared& sh, uint32_t ncl, uint32_t nt, bool must,
+                                  uint32_t pc, uint32_t pm, bool name, uint32_t d, uint32_t i, bool& open, float& sc) {
+  const GroupShared& g = sh.g;
+  float req = 0.0f, oth = 0.0f, opt = 0.0f;
+  uint32_t nm = 0;
+  bool any = false, keep = true;
+  open = false;
+  for (uint32_t ci = 0; ci < ncl && keep; ++ci) {
+    const uint32_t cw = g.cl[ci], oc = cl_occur(cw), t0 = cl_first(cw), t1 = min(t0 + cl_terms(cw), nt);
+    float a = 0.0f, b = 0.0f;
+    bool on = (cw & kClAll) != 0, unk = false;  // unk: a phrase of the clause is open
+    if (cw & kClPhrase) {
+      const uint32_t st = mgroup_phrase<kWave>(ix, sh, t0, t1, ci == pc ? i : kInvalid, name, d, a);
+      on = st == 1u;
+      unk = st == 2u;
+      if (ci == pc && st == 0u) keep = false;  // the pass clause does not match
+    } else {
+      const uint32_t mk = sh.mm[ci];
+      for (uint32_t x = t0, mi = 0; x < t1; ++mi) {
+        const uint32_t xe = mgroup_member_end(mk, t0, t1, x);
+        const bool lead = ci == pc && mi == pm;
+        float s = 0.0f;
+        uint32_t st;
+        if (xe - x > 1) st = mgroup_phrase<kWave>(ix, sh, x, xe, lead ? i : kInvalid, name, d, s);
+        else st = group_member(ix, g, x, d, lead ? i : kInvalid, s) ? 1u : 0u;
+        x = xe;
+        if (lead && st == 0u) keep = false;  // the pass member does not match: not this pass's doc
+        if (cw & kClAll) {
+          if (st == 0u) { on = false; unk = false; break; }
+          if (st == 2u) { unk = true; continue; }
+          if (mi < 2) a = mi == 0 ? s : a + s;
+          else b = b + s;
+        } else if (st == 2u) {
+          unk = true;  // (an earlier member of the pass's group: whether it matches decides the pass)
+        } else if (st) {
+          if ((cw & kClAny) && ci == pc && mi < pm) keep = false;  // an earlier member's pass has the doc
+          a = (cw & kClAny) ? a + s : s;
+          on = true;
+        }
+      }
+    }
+    if (unk) {
+      open = true;
+      if (!on || (cw & (kClAll | kClPhrase))) continue;  // whether the clause matches is not known: it drops no doc
+    }
+    const float cs = (cw & kClAll) ? 0.0f + (a + b) : a;
+    if (oc == kClMust) {
+      if (!on) keep = false;
+      else if (nm == 0) req = cs;
+      else if (nm == 1) req = req + cs;
+      else oth = oth + cs;
+      ++nm;
+    } else if (oc == kClMustNot) {
+      if (on) keep = false;
+    } else if (!must && ci <= pc && on != (ci == pc)) {
+      keep = false;  // an earlier pass's doc, or the pass clause does not match
+    } else if (on) {
+      opt = opt + cs;
+      any = true;
+    }
+  }
+  sc = opt;
+  if (must) {
+    if (nm > 1) req = req + oth;
+    sc = 0.0f + req;
+    if (any) sc = sc + opt;
+  }
+  return keep;
+}
+
+// The score sum over upper bounds for pass (pc, pm); lead_ub bounds the lead member when it is a term (uniform)
+__device__ inline float mgroup_bound(const MGroupShared& sh, uint32_t ncl, uint32_t nt, bool must, uint32_t pc,
+                                     uint32_t pm, float lead_ub) {
+  const GroupShared& g = sh.g;
+  float req = 0.0f, oth = 0.0f, opt = 0.0f;
+  uint32_t nm = 0;
+  for (uint32_t ci = 0; ci < ncl; ++ci) {
+    const uint32_t cw = g.cl[ci], oc = cl_occur(cw), t0 = cl_first(cw), t1 = min(t0 + cl_terms(cw), nt);
+    if (oc == kClMustNot || (!must && ci < pc)) continue;  // excluding, or absent in this pass's docs
+    const uint32_t mk = (cw & kClPhrase) ? 1u : sh.mm[ci];
+    float a = 0.0f, b = 0.0f;
+    for (uint32_t x = t0, mi = 0; x < t1; ++mi) {
+      const uint32_t xe = mgroup_member_end(mk, t0, t1, x);
+      // a phrase: its two field weights summed as its score sums the fields; a term: its scaled tmaxs, the lead's chunk
+      const float u = xe - x > 1 ? (0.0f + g.ub[x]) + g.ub[x + 1] : (ci == pc && mi == pm ? lead_ub : g.ub[x]);
+      x = xe;
+      if ((cw & kClAny) && ci == pc && mi < pm) continue;  // absent in this pass's docs
+      if (cw & kClAll) {
+        if (mi < 2) a = mi == 0 ? u : a + u;
+        else b = b + u;
+      } else {
+        a = (cw & kClAny) ? a + u : u;
+      }
+    }
+    const float cb = (cw & kClAll) ? 0.0f + (a + b) : a;
+    if (oc == kClMust) {
+      if (nm == 0) req = cb;
+      else if (nm == 1) req = req + cb;
+      else oth = oth + cb;
+      ++nm;
+    } else {
+      opt = opt + cb;
+    }
+  }
+  if (!must) return opt;
+  if (nm > 1) req = req + oth;
+  return (0.0f + req) + opt;
+}
+
+template <bool kMulti>
+__global__ __launch_bounds__(kThreads, 4) void k_mgroup(DevIndex ix0, DevPlan pl) {
+  __shared__ MGroupShared sh;
+  const uint32_t tid = threadIdx.x;
+  // after the k_gphrase items
+  const uint32_t w = pl.total_chunks + pl.n_scan + pl.n_phrase + pl.n_bphrase + pl.n_group + pl.n_gphrase + blockIdx.x;
+  const uint32_t q = pl.work_q[w];
+  const DevIndex ix = kMulti ? seg_index(pl, __builtin_amdgcn_readfirstlane(q / pl.seg_nq)) : ix0;
+  const uint32_t ql = kMulti ? __builtin_amdgcn_readfirstlane(q % pl.seg_nq) : q;
+  const uint32_t chunk0 = pl.work_c[w];
+  const uint32_t wn = pl.work_n[w];
+  const uint32_t nchunk = wn & ((1u << kGrpClauseShift) - 1u);
+  const uint32_t K = pl.k;
+  uint64_t* gthr = &pl.thresh[ql];
+  const uint64_t thr0 = pl.q_thr0[q];  // the plan's starting threshold (0: none)
+  const uint32_t qm = pl.q_m[q];
+  const uint32_t ncl = min(qm_terms(qm), kMaxTerms), nt = min(qm_phrase_terms(qm), kMaxTerms);
+  if (ncl == 0 || nt == 0) return;  // (never planned; uniform)
+  const uint32_t pc = min((wn >> kGrpClauseShift) & 15u, ncl - 1);
+  const size_t row = (size_t)q * kMaxTerms;
+  if (tid < nt) {
+    const uint32_t t = pl.q_terms[row + tid];
+    sh.g.tmeta[tid] = ix.tmeta[t];
+    sh.g.tdir[tid] = ix.dir_off[t];
+    sh.g.toff[tid] = ix.off[t];
+    sh.g.wt[tid] = pl.q_wt[row + tid];
+    sh.g.wn[tid] = pl.q_wn[row + tid];
+    sh.g.ub[tid] = pl.q_ub[row + tid];
+    sh.pterm[tid] = pl.q_pterm[row + tid];
+    sh.ppos[tid] = pl.q_ppos[row + tid];
+  }
+  if (tid < ncl) {
+    sh.g.cl[tid] = pl.q_clause[row + tid];
+    sh.mm[tid] = pl.q_member[row + tid] | 1u;  // (a clause's first row begins a member)
+  }
+  for (uint32_t i = tid; i < 512u; i += kThreads) sh.g.cache[i] = ix.cache[i];
+  if (tid == 0) {
+    sh.g.s.n_buf = 0;
+    sh.n_q = 0;
+    sh.g.s.thr = start_threshold(pl, thr0, ql, gthr);
+  }
+  __syncthreads();
+  const bool must = cl_occur(sh.g.cl[0]) == kClMust;  // (the Musts stand first)
+  const uint32_t pcw = sh.g.cl[pc];
+  // the lead: the first row of member pm of clause pc (a phrase's anchor)
+  const uint32_t pt0 = min(cl_first(pcw), nt - 1), pt1 = min(pt0 + max(cl_terms(pcw), 1u), nt);
+  const uint32_t pmk = (pcw & kClPhrase) ? 1u : sh.mm[pc];
+  const uint32_t pm_asked = (wn >> kGrpMemberShift) & 15u;
+  uint32_t li = pt0, pm = 0;
+  for (uint32_t xe = mgroup_member_end(pmk, pt0, pt1, li); pm < pm_asked && xe < pt1; xe = mgroup_member_end(pmk, pt0, pt1, li)) {
+    li = xe;
+    ++pm;
+  }
+  const bool lead_phrase = mgroup_member_end(pmk, pt0, pt1, li) - li > 1;
+  const uint32_t lead = pl.q_terms[row + li];
+  const uint64_t base = sh.g.toff[li];
+  const uint32_t df = (uint32_t)(ix.off[lead + 1] - base);
+  const float* __restrict__ cmax = ix.cmax + ix.coff[lead];
+  const float rup = pl.q_rup[row + li];
+  const bool name = ix.tfn_name != nullptr && ix.fwd_off_name != nullptr;
+  for (uint32_t c = 0; c < nchunk; ++c) {
+    const uint32_t i0 = (chunk0 + c) * kChunk;
+    if (i0 >= df) break;
+    // the chunk's bound against the threshold (uniform: the threshold is read after a barrier); a lead phrase is
+    // bounded by its weights inside mgroup_bound, never by the anchor's chunk maximum
+    const float lead_ub = lead_phrase ? 0.0f : fminf(cmax[chunk0 + c] * rup, sh.g.ub[li]);
+    const float bound = mgroup_bound(sh, ncl, nt, must, pc, pm, lead_ub);
+    if (make_key(inflate_bound(bound), 0u) < sh.g.s.thr) continue;
+    for (uint32_t r0 = 0; r0 < kChunk; r0 += kRound) {
+      const uint64_t thr = sh.g.s.thr;
+      // (a) a lane per lead doc
+      for (uint32_t j = 0; j < kRound / kThreads; ++j) {
+        const uint32_t i = i0 + r0 + j * kThreads + tid;
+        bool keep = i < df, open = false;
+        uint32_t d = 0;
+        float sc = 0.0f;
+        if (keep) {
+          d = ix.doc[base + i];
+          keep = doc_alive(ix, d);
+        }
+        if (keep) keep = mgroup_doc<false>(ix, sh, ncl, nt, must, pc, pm, name, d, i, open, sc);
+        const uint64_t key = make_key(sc, d);
+        wave_append(keep && !open && key >= thr, key, sh.g.s.buf, &sh.g.s.n_buf, kBufD);
+        wave_append(keep && open, ((uint64_t)i << 32) | d, sh.queue, &sh.n_q, kRound);
+      }
+      __syncthreads();
+      // (b) a wave per queued doc
+      const uint32_t nsv = min(sh.n_q, kRound);
+      for (uint32_t x = wave_id(); x < nsv; x += kThreads / 64) {
+        const uint64_t e = sh.queue[x];
+        const uint32_t d = __builtin_amdgcn_readfirstlane((uint32_t)e);
+        const uint32_t i = __builtin_amdgcn_readfirstlane((uint32_t)(e >> 32));
+        bool open = false;
+        float sc = 0.0f;
+        const bool keep = mgroup_doc<true>(ix, sh, ncl, nt, must, pc, pm, name, d, i, open, sc);
+        const uint64_t key = make_key(sc, d);
+        wave_append(lane_id() == 0 && keep && key >= thr, key, sh.g.s.buf, &sh.g.s.n_buf, kBufD);
+      }
+      __syncthreads();
+      if (tid == 0) sh.n_q = 0;
+      scan_truncate(sh.g.s, K, kTrunc, gthr, false, pl.pub_mask, pl, ql);
+    }
+    scan_truncate(sh.g.s, K, K, gthr, true, pl.pub_mask, pl, ql);
+  }
+  flush_candidates(pl, q, sh.g.s.buf, sh.g.s.n_buf, sh.g.s.thr, sh.g.s.scratch);
+}
+
 // ---------------------------------------------------------------- k_final
 // Dynamic LDS (80 KB: 2 workgroups per CU): candidate keys, the k winners,
 // the radix histogram.  Keeps 16-B alignment of the dynamic base (no static
@@ -3473,6 +3770,13 @@ hipError_t launch_gphrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s) 
   if (pl.n_gphrase == 0) return hipSuccess;
   if (pl.segs) k_gphrase<true><<<pl.n_gphrase, kThreads, 0, s>>>(ix, pl);
   else k_gphrase<false><<<pl.n_gphrase, kThreads, 0, s>>>(ix, pl);
+  return hipGetLastError();
+}
+
+hipError_t launch_mgroup(const DevIndex& ix, const DevPlan& pl, hipStream_t s) {
+  if (pl.n_mgroup == 0) return hipSuccess;
+  if (pl.segs) k_mgroup<true><<<pl.n_mgroup, kThreads, 0, s>>>(ix, pl);
+  else k_mgroup<false><<<pl.n_mgroup, kThreads, 0, s>>>(ix, pl);
   return hipGetLastError();
 }
 

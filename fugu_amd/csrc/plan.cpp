@@ -32,6 +32,8 @@ std::atomic<int> filter_clauses_on{0};
 // fg_group_phrase_clauses: queries with a group clause beside a phrase clause run on the device (k_gphrase); the
 // same contract
 std::atomic<int> group_phrase_clauses_on{0};
+// fg_group_member_phrases: a group may hold phrase members (k_mgroup); the same contract
+std::atomic<int> group_member_phrases_on{0};
 
 // stable LSD radix sort of `a` by its bits 32..63 (three 11-bit passes)
 void radix_sort_hi32(std::vector<uint64_t>& a, std::vector<uint64_t>& tmp) {
@@ -58,6 +60,7 @@ struct PlanTables {
   std::vector<uint32_t> q_pterm, q_ppos;  // phrase queries' (term, offset) rows; empty without phrase_len
   std::vector<uint32_t> q_clause;         // DevPlan::q_clause (k_bphrase / k_group slots); empty unless fg_phrase_clauses
                                           // or fg_group_clauses is on
+  std::vector<uint32_t> q_member;         // DevPlan::q_member (k_mgroup slots); empty unless fg_group_member_phrases
   std::vector<uint64_t> thr0;
   std::vector<float> q_ub, q_wt, q_wn, q_rup;
   std::vector<fg::ProbeDesc> q_probe;  // k_conj slots' probe descriptors (rows as above)
@@ -67,15 +70,15 @@ struct PlanTables {
   std::vector<uint64_t> f_woff;
   std::vector<float> f_tab, f_max;
   std::vector<uint32_t> ch_f, ch_c, ch_t, ch_s;
-  // work items: k_conj's, k_disj's, k_scan's, k_phrase's, k_bphrase's, k_group's, k_gphrase's; items: all
+  // work items: k_conj's, k_disj's, k_scan's, k_phrase's, k_bphrase's, k_group's, k_gphrase's, k_mgroup's; items: all
   // of them as the kernels run them (order_items, joined tables only)
-  std::vector<WItem> citems, ditems, scan, phrase, bphrase, group, gphrase, items;
+  std::vector<WItem> citems, ditems, scan, phrase, bphrase, group, gphrase, mgroup, items;
   // (a thread's plans reuse one set: assign / push_back into kept capacity, no
   // page faults on fresh arrays -- ~0.2 ms of an 8-snapshot batch's planning)
   void clear() {
     auto all = [](auto&... v) { (v.clear(), ...); };
     all(q_m, q_terms, lead, q_filter, ngroup, q_hlo, q_hhi, q_hsh, thr0, q_ub, q_wt, q_wn, q_rup, f_shift, f_seg, f_woff,
-        f_tab, f_max, ch_f, ch_c, ch_t, ch_s, citems, ditems, scan, phrase, bphrase, group, gphrase, items, q_pterm, q_ppos, q_clause,
+        f_tab, f_max, ch_f, ch_c, ch_t, ch_s, citems, ditems, scan, phrase, bphrase, group, gphrase, mgroup, items, q_pterm, q_ppos, q_clause, q_member,
         q_probe, q_tier);
     nf = 0;
   }
@@ -533,10 +536,212 @@ int plan_group_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, u
   return FG_OK;
 }
 
+// Query i of the batch when one of its groups holds a phrase member and
+// fg_group_member_phrases is on (the clause table was checked by plan_phrase;
+// DESIGN.md §19): never with facet clauses, only on a snapshot with positions, else
+// FG_EUNSUPPORTED.  A group's members are the runs of its rows that begin at an
+// offset 0: one row is a term, two or more a phrase.  A phrase (a member or a
+// clause) with a term the snapshot lacks is absent; an any-of group goes on without
+// an absent member (with none left it is absent), an all-of group is absent as a
+// whole; the clause rules, the costs and the order of the score sum are
+// plan_group_phrase's, a phrase member's cost a phrase clause's, an all-of group's
+// members in (cost, position) order.  The slot's rows are plan_group_phrase's with a
+// phrase member laid out as a phrase clause (anchor first, q_pterm / q_ppos, the
+// field weights at its first row, q_ub = (text weight, name weight, 0, ...)); q_member
+// marks, per clause, the rows that begin a member.  Work items (k_mgroup), each with
+// its pass (clause, member) in the count word, a member led by its term's list or
+// its phrase's anchor's:
+//  * a Must that is a term, a phrase or an all-of group exists: one pass, the
+//    shortest lead list among them (an all-of group's: its members' shortest);
+//  * every Must is an any-of group: a pass per member of the first (cheapest);
+//  * no Must: a pass per Should term, per Should phrase, per Should all-of group
+//    and per member of every Should any-of group.
+int plan_member_group(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t nq_size, uint32_t n_segs,
+                      PlanTables& h, bool nomatch) {
+  const uint32_t b = q->q_off[i], e = q->q_off[i + 1];
+  if (q->f_off && q->f_off[i + 1] > q->f_off[i])
+    return fail(FG_EUNSUPPORTED, "query %u: group with phrase members and facet filters", i);
+  if (!ix->has_positions) return fail(FG_EUNSUPPORTED, "query %u: snapshot built without positions", i);
+  auto len = [&](uint32_t t) { return (uint64_t)(ix->off[t + 1] - ix->off[t]); };
+  struct Row { uint32_t t, vt, pp; };  // the snapshot's id, the vocabulary id, the offset in a phrase
+  struct Mem { uint32_t at, n, anchor; uint64_t cost; float wt, wn, ubt, ubn; };  // rows [at, at + n)
+  struct Cl { uint32_t at, n, oc, kind; uint64_t cost; };                         // members [at, at + n)
+  Row rows[fg::kMaxTerms];
+  Mem mem[fg::kMaxTerms];
+  Cl cl[fg::kMaxTerms];
+  uint32_t ncl = 0, nmem = 0, nrow = 0, nm = 0, ns = 0;
+  bool must_missing = false;
+  for (uint32_t j = b; j < e;) {
+    const uint32_t raw = q->phrase_len[j], flags = raw & (FG_CLAUSE_ANY | FG_CLAUSE_ALL);
+    const uint32_t n = raw & ~(FG_CLAUSE_ANY | FG_CLAUSE_ALL);
+    const uint32_t oc = q->occur ? q->occur[j] : (q->mode == FG_MODE_OR ? FG_OCCUR_SHOULD : FG_OCCUR_MUST);
+    if (oc > FG_OCCUR_MUST_NOT) return fail(FG_EINVAL, "query %u: bad occur %u", i, oc);
+    if (q->phrase_pos[j + n - 1] >= (1u << 30)) return fail(FG_EINVAL, "query %u: phrase offset too large", i);
+    Cl c{nmem, 0, oc, flags == FG_CLAUSE_ANY ? fg::kClAny : flags == FG_CLAUSE_ALL ? fg::kClAll : n >= 2 ? fg::kClPhrase : 0u, 0};
+    const uint32_t row0 = nrow;
+    bool absent = false;
+    for (uint32_t x = 0; x < n;) {
+      uint32_t xe = x + 1;  // the member's rows [x, xe): a group's run up to the next offset 0, a phrase clause's all
+      while (xe < n && (!flags || q->phrase_pos[j + xe] != 0)) ++xe;
+      Mem m{nrow, 0, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f};
+      uint64_t ct = ~0ull, cn = ~0ull;
+      float it = 0.0f, in = 0.0f;
+      bool gone = false;
+      for (uint32_t y = x; y < xe && !gone; ++y) {
+        const uint32_t t = fgh::local_term(ix, q->terms[j + y]);
+        gone = !(t < ix->n_terms && ix->off[t + 1] > ix->off[t]);
+        if (gone) break;
+        ct = std::min<uint64_t>(ct, ix->df_text[t]);
+        cn = std::min<uint64_t>(cn, ix->df_name[t]);
+        it += ix->idf_text[t];
+        in += ix->idf_name[t];
+        if (m.n && len(t) < len(rows[m.at + m.anchor].t)) m.anchor = m.n;
+        rows[m.at + m.n++] = Row{t, q->terms[j + y], q->phrase_pos[j + y]};
+      }
+      if (gone) {
+        absent |= c.kind != fg::kClAny;
+      } else {
+        if (xe - x >= 2) {
+          m.cost = ct + cn;
+          m.wt = it * (1.0f + 1.2f);  // (1 + K1), as bm25_weight's
+          m.wn = in * (1.0f + 1.2f);
+          m.ubt = ct ? m.wt : 0.0f;
+          m.ubn = cn ? m.wn : 0.0f;
+        } else {
+          m.cost = (uint64_t)ix->df_text[rows[m.at].t] + ix->df_name[rows[m.at].t];
+        }
+        nrow += m.n;
+        mem[nmem + c.n++] = m;
+      }
+      x = xe;
+    }
+    j += n;
+    if (absent || c.n == 0) {
+      must_missing |= oc == FG_OCCUR_MUST;
+      nrow = row0;
+      continue;
+    }
+    Mem* m0 = mem + c.at;
+    if (c.kind == fg::kClAll) {
+      std::stable_sort(m0, m0 + c.n, [](const Mem& x, const Mem& y) { return x.cost < y.cost; });
+      c.cost = m0[0].cost;
+    } else {
+      for (uint32_t x = 0; x < c.n; ++x) c.cost += m0[x].cost;
+    }
+    nmem += c.n;
+    nm += oc == FG_OCCUR_MUST;
+    ns += oc == FG_OCCUR_SHOULD;
+    cl[ncl++] = c;
+  }
+  // a Must matches nothing, no positive clause, or facet clauses that match no doc: no hits
+  if (must_missing || nm + ns == 0 || nomatch) return FG_OK;
+  if (nm == 0 && ns == 1)
+    for (uint32_t c = 0; c < ncl; ++c)
+      if (cl[c].oc == FG_OCCUR_SHOULD) { cl[c].oc = FG_OCCUR_MUST; nm = 1; ns = 0; }
+  // the order of the score sum
+  auto rank = [&](const Cl& c) {
+    if (nm) return c.oc == FG_OCCUR_MUST ? 0 : c.oc == FG_OCCUR_MUST_NOT ? 1 : 2;
+    return c.oc == FG_OCCUR_SHOULD ? 0 : 1;
+  };
+  std::stable_sort(cl, cl + ncl, [&](const Cl& x, const Cl& y) {
+    const int rx = rank(x), ry = rank(y);
+    if (rx != ry) return rx < ry;
+    return nm && rx == 0 && x.cost < y.cost;  // (stable: ties and the other kinds by clause position)
+  });
+  const size_t row = (size_t)i * fg::kMaxTerms;
+  uint32_t lead_row[fg::kMaxTerms], first[fg::kMaxTerms], o = 0;  // lead_row: per member (cl.at + u), its first row
+  for (uint32_t c = 0; c < ncl; ++c) {
+    const Cl& x = cl[c];
+    first[c] = o;
+    uint32_t mask = 0;
+    for (uint32_t u = 0; u < x.n; ++u) {
+      const Mem& m = mem[x.at + u];
+      lead_row[x.at + u] = o;
+      mask |= 1u << (o - first[c]);
+      if (m.n >= 2) {
+        for (uint32_t y = 0, at = 1; y < m.n; ++y) {
+          const uint32_t dst = o + (y == m.anchor ? 0 : at++);
+          h.q_terms[row + dst] = rows[m.at + y].t;
+          h.q_pterm[row + dst] = rows[m.at + y].vt;
+          h.q_ppos[row + dst] = rows[m.at + y].pp;
+        }
+        h.q_wt[row + o] = m.wt;
+        h.q_wn[row + o] = m.wn;
+        // the bound: a field's weight, or 0.0 where some term of the phrase has no posting in that field here
+        h.q_ub[row + o] = m.ubt;
+        h.q_ub[row + o + 1] = m.ubn;
+      } else {
+        const uint32_t t = rows[m.at].t;
+        float rdn, rup;
+        fgh::term_ratio(ix, t, &rdn, &rup);
+        h.q_terms[row + o] = t;
+        h.q_wt[row + o] = ix->w_text[t];
+        h.q_wn[row + o] = ix->w_name[t];
+        h.q_rup[row + o] = rup;
+        h.q_ub[row + o] = fgh::term_max_scaled(ix, t, rup);
+      }
+      o += m.n;
+    }
+    h.q_clause[row + c] =
+        fg::cl_pack(first[c], o - first[c], x.oc, x.kind == fg::kClPhrase, c) | (x.kind & (fg::kClAny | fg::kClAll));
+    h.q_member[row + c] = mask;
+  }
+  h.q_m[i] = fg::qm_phrase(ncl, o);
+  // the passes (clause, member)
+  struct Pass { uint32_t c, m; };
+  Pass pass[fg::kMaxTerms];
+  uint32_t np = 0;
+  auto term_of = [&](uint32_t c, uint32_t m) { return h.q_terms[row + lead_row[cl[c].at + m]]; };
+  auto candidate = [&](uint32_t c) {  // a term, a phrase's anchor, an all-of group's member with the shortest lead list
+    uint32_t m = 0;
+    if (cl[c].kind == fg::kClAll)
+      for (uint32_t u = 1; u < cl[c].n; ++u)
+        if (len(term_of(c, u)) < len(term_of(c, m))) m = u;
+    return m;
+  };
+  bool driver = false;  // a Must that is a term, a phrase or an all-of group
+  for (uint32_t c = 0; c < nm; ++c) {
+    if (cl[c].kind == fg::kClAny) continue;
+    const Pass p{c, candidate(c)};
+    if (!driver || len(term_of(p.c, p.m)) < len(term_of(pass[0].c, pass[0].m))) pass[0] = p;
+    driver = true;
+  }
+  if (driver) {
+    np = 1;
+  } else {
+    for (uint32_t c = 0; c < (nm ? 1u : ns); ++c) {
+      if (cl[c].kind == fg::kClAny)
+        for (uint32_t u = 0; u < cl[c].n; ++u) pass[np++] = Pass{c, u};
+      else
+        pass[np++] = Pass{c, candidate(c)};
+    }
+  }
+  const uint32_t cdiv = n_segs <= 1 ? 1u : n_segs;
+  const uint32_t per_q = std::max<uint32_t>(
+      1, std::min<uint32_t>(64, std::max<uint32_t>(fg::kConjGroupsPerQuery, 1024 / std::max(nq_size, 1u))) / cdiv);
+  h.lead[i] = (uint32_t)len(term_of(pass[0].c, pass[0].m));
+  uint32_t total = 0;
+  for (uint32_t x = 0; x < np; ++x) {
+    const uint32_t nch = (uint32_t)((len(term_of(pass[x].c, pass[x].m)) + fg::kChunk - 1) / fg::kChunk);
+    if (h.mgroup.size() + nch > 0x7FFFFFFFull)
+      return fail(FG_EUNSUPPORTED, "batch too large (%zu work items)", h.mgroup.size());
+    const uint32_t G = std::min<uint32_t>(fg::kPhraseMaxGroup, std::max<uint32_t>(1, (nch + per_q - 1) / per_q));
+    const uint32_t ng = (nch + G - 1) / G;
+    for (uint32_t g = 0; g < ng; ++g)
+      h.mgroup.push_back(WItem{(g + 0.5) / ng, i, g * G,
+                               std::min(G, nch - g * G) | (pass[x].c << fg::kGrpClauseShift) |
+                                   (pass[x].m << fg::kGrpMemberShift)});
+    total += ng;
+  }
+  h.ngroup[i] = total;
+  return FG_OK;
+}
+
 // Query i of the batch when it holds a phrase clause (fg_query_batch::phrase_len
 // >= 2; *phrase = 0 otherwise, after checking the clause table; a group clause,
 // fg_group_clauses, goes to plan_group, one beside a phrase clause, with
-// fg_group_phrase_clauses `gphrase`, to plan_group_phrase): the device
+// fg_group_phrase_clauses `gphrase`, to plan_group_phrase; a group that holds a
+// phrase member, with fg_group_member_phrases `members`, to plan_member_group): the device
 // subset -- the phrase is the query's only clause (`beside`, fg_phrase_clauses:
 // other clauses beside it go to plan_bool_phrase), facet clauses only with
 // `filters` (fg_filter_clauses; `nomatch`: they match no doc of the snapshot, so
@@ -549,10 +754,11 @@ int plan_group_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, u
 // idfs summed in phrase order from 0.0 (a repeated term each time), times
 // (1 + K1).  Work items (k_phrase): groups of the lead list's chunks, as k_conj's.
 int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t nq_size, uint32_t n_segs,
-                PlanTables& h, int* phrase, bool beside, bool groups, bool filters, bool gphrase, bool nomatch) {
+                PlanTables& h, int* phrase, bool beside, bool groups, bool filters, bool gphrase, bool members, bool nomatch) {
   *phrase = 0;
   const uint32_t b = q->q_off[i], e = q->q_off[i + 1], m = e - b;
   uint32_t n_clauses = 0, n_phr = 0, n_grp = 0;
+  bool has_pm = false;  // a group holds a nonzero offset: a phrase member (fg_group_member_phrases)
   for (uint32_t j = b; j < e;) {
     uint32_t n = q->phrase_len[j];
     // a group clause (fg_group_clauses; off: the flags make n a bad phrase_len, as before)
@@ -563,7 +769,21 @@ int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_
         return fail(FG_EINVAL, "query %u: bad phrase_len at term %u", i, j - b);
       for (uint32_t x = 0; x < n; ++x) {
         if (x && q->phrase_len[j + x] != 0) return fail(FG_EINVAL, "query %u: phrase_len inside a group must be 0", i);
-        if (q->phrase_pos[j + x] != 0) return fail(FG_EINVAL, "query %u: a group member's offset must be 0", i);
+        const uint32_t pp = q->phrase_pos[j + x];
+        if (!members || x == 0) {
+          if (pp != 0) return fail(FG_EINVAL, "query %u: a group member's offset must be 0", i);
+          continue;
+        }
+        // fg_group_member_phrases: an offset > 0 continues the member before it as the next term of a phrase
+        if (pp == 0) continue;
+        if (pp <= q->phrase_pos[j + x - 1]) return fail(FG_EINVAL, "query %u: phrase offsets must increase", i);
+        if (pp >= (1u << 30)) return fail(FG_EINVAL, "query %u: phrase offset too large", i);
+        has_pm = true;
+      }
+      if (members) {
+        uint32_t nmem = 0;
+        for (uint32_t x = 0; x < n; ++x) nmem += q->phrase_pos[j + x] == 0;
+        if (nmem < 2) return fail(FG_EINVAL, "query %u: a group needs two members", i);
       }
       ++n_grp;
       ++n_clauses;
@@ -585,6 +805,7 @@ int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_
   }
   if (n_grp) {
     *phrase = 1;
+    if (has_pm) return plan_member_group(ix, q, i, nq_size, n_segs, h, nomatch);
     if (n_phr && gphrase) return plan_group_phrase(ix, q, i, nq_size, n_segs, h, nomatch);
     if (n_phr) return fail(FG_EUNSUPPORTED, "query %u: group clause beside a phrase clause", i);
     return plan_group(ix, q, i, nq_size, n_segs, h, filters, nomatch);
@@ -648,10 +869,10 @@ int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_
 // that batch: plan_pieces plans a snapshot's queries in pieces)
 // qtime: the plan forms its scores at query time (some snapshot's statistics
 // changed since its build: DevPlan::feat), so the descriptors point at payloads
-// beside, groups, filters, gphrase: fg_phrase_clauses, fg_group_clauses, fg_filter_clauses, fg_group_phrase_clauses as
-// the plan's creation read them
+// beside, groups, filters, gphrase, members: fg_phrase_clauses, fg_group_clauses, fg_filter_clauses,
+// fg_group_phrase_clauses, fg_group_member_phrases as the plan's creation read them
 int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t n_segs, PlanTables& h,
-              uint32_t nq_size, bool qtime, bool beside, bool groups, bool filters, bool gphrase) {
+              uint32_t nq_size, bool qtime, bool beside, bool groups, bool filters, bool gphrase, bool members) {
   if (!ix || !q || (q->n_queries && !q->q_off)) return fail(FG_EINVAL, "bad arguments");
   if (q->n_queries && q->q_off[q->n_queries] > q->q_off[0] && !q->terms) return fail(FG_EINVAL, "q_off without terms");
   if (q->f_off && q->n_queries && q->f_off[q->n_queries] > q->f_off[0] && !q->f_terms)
@@ -678,6 +899,7 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
     h.q_pterm.assign(nqt, 0);
     h.q_ppos.assign(nqt, 0);
     if (beside || groups) h.q_clause.assign(nqt, 0);
+    if (groups && members) h.q_member.assign(nqt, 0);
   }
 
   // ---- facet filters: one mask per distinct clause list (fg_internal.h DevFilters)
@@ -797,7 +1019,7 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
     if (m > fg::kMaxTerms) return fail(FG_EUNSUPPORTED, "query %u has %u terms (> %u)", i, m, fg::kMaxTerms);
     if (q->phrase_len) {
       int phrase = 0;
-      if (int rc = plan_phrase(ix, q, i, nq_size, n_segs, h, &phrase, beside, groups, filters, gphrase, q_nomatch[i] != 0)) return rc;
+      if (int rc = plan_phrase(ix, q, i, nq_size, n_segs, h, &phrase, beside, groups, filters, gphrase, members, q_nomatch[i] != 0)) return rc;
       if (phrase) continue;
     }
     if (q_nomatch[i]) continue;  // the facet clauses match nothing: no hits
@@ -1017,7 +1239,8 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
   const bool groups = group_clauses_on.load(std::memory_order_relaxed) != 0;
   const bool filters = filter_clauses_on.load(std::memory_order_relaxed) != 0;
   const bool gphrase = group_phrase_clauses_on.load(std::memory_order_relaxed) != 0;
-  if (S == 1) return plan_host(ixs[0], q, k, S, hs[0], nq1, qt, beside, groups, filters, gphrase);  // (used in place: nothing to join)
+  const bool members = group_member_phrases_on.load(std::memory_order_relaxed) != 0;
+  if (S == 1) return plan_host(ixs[0], q, k, S, hs[0], nq1, qt, beside, groups, filters, gphrase, members);  // (used in place: nothing to join)
   J.clear();
   const size_t nq = (size_t)S * nq1, nqt = nq * fg::kMaxTerms;
   for (auto* v : {&J.q_m, &J.lead, &J.ngroup, &J.q_tier}) v->resize(nq);
@@ -1028,6 +1251,7 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
   if (q->phrase_len)
     for (auto* v : {&J.q_pterm, &J.q_ppos}) v->resize(nqt);
   if (q->phrase_len && (beside || groups)) J.q_clause.resize(nqt);
+  if (q->phrase_len && groups && members) J.q_member.resize(nqt);
   auto put_slot = [&](uint32_t p) {  // piece p's per-query tables into its slots
     const PlanTables& h = hs[p];
     const size_t v0 = pc.slot(p), t0 = v0 * fg::kMaxTerms;
@@ -1039,6 +1263,7 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
     cp(J.q_probe, h.q_probe, t0);
     cp(J.q_pterm, h.q_pterm, t0); cp(J.q_ppos, h.q_ppos, t0);  // (empty without phrase_len)
     cp(J.q_clause, h.q_clause, t0);
+    cp(J.q_member, h.q_member, t0);
   };
   if (par) {
     std::vector<int> rcs(n, FG_OK);
@@ -1049,14 +1274,14 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
       qp.n_queries = b - a;
       qp.q_off = q->q_off + a;
       if (q->f_off) qp.f_off = q->f_off + a;
-      if ((rcs[p] = plan_host(ixs[p / pc.P], &qp, k, S, hs[p], nq1, qt, beside, groups, filters, gphrase))) errs[p] = fg_last_error();
+      if ((rcs[p] = plan_host(ixs[p / pc.P], &qp, k, S, hs[p], nq1, qt, beside, groups, filters, gphrase, members))) errs[p] = fg_last_error();
       else put_slot(p);
     });
     for (uint32_t p = 0; p < n; ++p)
       if (rcs[p]) return fail(rcs[p], "snapshot %u: %s", p / pc.P, errs[p].c_str());
   } else {
     for (uint32_t s = 0; s < S; ++s) {
-      if (int rc = plan_host(ixs[s], q, k, S, hs[s], nq1, qt, beside, groups, filters, gphrase)) {
+      if (int rc = plan_host(ixs[s], q, k, S, hs[s], nq1, qt, beside, groups, filters, gphrase, members)) {
         const std::string e = fg_last_error();
         return fail(rc, "snapshot %u: %s", s, e.c_str());
       }
@@ -1093,6 +1318,7 @@ PlanTables& join_pieces(const Pieces& pc, std::vector<PlanTables>& hs, PlanTable
     for (WItem x : h.bphrase) { x.q += vb; J.bphrase.push_back(x); }
     for (WItem x : h.group) { x.q += vb; J.group.push_back(x); }
     for (WItem x : h.gphrase) { x.q += vb; J.gphrase.push_back(x); }
+    for (WItem x : h.mgroup) { x.q += vb; J.mgroup.push_back(x); }
     J.nf += h.nf;
   }
   // one bin geometry per batch query over the snapshots where it has work
@@ -1208,9 +1434,9 @@ void sort_sweep(std::vector<WItem>& items, bool conj, const PlanTables& t, uint3
 struct WorkList {
   std::vector<uint32_t> work_q, work_c, work_n;
   std::vector<uint64_t> cand_off;
-  uint64_t n_single = 0, n_conj = 0, n_main = 0, n_scan = 0, n_phrase = 0, n_bphrase = 0, n_group = 0, n_gphrase = 0;
+  uint64_t n_single = 0, n_conj = 0, n_main = 0, n_scan = 0, n_phrase = 0, n_bphrase = 0, n_group = 0, n_gphrase = 0, n_mgroup = 0;
   uint32_t xcd_first[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // DevPlan::xcd_first
-  uint64_t count() const { return n_main + n_scan + n_phrase + n_bphrase + n_group + n_gphrase; }
+  uint64_t count() const { return n_main + n_scan + n_phrase + n_bphrase + n_group + n_gphrase + n_mgroup; }
 };
 
 // k_conj's multi-list items (sorted) cut into the 8 XCDs' stretches by expected
@@ -1245,13 +1471,13 @@ void xcd_stretches(const PlanTables& t, WorkList& w) {
 int order_items(PlanTables& t, uint32_t nq, uint32_t k, WorkList& w) {
   if (t.f_woff[t.nf] * 4 > (8ull << 30)) return fail(FG_EUNSUPPORTED, "facet masks of this batch exceed 8 GiB");
   if (t.ch_f.size() > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "facet postings of this batch too large");
-  if (t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size() > 0x7FFFFFFFull)
+  if (t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size() + t.mgroup.size() > 0x7FFFFFFFull)
     return fail(FG_EUNSUPPORTED, "batch too large (%zu work items)",
-                t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size());
+                t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size() + t.mgroup.size());
   sort_sweep(t.citems, true, t, nq);
   sort_sweep(t.ditems, false, t, nq);
   auto& items = t.items;
-  items.reserve(t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size());
+  items.reserve(t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size() + t.mgroup.size());
   items.insert(items.end(), t.citems.begin(), t.citems.end());
   w.n_conj = t.citems.size();
   items.insert(items.end(), t.ditems.begin(), t.ditems.end());
@@ -1273,13 +1499,17 @@ int order_items(PlanTables& t, uint32_t nq, uint32_t k, WorkList& w) {
   // k_gphrase: the same sweep
   std::stable_sort(t.gphrase.begin(), t.gphrase.end(), [](const WItem& a, const WItem& b) { return a.key < b.key; });
   w.n_gphrase = t.gphrase.size();
-  const uint64_t chunks = w.count();  // work items (k_conj / k_disj, then k_scan, k_phrase, k_bphrase, k_group, k_gphrase)
+  // k_mgroup: the same sweep
+  std::stable_sort(t.mgroup.begin(), t.mgroup.end(), [](const WItem& a, const WItem& b) { return a.key < b.key; });
+  w.n_mgroup = t.mgroup.size();
+  const uint64_t chunks = w.count();  // work items (k_conj / k_disj, then k_scan, k_phrase, k_bphrase, k_group, k_gphrase, k_mgroup)
   if (chunks > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "batch too large (%llu work items)", (unsigned long long)chunks);
   items.insert(items.end(), t.scan.begin(), t.scan.end());
   items.insert(items.end(), t.phrase.begin(), t.phrase.end());
   items.insert(items.end(), t.bphrase.begin(), t.bphrase.end());
   items.insert(items.end(), t.group.begin(), t.group.end());
   items.insert(items.end(), t.gphrase.begin(), t.gphrase.end());
+  items.insert(items.end(), t.mgroup.begin(), t.mgroup.end());
   w.work_q.resize(chunks);
   w.work_c.resize(chunks);
   w.work_n.resize(chunks);
@@ -1371,6 +1601,7 @@ int stage_and_upload(fg_plan* p, fg_index* const* ixs, PlanTables& t, const Work
   L.in(d.q_pterm, t.q_pterm.data(), 4 * t.q_pterm.size());
   L.in(d.q_ppos, t.q_ppos.data(), 4 * t.q_ppos.size());
   L.in(d.q_clause, t.q_clause.data(), 4 * t.q_clause.size());
+  L.in(d.q_member, t.q_member.data(), 4 * t.q_member.size());
   const size_t o_cache = L.add(4ull * 512 * S);  // (room for S even when fewer distinct caches are stored)
   L.in(d.f.q_filter, t.q_filter.data(), 4ull * nq);
   L.in(d.f.f_shift, t.f_shift.data(), 4ull * nf);
@@ -1476,6 +1707,7 @@ void fill_view(fg_plan* p, fg_index* const* ixs, PlanTables& t, const WorkList& 
   p->d.n_bphrase = (uint32_t)w.n_bphrase;
   p->d.n_group = (uint32_t)w.n_group;
   p->d.n_gphrase = (uint32_t)w.n_gphrase;
+  p->d.n_mgroup = (uint32_t)w.n_mgroup;
   p->d.n_single = (uint32_t)w.n_single;
   std::copy(w.xcd_first, w.xcd_first + 9, p->d.xcd_first);
   p->d.k = p->k;
@@ -1580,6 +1812,11 @@ int fg_filter_clauses(int on) {
 int fg_group_phrase_clauses(int on) {
   if (on < 0) return group_phrase_clauses_on.load(std::memory_order_relaxed);
   return group_phrase_clauses_on.exchange(on != 0 ? 1 : 0, std::memory_order_relaxed);
+}
+
+int fg_group_member_phrases(int on) {
+  if (on < 0) return group_member_phrases_on.load(std::memory_order_relaxed);
+  return group_member_phrases_on.exchange(on != 0 ? 1 : 0, std::memory_order_relaxed);
 }
 
 int fg_plan_tiered_slots(const fg_plan* p, uint32_t* out) {

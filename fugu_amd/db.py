@@ -235,13 +235,15 @@ def parse_query_clause_lines(query: str):
 
 def parse_query_groups(query: str):
     """[(occur, kind, [term, ...])] with kind "term", "phrase", "any" or "all": the query's
-    clauses with group clauses (native.group_clauses) told apart."""
+    clauses with group clauses (native.group_clauses) told apart.  A phrase member of a group
+    (native.group_member_phrases) is a list of its tokens inside the group's list."""
     out = []
     for line in parse_query_clause_lines(query):
         oc, body = int(line[0]), line[2:]
         if body.startswith("("):
             kind = "any" if " | " in body else "all"
-            out.append((oc, kind, body[1:-1].split(" | " if kind == "any" else " & ")))
+            mem = body[1:-1].split(" | " if kind == "any" else " & ")
+            out.append((oc, kind, [[x.rsplit("@", 1)[0] for x in m.split(" ")] if " " in m else m for m in mem]))
         else:
             toks = [x.rsplit("@", 1)[0] for x in body.split(" ")]
             out.append((oc, "term" if len(toks) == 1 else "phrase", toks))

@@ -66,7 +66,7 @@ EXPORTS = (
     "fg_index_build_positional", "fg_index_positions_get",
     "fg_index_bands_get", "fg_index_band_read", "fg_plan_tiered_slots",
     "fg_phrase_clauses", "fg_group_clauses", "fg_filter_clauses", "fg_count_clauses", "fg_count_clause_trace",
-    "fg_group_phrase_clauses",
+    "fg_group_phrase_clauses", "fg_group_member_phrases",
 )
 BAND_TIERS = 5  # fugu.h FG_BAND_TIERS
 LADDER_KS = (1, 2, 3, 5, 10, 13, 20, 25, 50, 100, 125, 250, 500, 1000)  # FG_LADDER_LEVELS ranks
@@ -195,6 +195,8 @@ if hasattr(_lib, "fg_filter_clauses"):  # (likewise)
     _sig("fg_filter_clauses", C.c_int, C.c_int)
 if hasattr(_lib, "fg_group_phrase_clauses"):  # (likewise)
     _sig("fg_group_phrase_clauses", C.c_int, C.c_int)
+if hasattr(_lib, "fg_group_member_phrases"):  # (likewise)
+    _sig("fg_group_member_phrases", C.c_int, C.c_int)
 if hasattr(_lib, "fg_count_clauses"):  # (likewise)
     _sig("fg_count_clauses", C.c_int, C.c_int)
     _sig("fg_count_clause_trace", C.c_int, C.c_int, _f64p, _u32p)
@@ -305,6 +307,16 @@ def group_phrase_clauses(on: int = -1) -> int:
     if not hasattr(_lib, "fg_group_phrase_clauses"):
         raise Unsupported(FG_EUNSUPPORTED, "this libfugu has no fg_group_phrase_clauses")
     return int(_lib.fg_group_phrase_clauses(int(on)))
+
+
+def group_member_phrases(on: int = -1) -> int:
+    """fg_group_member_phrases: a group may hold phrase members -- `(e-mail OR email) server` --
+    (group_clauses as well, so that the flags parse; no other switch is consulted); such a query
+    runs on the device (k_mgroup) when on; process-wide, off by default, read when a plan is
+    created.  on: 1 / 0 sets it, < 0 only asks.  Returns the previous setting."""
+    if not hasattr(_lib, "fg_group_member_phrases"):
+        raise Unsupported(FG_EUNSUPPORTED, "this libfugu has no fg_group_member_phrases")
+    return int(_lib.fg_group_member_phrases(int(on)))
 
 
 def count_clauses(on: "int | None" = None) -> int:
@@ -872,7 +884,7 @@ class Plan:
     def seed_thresholds(self, score):
         """fg_plan_seed_thr0 (diagnostic): every query starts from the lowest key with
         score[i] ([n_batch] f32, 0: no starting threshold).  Every top-k kernel reads
-        it: k_conj, k_disj, k_scan, k_phrase, k_bphrase, k_group and k_gphrase."""
+        it: k_conj, k_disj, k_scan, k_phrase, k_bphrase, k_group, k_gphrase and k_mgroup."""
         s = np.ascontiguousarray(score, np.float32)
         if s.shape != (self.n_batch,):
             raise ValueError(f"scores of {s.shape}, expected ({self.n_batch},)")

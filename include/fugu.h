@@ -469,6 +469,38 @@ int fg_filter_clauses(int on);
  * untouched (fg_count_clauses). */
 int fg_group_phrase_clauses(int on);
 
+/* PHRASES AS GROUP MEMBERS (`(e-mail OR email) server`, `("new york" OR boston)
+ * pizza`, `+(disk-full enospc) +error`: the shape fg_group_clauses refuses with "a
+ * group member's offset must be 0") run on the device (k_mgroup)
+ * when on != 0.  The contract of fg_group_phrase_clauses: process-wide, off by
+ * default, read when a plan is created; on: 1 / 0 sets it, < 0 only asks; returns
+ * the previous setting.  It consults fg_group_clauses (so that the flags parse)
+ * and none of the other switches.  Off: every entry point answers as before.
+ * On, a group is written as now -- FG_CLAUSE_ANY / FG_CLAUSE_ALL OR-ed onto the
+ * number of ROWS n of the group in `phrase_len` at its first term, n - 1 zeros
+ * after -- and `phrase_pos` tells its members apart: a row with offset 0 begins a
+ * member, a row with offset > 0 continues the member before it as the next term
+ * of a phrase (offsets increase strictly inside a member; a hole is a token the
+ * analyzer dropped; a repeated term is allowed).  A group whose offsets are all 0
+ * means what it meant.  FG_EINVAL: the group's first offset is not 0 ("a group
+ * member's offset must be 0"), "phrase offsets must increase", "phrase offset too
+ * large" (>= 2^30), "a group needs two members".  FG_MAX_TERMS holds over all
+ * rows of the query together.  A query that holds at least one group with a
+ * phrase member may hold terms, phrase clauses and other groups beside it, under
+ * any occur; a query without one plans exactly as before.  Every member gives a
+ * doc a score or "absent": a term as everywhere, a phrase as a phrase clause
+ * (fg_phrase_clauses: its cost the sum over the two fields of its terms' smallest
+ * doc count there); the group joins its members as fg_group_clauses' groups do
+ * (any-of: present members from 0.0 in written order, cost the sum; all-of:
+ * (cost, position) order, (s0 + s1) + (0.0 + s2 + ...), cost the smallest).  Per
+ * snapshot a phrase member with a term the snapshot lacks is absent; an any-of
+ * group goes on without an absent member, an all-of group is absent as a whole.
+ * Still FG_EUNSUPPORTED: facet clauses on such a query ("group with phrase
+ * members and facet filters", whatever fg_filter_clauses says), a snapshot
+ * without positions ("snapshot built without positions"), and fg_model_batch.
+ * fg_count_batch is untouched. */
+int fg_group_member_phrases(int on);
+
 /* Plan a batch: host-side query planning (tantivy Weight creation: terms
  * ordered by cost, query/intersection.rs) and upload of the plan to HBM.
  * Returns FG_EUNSUPPORTED for queries outside the device subset

@@ -49,7 +49,9 @@
  * (grouping while that switch is off or deeper than one level, a phrase beside other
  * clauses while that switch is off, a group beside a phrase -- `e-mail (server OR host)`
  * -- unless fg_group_phrase_clauses(1) is set as well (fugu.h; process-wide, off by
- * default: k_gphrase), a phrase or a group with filters unless
+ * default: k_gphrase), a phrase as a group member -- `(e-mail OR email) server`,
+ * `e-mail AND server OR host` -- unless fg_group_member_phrases(1) is set as well
+ * (fugu.h; process-wide, off by default: k_mgroup), a phrase or a group with filters unless
  * fg_filter_clauses(1) is set (fugu.h; process-wide, off by default), slop / prefix
  * suffixes on a quoted literal, field:,
  * boosts, a text query with filters that parse to no facet term) return
