@@ -94,6 +94,9 @@ int check_clauses(fg_index* const* ixs, uint32_t n_segs, const fg_query_batch* q
   for (uint32_t j = b; j < e;) {
     const uint32_t raw = q->phrase_len[j], kind = raw & both;
     const uint32_t n = raw & ~both;
+    // a field clause (fg_field_clauses) is not counted on the device, whatever the other switches say
+    if ((raw & (FG_CLAUSE_TEXT | FG_CLAUSE_NAME)) && fg_field_clauses(-1) > 0)
+      return fail(FG_EUNSUPPORTED, "query %u: field clause in a count query", i);
     if (kind) {
       if (kind == both || n < 2 || n > e - j) return fail(FG_EINVAL, "query %u: bad phrase_len at term %u", i, j - b);
       for (uint32_t x = 0; x < n; ++x) {
@@ -150,6 +153,8 @@ int check_batch(fg_index* const* ixs, uint32_t n_segs, const fg_query_batch* q, 
     if (table)
       if (int rc = check_clauses(ixs, n_segs, q, i, c)) return rc;
     for (uint32_t j = b; j < e && !table; ++j) {
+      if (q->phrase_len && (q->phrase_len[j] & (FG_CLAUSE_TEXT | FG_CLAUSE_NAME)) && fg_field_clauses(-1) > 0)
+        return fail(FG_EUNSUPPORTED, "query %u: field clause in a count query", i);
       if (q->phrase_len && (q->phrase_len[j] & (FG_CLAUSE_ANY | FG_CLAUSE_ALL)) && fg_group_clauses(-1) > 0)
         return fail(FG_EUNSUPPORTED, "query %u: group clause in a count query", i);
       if (q->phrase_len && q->phrase_len[j] >= 2) return fail(FG_EUNSUPPORTED, "query %u: phrase clause in a count query", i);

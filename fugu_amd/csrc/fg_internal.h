@@ -288,6 +288,12 @@ constexpr uint32_t kBpPassShift = 8;
 // the member's largest current score (its scaled tmaxs) and its bound factor.
 // An all-of group's members stand in (cost, position) order.
 constexpr uint32_t kClAny = 1u << 12, kClAll = 1u << 13;
+// A slot of k_field (a field-qualified term clause, `name:report`: fg_field_clauses,
+// DESIGN.md §20): q_m, the q_clause row and work_n as k_group's, every clause ONE term
+// (its row as a k_group member's), a field clause marked kClText or kClName: the
+// clause is that field's TermQuery -- present where the field's tf > 0, scored by
+// that field's part alone.  A clause with neither bit is the unqualified term.
+constexpr uint32_t kClText = 1u << 14, kClName = 1u << 15;
 // a k_group work item's work_n: the lead chunks of its group, above them the
 // clause it leads from and that clause's member whose list it sweeps (the pass)
 constexpr uint32_t kGrpClauseShift = 8, kGrpMemberShift = 12;
@@ -776,6 +782,8 @@ struct DevPlan {
                                 // the pass's member counted in members.  The rows as k_gphrase's; a phrase
                                 // MEMBER's rows are a phrase clause's (anchor first, q_pterm / q_ppos, the field
                                 // weights at its first row, q_ub = (text weight, name weight, 0, ...))
+  uint32_t n_field;             // k_field work items (queries with a field-qualified term clause:
+                                // fg_field_clauses), after the k_mgroup items, work_n as k_group's (the member 0)
   const uint32_t* q_member;     // [nq * kMaxTerms] per clause of such a slot: the mask of its rows that begin a
                                 // member; empty without fg_group_member_phrases
   // Multi-snapshot plans (several segments / doc shards / namespaces of one
@@ -1090,6 +1098,7 @@ hipError_t launch_bphrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 hipError_t launch_group(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 hipError_t launch_gphrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 hipError_t launch_mgroup(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
+hipError_t launch_field(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 // out_shard != nullptr: the merged select of a multi-snapshot plan (one list per batch query)
 hipError_t launch_final(const DevPlan& pl, float* out_score, uint32_t* out_doc, uint32_t* out_n, hipStream_t s,
                         uint32_t* out_shard = nullptr);

@@ -397,8 +397,15 @@ class DocStore {
 // all-of group.  With fg_group_member_phrases(1) as well a group
 // member or an AND-run's operand may be a word of several tokens or a quoted
 // literal: a phrase member (`(e-mail OR email) server`, `e-mail AND server OR host`).
-// Anything else (mixed AND / OR and parentheses while that switch is off, field:,
-// slop, boosts, ranges, a
+// With fg_field_clauses(1) (fugu.h; off by default) a word of the form
+// `text:WORD` or `name:WORD` -- the field name exactly as the schema writes it, WORD
+// a plain word of ONE token -- is that field's TermQuery: bare, behind `+` / `-`, or
+// an operand of the uniform AND / OR forms.  `name:"..."` and a WORD of several
+// tokens ("field-qualified phrase"), `name:(...)` and a field word inside
+// parentheses or inside a mixed-infix AND-run ("field-qualified group") and any
+// other field (`id:`, `namespace:`: "field outside [text, name]") are FG_EUNSUPPORTED.
+// Anything else (mixed AND / OR and parentheses while that switch is off, field:
+// while fg_field_clauses is off, slop, boosts, ranges, a
 // query of MustNot clauses only) is FG_EUNSUPPORTED: the reference host runs tantivy.
 // An empty query is AllQuery (src/db/search.rs:115-116), handled by the caller.
 bool is_special(char c) {
@@ -424,8 +431,16 @@ struct Clause {
   std::vector<std::string> terms;
   std::vector<uint32_t> pos;
   uint8_t group = 0;  // kGroupAny / kGroupAll; 0: a term or a phrase
+  uint8_t field = 0;  // kFieldText / kFieldName: a field-qualified term (fg_field_clauses); 0: both fields
 };
 constexpr uint8_t kGroupAny = 1, kGroupAll = 2;
+constexpr uint8_t kFieldText = 1, kFieldName = 2;
+// why a word with the special character c is outside the subset; a `:` while fg_field_clauses is on: a field
+// word where a group's member stands
+const char* member_special(char c, const char* quote_why) {
+  if (c == ':' && fg_field_clauses(-1) > 0) return "field-qualified group";
+  return c == '"' ? quote_why : c == '(' || c == ')' ? "a group inside a group" : "query syntax beyond bare/+/-/AND/OR terms";
+}
 
 bool is_operator_word(std::string_view w) { return w == "AND" || w == "OR" || w == "NOT" || w == "IN" || w == "TO"; }
 
@@ -434,8 +449,7 @@ int group_word(std::string_view w, std::string& tok, std::string& why) {
   if (is_operator_word(w)) { why = "operator outside the supported forms"; return FG_EUNSUPPORTED; }
   for (size_t c = 0; c < w.size(); ++c)
     if (is_special(w[c]) && !(w[c] == '-' && c >= 1)) {
-      why = w[c] == '"' ? "a quoted literal inside a group"
-                        : w[c] == '(' || w[c] == ')' ? "a group inside a group" : "query syntax beyond bare/+/-/AND/OR terms";
+      why = member_special(w[c], "a quoted literal inside a group");
       return FG_EUNSUPPORTED;
     }
   std::vector<std::string> toks;
@@ -462,8 +476,7 @@ int group_member(std::string_view w, bool quoted, bool members, Clause& cl, std:
     if (is_operator_word(w)) { why = "operator outside the supported forms"; return FG_EUNSUPPORTED; }
     for (size_t c = 0; c < w.size(); ++c)
       if (is_special(w[c]) && !(w[c] == '-' && c >= 1)) {
-        why = w[c] == '"' ? "query syntax beyond bare/+/-/AND/OR terms and plain quoted phrases (slop, prefix, boost)"
-                          : w[c] == '(' || w[c] == ')' ? "a group inside a group" : "query syntax beyond bare/+/-/AND/OR terms";
+        why = member_special(w[c], "query syntax beyond bare/+/-/AND/OR terms and plain quoted phrases (slop, prefix, boost)");
         return FG_EUNSUPPORTED;
       }
   } else if (w.find('\\') != std::string_view::npos) {
@@ -549,6 +562,28 @@ int parse_group(std::string_view body, Clause& cl, std::string& why, bool member
   return FG_OK;
 }
 
+// A word `FIELD:WORD` (fg_field_clauses is on, w holds a `:`, the prefix is behind it): the field and the rest, or
+// `why` (a code < 0).  1: of that form; 0: not (an empty or non-word field name), the caller's checks answer as before.
+int field_word(std::string_view w, uint8_t& field, std::string_view& rest, std::string& why) {
+  const size_t colon = w.find(':');
+  if (colon == 0 || colon == std::string_view::npos) return 0;
+  const std::string_view name = w.substr(0, colon);
+  for (char c : name)
+    if (is_special(c)) {  // `(name:a`: a field word inside parentheses
+      if (c == '(' || c == ')') { why = "field-qualified group"; return FG_EUNSUPPORTED; }
+      return 0;
+    }
+  if (name != "text" && name != "name") { why = "field outside [text, name]"; return FG_EUNSUPPORTED; }
+  rest = w.substr(colon + 1);
+  if (!rest.empty() && rest[0] == '"') { why = "field-qualified phrase"; return FG_EUNSUPPORTED; }
+  if (rest.find('(') != std::string_view::npos || rest.find(')') != std::string_view::npos) {
+    why = "field-qualified group";
+    return FG_EUNSUPPORTED;
+  }
+  field = name == "text" ? kFieldText : kFieldName;
+  return 1;
+}
+
 // The clauses of a query.  A literal is a word or a quoted "..." (no `\` or `"`
 // inside, nothing but white space after the closing quote: slop `~` and prefix
 // `*` suffixes are outside the subset); a word may hold `-` after its first
@@ -558,6 +593,7 @@ int parse_clauses(std::string_view q, std::vector<Clause>& out, std::string& why
   out.clear();
   const bool groups = fg_group_clauses(-1) > 0;
   const bool members = groups && fg_group_member_phrases(-1) > 0;  // a group may hold phrase members
+  const bool fields = fg_field_clauses(-1) > 0;  // `text:WORD` / `name:WORD`
   struct Item { std::string_view body; bool quoted; bool prefixed; uint8_t occur; bool group = false; };
   std::vector<Item> items;
   auto space = [](char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r'; };
@@ -673,14 +709,18 @@ int parse_clauses(std::string_view q, std::vector<Clause>& out, std::string& why
     raw = items;
   }
   bool positive = false;
+  bool has_field = false;  // fg_field_clauses: some word begins `text:` / `name:`
+  for (const Item& it : items) {
+    const std::string_view f = it.body.substr(0, std::min<size_t>(it.body.size(), 5));
+    has_field |= fields && !it.quoted && !it.group && (f == "text:" || f == "name:");
+  }
   for (size_t r = 0; r < raw.size(); ++r) {
     const Item& it = raw[r];
-    const std::string_view w = it.body;
     if (it.group || (!runs.empty() && runs[r].second > runs[r].first)) {
       Clause cl;
       cl.occur = it.occur;
       if (it.group) {
-        if (int rc = parse_group(w, cl, why, members)) return rc;
+        if (int rc = parse_group(it.body, cl, why, members)) return rc;
       } else {  // an AND-run of plain words (fg_group_member_phrases: of literals)
         for (size_t x = runs[r].first; x <= runs[r].second; x += 2)
           if (int rc = group_member(items[x].body, items[x].quoted, members, cl, why)) return rc;
@@ -690,6 +730,15 @@ int parse_clauses(std::string_view q, std::vector<Clause>& out, std::string& why
       out.push_back(std::move(cl));
       continue;
     }
+    Clause cl;
+    cl.occur = it.occur;
+    std::string_view w = it.body;
+    if (fields && !it.quoted && w.find(':') != std::string_view::npos) {
+      std::string_view rest;
+      const int rc = field_word(w, cl.field, rest, why);
+      if (rc < 0) return rc;
+      if (rc > 0) w = rest;
+    }
     if (!it.quoted) {
       if (w == "AND" || w == "OR" || w == "NOT" || w == "IN" || w == "TO") {
         why = "operator outside the supported forms";
@@ -697,15 +746,18 @@ int parse_clauses(std::string_view q, std::vector<Clause>& out, std::string& why
       }
       for (size_t c = 0; c < w.size(); ++c)
         if (is_special(w[c]) && !(w[c] == '-' && c >= 1)) {
-          why = "query syntax beyond bare/+/-/AND/OR terms";
+          // (a word in parentheses beside a field word: `(b name:a)` while fg_group_clauses is off)
+          why = has_field && (w[c] == '(' || w[c] == ')') ? "field-qualified group" : "query syntax beyond bare/+/-/AND/OR terms";
           return FG_EUNSUPPORTED;
         }
     }
-    Clause cl;
-    cl.occur = it.occur;
     analyze(w, cl.terms, &cl.pos);
     if (cl.terms.empty()) {
       why = "a term analyzes to no token";
+      return FG_EUNSUPPORTED;
+    }
+    if (cl.field && cl.terms.size() > 1) {
+      why = "field-qualified phrase";
       return FG_EUNSUPPORTED;
     }
     for (size_t j = cl.pos.size(); j-- > 0;) cl.pos[j] -= cl.pos[0];
@@ -729,6 +781,10 @@ int parse_query(std::string_view q, std::vector<std::string>& terms, std::vector
   for (auto& c : cl) {
     if (c.group) {
       why = "a group clause (a nested BooleanQuery)";
+      return FG_EUNSUPPORTED;
+    }
+    if (c.field) {
+      why = "a field-qualified term";
       return FG_EUNSUPPORTED;
     }
     if (c.terms.size() != 1) {
@@ -1368,8 +1424,9 @@ int search_hits(fg_db* db, Namespace& ns, const char* query, const std::vector<s
     int rc = parse_clauses(qv, cls, why);
     if (rc) return hfail(rc, "query outside the device subset: " + why);
     for (Clause& c : cls) {
-      any_phrase |= c.terms.size() > 1;
-      const uint32_t flag = c.group == kGroupAny ? FG_CLAUSE_ANY : c.group == kGroupAll ? FG_CLAUSE_ALL : 0u;
+      any_phrase |= c.terms.size() > 1 || c.field;
+      const uint32_t flag = c.group == kGroupAny ? FG_CLAUSE_ANY : c.group == kGroupAll ? FG_CLAUSE_ALL
+                            : c.field == kFieldText ? FG_CLAUSE_TEXT : c.field == kFieldName ? FG_CLAUSE_NAME : 0u;
       for (size_t j = 0; j < c.terms.size(); ++j) {
         terms.push_back(std::move(c.terms[j]));
         occur.push_back(c.occur);
@@ -1458,6 +1515,7 @@ int count_query(Namespace& ns, const char* query, const std::vector<std::string>
     if (rc) return hfail(rc, "query outside the device subset: " + why);
     const bool rows = fg_count_clauses(-1) > 0;  // phrase and group clauses are counted
     for (Clause& c : cls) {
+      if (c.field) return hfail(FG_EUNSUPPORTED, "query outside the device subset: field clause in a count query");
       if (!rows) {
         if (c.group) return hfail(FG_EUNSUPPORTED, "query outside the device subset: group clause in a count query");
         if (c.terms.size() > 1) return hfail(FG_EUNSUPPORTED, "query outside the device subset: phrase clause in a count query");
@@ -3036,6 +3094,7 @@ int fg_parse_query_clauses(const char* query, char* out, size_t cap, size_t* len
       o.push_back(')');
       continue;
     }
+    if (cls[i].field) o += cls[i].field == kFieldText ? "text:" : "name:";  // a field clause: "name:report@0"
     for (size_t j = 0; j < cls[i].terms.size(); ++j) {
       if (j) o.push_back(' ');
       o += cls[i].terms[j] + "@" + std::to_string(cls[i].pos[j]);

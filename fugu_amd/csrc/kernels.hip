@@ -3411,6 +3411,151 @@ __global__ __launch_bounds__(kThreads, 4) void k_mgroup(DevIndex ix0, DevPlan pl
   flush_candidates(pl, q, sh.g.s.buf, sh.g.s.n_buf, sh.g.s.thr, sh.g.s.scratch);
 }
 
+// ---------------------------------------------------------------- k_field
+// Queries with a field-qualified term clause (`name:report`, `+name:a +text:b`:
+// tantivy's TermQuery on ONE field; fg_field_clauses).  The slot is
+// k_group's with one-term clauses: the clause table (DevPlan::q_clause) in the
+// order of the score sum, a row per clause in q_terms / q_wt / q_wn / q_ub / q_rup,
+// a field clause marked kClText or kClName.  A work item is a group of kChunk-
+// posting chunks of the MERGED list of clause pc's term (work_n's upper bits), the
+// pass: with a Must one pass, the Must clause with the shortest merged list;
+// without, a pass per Should clause, pass pc leaving a doc that an earlier Should
+// clause matches to that earlier pass.  One LANE per lead doc, kRound docs between
+// truncations: the lane looks every clause's posting up (posting_pos_at; the lead's
+// position is the lane's own), loads the payload, resolves an escaped tf as
+// tfn_score does, and ZEROES the tf of the field the clause does not name: the
+// clause is present iff a tf is left, and scores as tfn_score does on what is left
+// -- a field clause its field's part alone (0.0 + the part: the bits of the
+// unqualified clause on a doc that holds the term in that field only), an
+// unqualified clause bit for bit as today.  A doc of the lead list that holds the
+// term only in the other field misses the lead clause and drops out.  The join is
+// the term clauses': (s0 + s1) + (0.0 + s2 + ...) over the Musts, (0.0 + req) + opt
+// with opt the matching Shoulds from 0.0.  Keys go through k_scan's buffer,
+// threshold word and flush.
+// Pruning (exact): k_group's chunk skip, group_bound over the rows' upper bounds,
+// the lead bounded by min(cmax[chunk] * q_rup, q_ub).  These are the merged term's
+// bounds: >= every one-field score, since the other field's part is >= 0 and f32
+// addition is monotone.
+__device__ inline bool field_member(const DevIndex& ix, const GroupShared& sh, uint32_t x, uint32_t cw, uint32_t d,
+                                    uint32_t pos, float& s) {
+  if (pos == kInvalid) pos = posting_pos_at(ix, sh.tmeta[x], sh.toff[x], sh.tdir[x], d);
+  if (pos == kInvalid) return false;
+  const uint64_t p = sh.toff[x] + pos;
+  uint32_t v = ix.tfn[p];
+  if (ix.tfn_name) v |= (uint32_t)ix.tfn_name[p] << 16;
+  uint32_t tt = v & 0xFFu, tn = (v >> 16) & 0xFFu;
+  if (tt == kTfEsc || tn == kTfEsc) {
+    const uint32_t e = tf_escaped(ix.esc_pos, ix.esc_tf, ix.n_esc, p);
+    if (tt == kTfEsc) tt = e & 0xFFFFu;
+    if (tn == kTfEsc) tn = e >> 16;
+  }
+  if (cw & kClName) tt = 0u;
+  if (cw & kClText) tn = 0u;
+  s = 0.0f;
+  if (tt) s += field_score(tt, (v >> 8) & 0xFFu, sh.wt[x], sh.cache);
+  if (tn) s += field_score(tn, v >> 24, sh.wn[x], sh.cache + 256);
+  return (cw & (kClText | kClName)) == 0u || (tt | tn) != 0u;
+}
+
+template <bool kMulti>
+__global__ __launch_bounds__(kThreads, 4) void k_field(DevIndex ix0, DevPlan pl) {
+  __shared__ GroupShared sh;
+  const uint32_t tid = threadIdx.x;
+  // after the k_mgroup items
+  const uint32_t w = pl.total_chunks + pl.n_scan + pl.n_phrase + pl.n_bphrase + pl.n_group + pl.n_gphrase + pl.n_mgroup +
+                     blockIdx.x;
+  const uint32_t q = pl.work_q[w];
+  const DevIndex ix = kMulti ? seg_index(pl, __builtin_amdgcn_readfirstlane(q / pl.seg_nq)) : ix0;
+  const uint32_t ql = kMulti ? __builtin_amdgcn_readfirstlane(q % pl.seg_nq) : q;
+  const uint32_t chunk0 = pl.work_c[w];
+  const uint32_t wn = pl.work_n[w];
+  const uint32_t nchunk = wn & ((1u << kGrpClauseShift) - 1u);
+  const uint32_t K = pl.k;
+  uint64_t* gthr = &pl.thresh[ql];
+  const uint64_t thr0 = pl.q_thr0[q];  // the plan's starting threshold (0 for these slots: plan_field)
+  const uint32_t qm = pl.q_m[q];
+  const uint32_t ncl = min(qm_terms(qm), kMaxTerms);  // a row per clause
+  if (ncl == 0) return;  // (never planned; uniform)
+  const uint32_t pc = min((wn >> kGrpClauseShift) & 15u, ncl - 1);
+  const size_t row = (size_t)q * kMaxTerms;
+  if (tid < ncl) {
+    const uint32_t t = pl.q_terms[row + tid];
+    sh.tmeta[tid] = ix.tmeta[t];
+    sh.tdir[tid] = ix.dir_off[t];
+    sh.toff[tid] = ix.off[t];
+    sh.wt[tid] = pl.q_wt[row + tid];
+    sh.wn[tid] = pl.q_wn[row + tid];
+    sh.ub[tid] = pl.q_ub[row + tid];
+    // (a clause's row is its index: group_bound reads it through cl_first / cl_terms)
+    sh.cl[tid] = (pl.q_clause[row + tid] & ~0x1FFu) | tid | (1u << 4);
+  }
+  for (uint32_t i = tid; i < 512u; i += kThreads) sh.cache[i] = ix.cache[i];
+  if (tid == 0) {
+    sh.s.n_buf = 0;
+    sh.s.thr = start_threshold(pl, thr0, ql, gthr);
+  }
+  __syncthreads();
+  const bool must = cl_occur(sh.cl[0]) == kClMust;  // (the Musts stand first)
+  const uint32_t lead = pl.q_terms[row + pc];       // the lead: clause pc's merged list
+  const uint64_t base = sh.toff[pc];
+  const uint32_t df = (uint32_t)(ix.off[lead + 1] - base);
+  const float* __restrict__ cmax = ix.cmax + ix.coff[lead];
+  const float rup = pl.q_rup[row + pc];
+  for (uint32_t c = 0; c < nchunk; ++c) {
+    const uint32_t i0 = (chunk0 + c) * kChunk;
+    if (i0 >= df) break;
+    // the chunk's bound against the threshold (uniform: sh.s.thr is read after a barrier)
+    const float bound = group_bound(sh, ncl, ncl, must, pc, 0u, fminf(cmax[chunk0 + c] * rup, sh.ub[pc]));
+    if (make_key(inflate_bound(bound), 0u) < sh.s.thr) continue;
+    for (uint32_t r0 = 0; r0 < kChunk; r0 += kRound) {
+      const uint64_t thr = sh.s.thr;
+      for (uint32_t j = 0; j < kRound / kThreads; ++j) {
+        const uint32_t i = i0 + r0 + j * kThreads + tid;
+        bool keep = i < df;
+        uint32_t d = 0;
+        if (keep) {
+          d = ix.doc[base + i];
+          keep = doc_alive(ix, d);
+        }
+        float req = 0.0f, oth = 0.0f, opt = 0.0f;
+        uint32_t nm = 0;
+        bool any = false;
+        for (uint32_t ci = 0; ci < ncl && keep; ++ci) {
+          const uint32_t cw = sh.cl[ci], oc = cl_occur(cw);
+          float cs = 0.0f;
+          const bool on = field_member(ix, sh, ci, cw, d, ci == pc ? i : kInvalid, cs);
+          if (oc == kClMust) {
+            if (!on) keep = false;
+            else if (nm == 0) req = cs;
+            else if (nm == 1) req = req + cs;
+            else oth = oth + cs;
+            ++nm;
+          } else if (oc == kClMustNot) {
+            if (on) keep = false;
+          } else if (!must && ci <= pc && on != (ci == pc)) {
+            keep = false;  // an earlier pass's doc, or the pass clause does not match
+          } else if (on) {
+            opt = opt + cs;
+            any = true;
+          }
+        }
+        float sc = opt;
+        if (must) {
+          if (nm > 1) req = req + oth;
+          sc = 0.0f + req;
+          if (any) sc = sc + opt;
+        }
+        const uint64_t key = make_key(sc, d);
+        wave_append(keep && key >= thr, key, sh.s.buf, &sh.s.n_buf, kBufD);
+      }
+      __syncthreads();
+      scan_truncate(sh.s, K, kTrunc, gthr, false, pl.pub_mask, pl, ql);
+    }
+    scan_truncate(sh.s, K, K, gthr, true, pl.pub_mask, pl, ql);
+  }
+  flush_candidates(pl, q, sh.s.buf, sh.s.n_buf, sh.s.thr, sh.s.scratch);
+}
+
 // ---------------------------------------------------------------- k_final
 // Dynamic LDS (80 KB: 2 workgroups per CU): candidate keys, the k winners,
 // the radix histogram.  Keeps 16-B alignment of the dynamic base (no static
@@ -3777,6 +3922,13 @@ hipError_t launch_mgroup(const DevIndex& ix, const DevPlan& pl, hipStream_t s) {
   if (pl.n_mgroup == 0) return hipSuccess;
   if (pl.segs) k_mgroup<true><<<pl.n_mgroup, kThreads, 0, s>>>(ix, pl);
   else k_mgroup<false><<<pl.n_mgroup, kThreads, 0, s>>>(ix, pl);
+  return hipGetLastError();
+}
+
+hipError_t launch_field(const DevIndex& ix, const DevPlan& pl, hipStream_t s) {
+  if (pl.n_field == 0) return hipSuccess;
+  if (pl.segs) k_field<true><<<pl.n_field, kThreads, 0, s>>>(ix, pl);
+  else k_field<false><<<pl.n_field, kThreads, 0, s>>>(ix, pl);
   return hipGetLastError();
 }
 

@@ -612,9 +612,12 @@ extern "C" {
 int fg_model_batch(const fg_index* ix, const fg_query_batch* q, uint32_t k, const float* thr_score, double* per_query,
                    fg_model_out* out) {
   if (!ix || !q || !out || (q->n_queries && !q->q_off) || k == 0) return fail(FG_EINVAL, "bad arguments");
-  // phrase clauses (k_phrase) and group clauses (k_group, fg_group_clauses) are not modelled
+  // phrase clauses (k_phrase), group clauses (k_group, fg_group_clauses) and field clauses (k_field,
+  // fg_field_clauses) are not modelled
   if (q->phrase_len)
     for (uint32_t j = q->n_queries ? q->q_off[0] : 0; q->n_queries && j < q->q_off[q->n_queries]; ++j) {
+      if ((q->phrase_len[j] & (FG_CLAUSE_TEXT | FG_CLAUSE_NAME)) && fg_field_clauses(-1) > 0)
+        return fail(FG_EUNSUPPORTED, "bad query batch (the model does not cover field clauses)");
       if ((q->phrase_len[j] & (FG_CLAUSE_ANY | FG_CLAUSE_ALL)) && fg_group_clauses(-1) > 0)
         return fail(FG_EUNSUPPORTED, "bad query batch (the model does not cover group clauses)");
       if (q->phrase_len[j] != 1) return fail(FG_EINVAL, "bad query batch (the model does not cover phrase queries)");

@@ -34,6 +34,8 @@ std::atomic<int> filter_clauses_on{0};
 std::atomic<int> group_phrase_clauses_on{0};
 // fg_group_member_phrases: a group may hold phrase members (k_mgroup); the same contract
 std::atomic<int> group_member_phrases_on{0};
+// fg_field_clauses: queries with a field-qualified term clause run on the device (k_field); the same contract
+std::atomic<int> field_clauses_on{0};
 
 // stable LSD radix sort of `a` by its bits 32..63 (three 11-bit passes)
 void radix_sort_hi32(std::vector<uint64_t>& a, std::vector<uint64_t>& tmp) {
@@ -58,8 +60,8 @@ struct PlanTables {
   std::vector<uint32_t> q_m, q_terms, lead, q_filter, ngroup, q_hlo, q_hhi, q_hsh;
   std::vector<uint32_t> q_tier;  // DevPlan::q_tier: slots that lead from a score-tiered copy
   std::vector<uint32_t> q_pterm, q_ppos;  // phrase queries' (term, offset) rows; empty without phrase_len
-  std::vector<uint32_t> q_clause;         // DevPlan::q_clause (k_bphrase / k_group slots); empty unless fg_phrase_clauses
-                                          // or fg_group_clauses is on
+  std::vector<uint32_t> q_clause;         // DevPlan::q_clause (k_bphrase / k_group / k_field slots); empty unless
+                                          // fg_phrase_clauses, fg_group_clauses or fg_field_clauses is on
   std::vector<uint32_t> q_member;         // DevPlan::q_member (k_mgroup slots); empty unless fg_group_member_phrases
   std::vector<uint64_t> thr0;
   std::vector<float> q_ub, q_wt, q_wn, q_rup;
@@ -70,15 +72,15 @@ struct PlanTables {
   std::vector<uint64_t> f_woff;
   std::vector<float> f_tab, f_max;
   std::vector<uint32_t> ch_f, ch_c, ch_t, ch_s;
-  // work items: k_conj's, k_disj's, k_scan's, k_phrase's, k_bphrase's, k_group's, k_gphrase's, k_mgroup's; items: all
+  // work items: k_conj's, k_disj's, k_scan's, k_phrase's, k_bphrase's, k_group's, k_gphrase's, k_mgroup's, k_field's; items: all
   // of them as the kernels run them (order_items, joined tables only)
-  std::vector<WItem> citems, ditems, scan, phrase, bphrase, group, gphrase, mgroup, items;
+  std::vector<WItem> citems, ditems, scan, phrase, bphrase, group, gphrase, mgroup, field, items;
   // (a thread's plans reuse one set: assign / push_back into kept capacity, no
   // page faults on fresh arrays -- ~0.2 ms of an 8-snapshot batch's planning)
   void clear() {
     auto all = [](auto&... v) { (v.clear(), ...); };
     all(q_m, q_terms, lead, q_filter, ngroup, q_hlo, q_hhi, q_hsh, thr0, q_ub, q_wt, q_wn, q_rup, f_shift, f_seg, f_woff,
-        f_tab, f_max, ch_f, ch_c, ch_t, ch_s, citems, ditems, scan, phrase, bphrase, group, gphrase, mgroup, items, q_pterm, q_ppos, q_clause, q_member,
+        f_tab, f_max, ch_f, ch_c, ch_t, ch_s, citems, ditems, scan, phrase, bphrase, group, gphrase, mgroup, field, items, q_pterm, q_ppos, q_clause, q_member,
         q_probe, q_tier);
     nf = 0;
   }
@@ -737,11 +739,111 @@ int plan_member_group(const fg_index* ix, const fg_query_batch* q, uint32_t i, u
   return FG_OK;
 }
 
+// Query i of the batch when it holds a field-qualified term clause and
+// fg_field_clauses is on (the clause table was checked by plan_phrase: every clause
+// is one term, some carry FG_CLAUSE_TEXT / FG_CLAUSE_NAME): never
+// with facet clauses, whatever fg_filter_clauses says, else FG_EUNSUPPORTED.  A field
+// clause is that field's TermQuery: absent in a snapshot that lacks the term in
+// that field (df_text / df_name 0, or no name postings at all); absence, the order
+// of the score sum and the passes are plan_group's for single-member clauses.  A
+// clause's cost: an unqualified term's df_text + df_name, a field clause's the
+// field's doc count alone.  The slot's rows (q_terms / q_wt / q_wn / q_ub / q_rup,
+// one per clause) are plan_group's: q_ub / q_rup stay the MERGED term's, still upper
+// bounds of a one-field score (the other field's part is >= 0 and f32 addition is
+// monotone); the clause word carries the field (fg_internal.h kClText / kClName).
+// Work items (k_field): with a Must, groups of the chunks of the shortest merged
+// list among the Must clauses; without, a pass per Should clause.
+int plan_field(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t nq_size, uint32_t n_segs,
+               PlanTables& h, bool nomatch) {
+  const uint32_t b = q->q_off[i], e = q->q_off[i + 1];
+  if (q->f_off && q->f_off[i + 1] > q->f_off[i])
+    return fail(FG_EUNSUPPORTED, "query %u: field clause with facet filters", i);
+  auto len = [&](uint32_t t) { return (uint64_t)(ix->off[t + 1] - ix->off[t]); };
+  struct Cl { uint32_t t, oc, field; uint64_t cost; };
+  Cl cl[fg::kMaxTerms];
+  uint32_t ncl = 0, nm = 0, ns = 0;
+  bool must_missing = false;
+  for (uint32_t j = b; j < e; ++j) {
+    const uint32_t raw = q->phrase_len[j];
+    const uint32_t oc = q->occur ? q->occur[j] : (q->mode == FG_MODE_OR ? FG_OCCUR_SHOULD : FG_OCCUR_MUST);
+    if (oc > FG_OCCUR_MUST_NOT) return fail(FG_EINVAL, "query %u: bad occur %u", i, oc);
+    Cl c{fgh::local_term(ix, q->terms[j]), oc, raw & FG_CLAUSE_TEXT ? fg::kClText : raw & FG_CLAUSE_NAME ? fg::kClName : 0u, 0};
+    bool present = c.t < ix->n_terms && ix->off[c.t + 1] > ix->off[c.t];
+    if (present) {
+      const uint64_t dt = ix->df_text[c.t], dn = ix->d.tfn_name ? ix->df_name[c.t] : 0;
+      c.cost = c.field == fg::kClText ? dt : c.field == fg::kClName ? dn : (uint64_t)ix->df_text[c.t] + ix->df_name[c.t];
+      present = !c.field || c.cost > 0;  // a field clause: the term has postings in that field here
+    }
+    if (!present) {
+      must_missing |= oc == FG_OCCUR_MUST;
+      continue;
+    }
+    nm += oc == FG_OCCUR_MUST;
+    ns += oc == FG_OCCUR_SHOULD;
+    cl[ncl++] = c;
+  }
+  // a Must matches nothing, no positive clause, or facet clauses that match no doc: no hits
+  if (must_missing || nm + ns == 0 || nomatch) return FG_OK;
+  if (nm == 0 && ns == 1)
+    for (uint32_t c = 0; c < ncl; ++c)
+      if (cl[c].oc == FG_OCCUR_SHOULD) { cl[c].oc = FG_OCCUR_MUST; nm = 1; ns = 0; }
+  // the order of the score sum
+  auto rank = [&](const Cl& c) {
+    if (nm) return c.oc == FG_OCCUR_MUST ? 0 : c.oc == FG_OCCUR_MUST_NOT ? 1 : 2;
+    return c.oc == FG_OCCUR_SHOULD ? 0 : 1;
+  };
+  std::stable_sort(cl, cl + ncl, [&](const Cl& x, const Cl& y) {
+    const int rx = rank(x), ry = rank(y);
+    if (rx != ry) return rx < ry;
+    return nm && rx == 0 && x.cost < y.cost;  // (stable: ties and the other kinds by clause position)
+  });
+  const size_t row = (size_t)i * fg::kMaxTerms;
+  for (uint32_t c = 0; c < ncl; ++c) {
+    const uint32_t t = cl[c].t;
+    float rdn, rup;
+    fgh::term_ratio(ix, t, &rdn, &rup);
+    h.q_terms[row + c] = t;
+    h.q_wt[row + c] = ix->w_text[t];
+    h.q_wn[row + c] = ix->w_name[t];
+    h.q_rup[row + c] = rup;
+    h.q_ub[row + c] = fgh::term_max_scaled(ix, t, rup);
+    h.q_clause[row + c] = fg::cl_pack(c, 1, cl[c].oc, false, c) | cl[c].field;
+  }
+  h.q_m[i] = fg::qm_phrase(ncl, ncl);
+  // The slot starts at threshold 0 (h.thr0[i] stays 0) and takes no k-th floor: the
+  // snapshot's per-term K-th scores and ladder floors are scores of the MERGED
+  // clause, Should(text:t, name:t), not lower bounds of a one-field score; starting
+  // from them would drop hits.
+  // the passes: the Must clause with the shortest merged list, or every Should clause
+  uint32_t lo = 0, hi = nm ? 1 : ns;
+  for (uint32_t c = 1; c < nm; ++c)
+    if (len(cl[c].t) < len(cl[lo].t)) lo = c;
+  if (nm) hi = lo + 1;
+  const uint32_t cdiv = n_segs <= 1 ? 1u : n_segs;
+  const uint32_t per_q = std::max<uint32_t>(
+      1, std::min<uint32_t>(64, std::max<uint32_t>(fg::kConjGroupsPerQuery, 1024 / std::max(nq_size, 1u))) / cdiv);
+  h.lead[i] = (uint32_t)len(cl[lo].t);
+  uint32_t total = 0;
+  for (uint32_t c = lo; c < hi; ++c) {
+    const uint32_t nch = (uint32_t)((len(cl[c].t) + fg::kChunk - 1) / fg::kChunk);
+    if (h.field.size() + nch > 0x7FFFFFFFull)
+      return fail(FG_EUNSUPPORTED, "batch too large (%zu work items)", h.field.size());
+    const uint32_t G = std::min<uint32_t>(fg::kPhraseMaxGroup, std::max<uint32_t>(1, (nch + per_q - 1) / per_q));
+    const uint32_t ng = (nch + G - 1) / G;
+    for (uint32_t g = 0; g < ng; ++g)
+      h.field.push_back(WItem{(g + 0.5) / ng, i, g * G, std::min(G, nch - g * G) | (c << fg::kGrpClauseShift)});
+    total += ng;
+  }
+  h.ngroup[i] = total;
+  return FG_OK;
+}
+
 // Query i of the batch when it holds a phrase clause (fg_query_batch::phrase_len
 // >= 2; *phrase = 0 otherwise, after checking the clause table; a group clause,
 // fg_group_clauses, goes to plan_group, one beside a phrase clause, with
 // fg_group_phrase_clauses `gphrase`, to plan_group_phrase; a group that holds a
-// phrase member, with fg_group_member_phrases `members`, to plan_member_group): the device
+// phrase member, with fg_group_member_phrases `members`, to plan_member_group; a query
+// with a field-qualified term clause, fg_field_clauses `fields`, to plan_field): the device
 // subset -- the phrase is the query's only clause (`beside`, fg_phrase_clauses:
 // other clauses beside it go to plan_bool_phrase), facet clauses only with
 // `filters` (fg_filter_clauses; `nomatch`: they match no doc of the snapshot, so
@@ -754,13 +856,26 @@ int plan_member_group(const fg_index* ix, const fg_query_batch* q, uint32_t i, u
 // idfs summed in phrase order from 0.0 (a repeated term each time), times
 // (1 + K1).  Work items (k_phrase): groups of the lead list's chunks, as k_conj's.
 int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t nq_size, uint32_t n_segs,
-                PlanTables& h, int* phrase, bool beside, bool groups, bool filters, bool gphrase, bool members, bool nomatch) {
+                PlanTables& h, int* phrase, bool beside, bool groups, bool filters, bool gphrase, bool members, bool fields,
+                bool nomatch) {
   *phrase = 0;
   const uint32_t b = q->q_off[i], e = q->q_off[i + 1], m = e - b;
-  uint32_t n_clauses = 0, n_phr = 0, n_grp = 0;
+  uint32_t n_clauses = 0, n_phr = 0, n_grp = 0, n_fld = 0;
   bool has_pm = false;  // a group holds a nonzero offset: a phrase member (fg_group_member_phrases)
   for (uint32_t j = b; j < e;) {
     uint32_t n = q->phrase_len[j];
+    // a field clause (fg_field_clauses; off: the flags make n a bad phrase_len, as before): a plain term
+    // clause's entry with FG_CLAUSE_TEXT or FG_CLAUSE_NAME on it
+    if (fields && (n & (FG_CLAUSE_TEXT | FG_CLAUSE_NAME))) {
+      if ((n & (FG_CLAUSE_TEXT | FG_CLAUSE_NAME)) == (FG_CLAUSE_TEXT | FG_CLAUSE_NAME))
+        return fail(FG_EINVAL, "query %u: bad phrase_len at term %u", i, j - b);
+      if (n & (FG_CLAUSE_ANY | FG_CLAUSE_ALL)) return fail(FG_EUNSUPPORTED, "query %u: field-qualified group", i);
+      if ((n & ~(FG_CLAUSE_TEXT | FG_CLAUSE_NAME)) != 1) return fail(FG_EUNSUPPORTED, "query %u: field-qualified phrase", i);
+      ++n_fld;
+      ++n_clauses;
+      ++j;
+      continue;
+    }
     // a group clause (fg_group_clauses; off: the flags make n a bad phrase_len, as before)
     const uint32_t kind = groups ? n & (FG_CLAUSE_ANY | FG_CLAUSE_ALL) : 0u;
     if (kind) {
@@ -768,6 +883,8 @@ int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_
       if (kind == (FG_CLAUSE_ANY | FG_CLAUSE_ALL) || n < 2 || n > e - j)
         return fail(FG_EINVAL, "query %u: bad phrase_len at term %u", i, j - b);
       for (uint32_t x = 0; x < n; ++x) {
+        if (x && fields && (q->phrase_len[j + x] & (FG_CLAUSE_TEXT | FG_CLAUSE_NAME)))
+          return fail(FG_EUNSUPPORTED, "query %u: field-qualified group", i);
         if (x && q->phrase_len[j + x] != 0) return fail(FG_EINVAL, "query %u: phrase_len inside a group must be 0", i);
         const uint32_t pp = q->phrase_pos[j + x];
         if (!members || x == 0) {
@@ -802,6 +919,12 @@ int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_
     }
     ++n_clauses;
     j += n;
+  }
+  if (n_fld) {  // (whatever the other switches say)
+    *phrase = 1;
+    if (n_phr) return fail(FG_EUNSUPPORTED, "query %u: field clause beside a phrase clause", i);
+    if (n_grp) return fail(FG_EUNSUPPORTED, "query %u: field clause beside a group clause", i);
+    return plan_field(ix, q, i, nq_size, n_segs, h, nomatch);
   }
   if (n_grp) {
     *phrase = 1;
@@ -869,10 +992,11 @@ int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_
 // that batch: plan_pieces plans a snapshot's queries in pieces)
 // qtime: the plan forms its scores at query time (some snapshot's statistics
 // changed since its build: DevPlan::feat), so the descriptors point at payloads
-// beside, groups, filters, gphrase, members: fg_phrase_clauses, fg_group_clauses, fg_filter_clauses,
-// fg_group_phrase_clauses, fg_group_member_phrases as the plan's creation read them
+// beside, groups, filters, gphrase, members, fields: fg_phrase_clauses, fg_group_clauses, fg_filter_clauses,
+// fg_group_phrase_clauses, fg_group_member_phrases, fg_field_clauses as the plan's creation read them
 int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t n_segs, PlanTables& h,
-              uint32_t nq_size, bool qtime, bool beside, bool groups, bool filters, bool gphrase, bool members) {
+              uint32_t nq_size, bool qtime, bool beside, bool groups, bool filters, bool gphrase, bool members,
+              bool fields) {
   if (!ix || !q || (q->n_queries && !q->q_off)) return fail(FG_EINVAL, "bad arguments");
   if (q->n_queries && q->q_off[q->n_queries] > q->q_off[0] && !q->terms) return fail(FG_EINVAL, "q_off without terms");
   if (q->f_off && q->n_queries && q->f_off[q->n_queries] > q->f_off[0] && !q->f_terms)
@@ -898,7 +1022,7 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
     if (!q->phrase_pos) return fail(FG_EINVAL, "phrase_len without phrase_pos");
     h.q_pterm.assign(nqt, 0);
     h.q_ppos.assign(nqt, 0);
-    if (beside || groups) h.q_clause.assign(nqt, 0);
+    if (beside || groups || fields) h.q_clause.assign(nqt, 0);
     if (groups && members) h.q_member.assign(nqt, 0);
   }
 
@@ -1019,7 +1143,9 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
     if (m > fg::kMaxTerms) return fail(FG_EUNSUPPORTED, "query %u has %u terms (> %u)", i, m, fg::kMaxTerms);
     if (q->phrase_len) {
       int phrase = 0;
-      if (int rc = plan_phrase(ix, q, i, nq_size, n_segs, h, &phrase, beside, groups, filters, gphrase, members, q_nomatch[i] != 0)) return rc;
+      if (int rc = plan_phrase(ix, q, i, nq_size, n_segs, h, &phrase, beside, groups, filters, gphrase, members, fields,
+                               q_nomatch[i] != 0))
+        return rc;
       if (phrase) continue;
     }
     if (q_nomatch[i]) continue;  // the facet clauses match nothing: no hits
@@ -1240,7 +1366,8 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
   const bool filters = filter_clauses_on.load(std::memory_order_relaxed) != 0;
   const bool gphrase = group_phrase_clauses_on.load(std::memory_order_relaxed) != 0;
   const bool members = group_member_phrases_on.load(std::memory_order_relaxed) != 0;
-  if (S == 1) return plan_host(ixs[0], q, k, S, hs[0], nq1, qt, beside, groups, filters, gphrase, members);  // (used in place: nothing to join)
+  const bool fields = field_clauses_on.load(std::memory_order_relaxed) != 0;
+  if (S == 1) return plan_host(ixs[0], q, k, S, hs[0], nq1, qt, beside, groups, filters, gphrase, members, fields);  // (used in place: nothing to join)
   J.clear();
   const size_t nq = (size_t)S * nq1, nqt = nq * fg::kMaxTerms;
   for (auto* v : {&J.q_m, &J.lead, &J.ngroup, &J.q_tier}) v->resize(nq);
@@ -1250,7 +1377,7 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
   J.q_probe.resize(nqt);
   if (q->phrase_len)
     for (auto* v : {&J.q_pterm, &J.q_ppos}) v->resize(nqt);
-  if (q->phrase_len && (beside || groups)) J.q_clause.resize(nqt);
+  if (q->phrase_len && (beside || groups || fields)) J.q_clause.resize(nqt);
   if (q->phrase_len && groups && members) J.q_member.resize(nqt);
   auto put_slot = [&](uint32_t p) {  // piece p's per-query tables into its slots
     const PlanTables& h = hs[p];
@@ -1274,14 +1401,14 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
       qp.n_queries = b - a;
       qp.q_off = q->q_off + a;
       if (q->f_off) qp.f_off = q->f_off + a;
-      if ((rcs[p] = plan_host(ixs[p / pc.P], &qp, k, S, hs[p], nq1, qt, beside, groups, filters, gphrase, members))) errs[p] = fg_last_error();
+      if ((rcs[p] = plan_host(ixs[p / pc.P], &qp, k, S, hs[p], nq1, qt, beside, groups, filters, gphrase, members, fields))) errs[p] = fg_last_error();
       else put_slot(p);
     });
     for (uint32_t p = 0; p < n; ++p)
       if (rcs[p]) return fail(rcs[p], "snapshot %u: %s", p / pc.P, errs[p].c_str());
   } else {
     for (uint32_t s = 0; s < S; ++s) {
-      if (int rc = plan_host(ixs[s], q, k, S, hs[s], nq1, qt, beside, groups, filters, gphrase, members)) {
+      if (int rc = plan_host(ixs[s], q, k, S, hs[s], nq1, qt, beside, groups, filters, gphrase, members, fields)) {
         const std::string e = fg_last_error();
         return fail(rc, "snapshot %u: %s", s, e.c_str());
       }
@@ -1319,6 +1446,7 @@ PlanTables& join_pieces(const Pieces& pc, std::vector<PlanTables>& hs, PlanTable
     for (WItem x : h.group) { x.q += vb; J.group.push_back(x); }
     for (WItem x : h.gphrase) { x.q += vb; J.gphrase.push_back(x); }
     for (WItem x : h.mgroup) { x.q += vb; J.mgroup.push_back(x); }
+    for (WItem x : h.field) { x.q += vb; J.field.push_back(x); }
     J.nf += h.nf;
   }
   // one bin geometry per batch query over the snapshots where it has work
@@ -1434,9 +1562,9 @@ void sort_sweep(std::vector<WItem>& items, bool conj, const PlanTables& t, uint3
 struct WorkList {
   std::vector<uint32_t> work_q, work_c, work_n;
   std::vector<uint64_t> cand_off;
-  uint64_t n_single = 0, n_conj = 0, n_main = 0, n_scan = 0, n_phrase = 0, n_bphrase = 0, n_group = 0, n_gphrase = 0, n_mgroup = 0;
+  uint64_t n_single = 0, n_conj = 0, n_main = 0, n_scan = 0, n_phrase = 0, n_bphrase = 0, n_group = 0, n_gphrase = 0, n_mgroup = 0, n_field = 0;
   uint32_t xcd_first[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // DevPlan::xcd_first
-  uint64_t count() const { return n_main + n_scan + n_phrase + n_bphrase + n_group + n_gphrase + n_mgroup; }
+  uint64_t count() const { return n_main + n_scan + n_phrase + n_bphrase + n_group + n_gphrase + n_mgroup + n_field; }
 };
 
 // k_conj's multi-list items (sorted) cut into the 8 XCDs' stretches by expected
@@ -1471,13 +1599,13 @@ void xcd_stretches(const PlanTables& t, WorkList& w) {
 int order_items(PlanTables& t, uint32_t nq, uint32_t k, WorkList& w) {
   if (t.f_woff[t.nf] * 4 > (8ull << 30)) return fail(FG_EUNSUPPORTED, "facet masks of this batch exceed 8 GiB");
   if (t.ch_f.size() > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "facet postings of this batch too large");
-  if (t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size() + t.mgroup.size() > 0x7FFFFFFFull)
+  if (t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size() + t.mgroup.size() + t.field.size() > 0x7FFFFFFFull)
     return fail(FG_EUNSUPPORTED, "batch too large (%zu work items)",
-                t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size() + t.mgroup.size());
+                t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size() + t.mgroup.size() + t.field.size());
   sort_sweep(t.citems, true, t, nq);
   sort_sweep(t.ditems, false, t, nq);
   auto& items = t.items;
-  items.reserve(t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size() + t.mgroup.size());
+  items.reserve(t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size() + t.mgroup.size() + t.field.size());
   items.insert(items.end(), t.citems.begin(), t.citems.end());
   w.n_conj = t.citems.size();
   items.insert(items.end(), t.ditems.begin(), t.ditems.end());
@@ -1502,7 +1630,10 @@ int order_items(PlanTables& t, uint32_t nq, uint32_t k, WorkList& w) {
   // k_mgroup: the same sweep
   std::stable_sort(t.mgroup.begin(), t.mgroup.end(), [](const WItem& a, const WItem& b) { return a.key < b.key; });
   w.n_mgroup = t.mgroup.size();
-  const uint64_t chunks = w.count();  // work items (k_conj / k_disj, then k_scan, k_phrase, k_bphrase, k_group, k_gphrase, k_mgroup)
+  // k_field: the same sweep
+  std::stable_sort(t.field.begin(), t.field.end(), [](const WItem& a, const WItem& b) { return a.key < b.key; });
+  w.n_field = t.field.size();
+  const uint64_t chunks = w.count();  // work items (k_conj / k_disj, then k_scan, k_phrase, k_bphrase, k_group, k_gphrase, k_mgroup, k_field)
   if (chunks > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "batch too large (%llu work items)", (unsigned long long)chunks);
   items.insert(items.end(), t.scan.begin(), t.scan.end());
   items.insert(items.end(), t.phrase.begin(), t.phrase.end());
@@ -1510,6 +1641,7 @@ int order_items(PlanTables& t, uint32_t nq, uint32_t k, WorkList& w) {
   items.insert(items.end(), t.group.begin(), t.group.end());
   items.insert(items.end(), t.gphrase.begin(), t.gphrase.end());
   items.insert(items.end(), t.mgroup.begin(), t.mgroup.end());
+  items.insert(items.end(), t.field.begin(), t.field.end());
   w.work_q.resize(chunks);
   w.work_c.resize(chunks);
   w.work_n.resize(chunks);
@@ -1708,6 +1840,7 @@ void fill_view(fg_plan* p, fg_index* const* ixs, PlanTables& t, const WorkList& 
   p->d.n_group = (uint32_t)w.n_group;
   p->d.n_gphrase = (uint32_t)w.n_gphrase;
   p->d.n_mgroup = (uint32_t)w.n_mgroup;
+  p->d.n_field = (uint32_t)w.n_field;
   p->d.n_single = (uint32_t)w.n_single;
   std::copy(w.xcd_first, w.xcd_first + 9, p->d.xcd_first);
   p->d.k = p->k;
@@ -1817,6 +1950,11 @@ int fg_group_phrase_clauses(int on) {
 int fg_group_member_phrases(int on) {
   if (on < 0) return group_member_phrases_on.load(std::memory_order_relaxed);
   return group_member_phrases_on.exchange(on != 0 ? 1 : 0, std::memory_order_relaxed);
+}
+
+int fg_field_clauses(int on) {
+  if (on < 0) return field_clauses_on.load(std::memory_order_relaxed);
+  return field_clauses_on.exchange(on != 0 ? 1 : 0, std::memory_order_relaxed);
 }
 
 int fg_plan_tiered_slots(const fg_plan* p, uint32_t* out) {

@@ -501,6 +501,41 @@ int fg_group_phrase_clauses(int on);
  * fg_count_batch is untouched. */
 int fg_group_member_phrases(int on);
 
+/* Field-qualified term clauses -- `name:report`, `text:error`, `+name:report
+ * +quarterly`: tantivy's TermQuery on ONE of the two default fields -- run on the
+ * device (k_field) when on != 0.  The contract of fg_group_clauses:
+ * process-wide, off by default, read when a plan is created; on: 1 / 0 sets it,
+ * < 0 only asks; returns the previous setting.  It consults none of the other
+ * switches.  Off: every entry point answers as before (such an entry is
+ * FG_EINVAL "bad phrase_len at term N").
+ * A field clause is a plain term clause whose phrase_len entry carries
+ * FG_CLAUSE_TEXT or FG_CLAUSE_NAME: the entry is flag | 1, phrase_pos 0.  It
+ * matches a doc that holds the term in THAT field (the field's tf > 0; a doc in
+ * the term's list because of the other field alone does not match) and scores
+ * the field's part alone, w_field * (tf / (tf + cache_field[fieldnorm_field])) in
+ * f32 under the statistics the unqualified clause uses: the bits of the
+ * unqualified clause on a doc that holds the term in that field only.  Among the
+ * Musts the order is (cost, position); a field clause's cost is the snapshot's
+ * doc count of the term in that field, an unqualified clause's stays df_text +
+ * df_name.  The clauses join as the term clauses of `occur` do.  A snapshot that
+ * lacks the term in that field (or has no name postings at all, for
+ * FG_CLAUSE_NAME) lacks the clause: a Must empties the query there, a Should or
+ * MustNot drops out.  (The cost rule is stated as upstream knowledge; it is not
+ * pinned against tantivy.)
+ * The device subset: the query holds at least one field clause and all its
+ * other clauses are plain term clauses, any occur, within FG_MAX_TERMS.  A query
+ * without a field clause plans exactly as before.
+ * FG_EINVAL "bad phrase_len at term N": both flags on one entry.
+ * FG_EUNSUPPORTED, whatever the other switches say: a field flag on an entry
+ * whose count is not 1 ("field-qualified phrase"), together with FG_CLAUSE_ANY /
+ * FG_CLAUSE_ALL or on a group's member row ("field-qualified group"), "field
+ * clause beside a phrase clause", "field clause beside a group clause", "field
+ * clause with facet filters", a field clause in fg_model_batch, and one in
+ * fg_count_batch ("field clause in a count query"). */
+#define FG_CLAUSE_TEXT 0x20000000u
+#define FG_CLAUSE_NAME 0x10000000u
+int fg_field_clauses(int on);
+
 /* Plan a batch: host-side query planning (tantivy Weight creation: terms
  * ordered by cost, query/intersection.rs) and upload of the plan to HBM.
  * Returns FG_EUNSUPPORTED for queries outside the device subset

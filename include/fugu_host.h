@@ -53,7 +53,11 @@
  * `e-mail AND server OR host` -- unless fg_group_member_phrases(1) is set as well
  * (fugu.h; process-wide, off by default: k_mgroup), a phrase or a group with filters unless
  * fg_filter_clauses(1) is set (fugu.h; process-wide, off by default), slop / prefix
- * suffixes on a quoted literal, field:,
+ * suffixes on a quoted literal, field: -- unless fg_field_clauses(1) is set (fugu.h;
+ * process-wide, off by default: k_field), with which `text:WORD` / `name:WORD`, WORD a
+ * plain word of one token, is that field's TermQuery; fg_parse_query_clauses prints it
+ * "<occur>:name:report@0", fg_parse_query and fg_parse_query_occur refuse it, and so do
+ * the count entry points --,
  * boosts, a text query with filters that parse to no facet term) return
  * FG_EUNSUPPORTED: the reference host then runs tantivy; this library never
  * answers them on the CPU.  Empty queries (AllQuery), facet-only queries and

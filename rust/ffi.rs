@@ -44,6 +44,8 @@ pub const FG_OCCUR_SHOULD: u8 = 1;
 pub const FG_OCCUR_MUST_NOT: u8 = 2;
 pub const FG_CLAUSE_ANY: u32 = 0x8000_0000;  // phrase_len flags of a group clause (fg_group_clauses)
 pub const FG_CLAUSE_ALL: u32 = 0x4000_0000;
+pub const FG_CLAUSE_TEXT: u32 = 0x2000_0000;  // phrase_len flags of a field-qualified term clause (fg_field_clauses)
+pub const FG_CLAUSE_NAME: u32 = 0x1000_0000;
 pub const FG_FIELD_TEXT: c_int = 0;
 pub const FG_FIELD_NAME: c_int = 1;
 pub const FG_FIELD_FACET: c_int = 2;
@@ -260,6 +262,7 @@ extern "C" {
     pub fn fg_filter_clauses(on: c_int) -> c_int;
     pub fn fg_group_phrase_clauses(on: c_int) -> c_int;
     pub fn fg_group_member_phrases(on: c_int) -> c_int;
+    pub fn fg_field_clauses(on: c_int) -> c_int;
     pub fn fg_plan_create(ix: *mut fg_index, q: *const fg_query_batch, k: u32, out: *mut *mut fg_plan) -> c_int;
     pub fn fg_plan_create_multi(ixs: *const *mut fg_index, n_segs: u32, q: *const fg_query_batch, k: u32,
                                 out: *mut *mut fg_plan) -> c_int;
