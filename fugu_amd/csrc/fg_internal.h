@@ -764,6 +764,15 @@ struct DevPlan {
                                 // Such a slot's q_terms / q_pterm / q_ppos rows hold every clause's terms
                                 // (local ids / vocabulary ids / offsets), clause after clause in q_clause's
                                 // order, a phrase's anchor first; q_wt / q_wn [row][c] are clause c's weights
+  uint32_t n_fphrase;           // k_fphrase work items (queries with a field-qualified phrase clause,
+                                // `name:"annual report"`, or a field term clause beside a phrase clause:
+                                // fg_field_phrases), after the k_field items.  Such a slot's q_m,
+                                // q_clause row, q_terms / q_pterm / q_ppos rows and work_n are k_bphrase's, a
+                                // field clause -- a term or a phrase (kClPhrase) -- marked kClText or kClName:
+                                // present where THAT field holds the term (the phrase), scored by that field's
+                                // part alone.  A field phrase's first row, the anchor, is its term with the
+                                // fewest postings in that field; q_wt / q_wn [c] hold clause c's weights, of
+                                // which a field clause uses its field's
   const uint32_t* q_clause;     // [nq * kMaxTerms] the clause table (cl_pack); empty without such a slot
   uint32_t n_group;             // k_group work items (queries with a group clause: fg_group_clauses), after the
                                 // k_bphrase items: (query slot, group of kChunk-posting chunks of a lead list,
@@ -1099,6 +1108,7 @@ hipError_t launch_group(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 hipError_t launch_gphrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 hipError_t launch_mgroup(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 hipError_t launch_field(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
+hipError_t launch_fphrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s);
 // out_shard != nullptr: the merged select of a multi-snapshot plan (one list per batch query)
 hipError_t launch_final(const DevPlan& pl, float* out_score, uint32_t* out_doc, uint32_t* out_n, hipStream_t s,
                         uint32_t* out_shard = nullptr);

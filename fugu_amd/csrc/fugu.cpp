@@ -921,6 +921,7 @@ static int execute_impl(fg_plan* p, hipStream_t s, float* os, uint32_t* od, uint
   if (last && p->d.n_gphrase) HIPCHK(fg::launch_gphrase(p->d0, p->d, s));
   if (last && p->d.n_mgroup) HIPCHK(fg::launch_mgroup(p->d0, p->d, s));
   if (last && p->d.n_field) HIPCHK(fg::launch_field(p->d0, p->d, s));
+  if (last && p->d.n_fphrase) HIPCHK(fg::launch_fphrase(p->d0, p->d, s));
   if (p->profile) HIPCHK(hipEventRecord(ev[1], s));
   if (last) HIPCHK(fg::launch_final(p->d, os, od, on, s, oshard));
   if (p->profile) {

@@ -400,8 +400,11 @@ class DocStore {
 // With fg_field_clauses(1) (fugu.h; off by default) a word of the form
 // `text:WORD` or `name:WORD` -- the field name exactly as the schema writes it, WORD
 // a plain word of ONE token -- is that field's TermQuery: bare, behind `+` / `-`, or
-// an operand of the uniform AND / OR forms.  `name:"..."` and a WORD of several
-// tokens ("field-qualified phrase"), `name:(...)` and a field word inside
+// an operand of the uniform AND / OR forms.  With fg_field_phrases(1) as well
+//  WORD may analyze to several tokens (`name:e-mail`) or be a plain
+// quoted literal (`name:"annual report"`): that field's PhraseQuery, a literal of one
+// token its TermQuery; otherwise `name:"..."` and a WORD of several
+// tokens are refused ("field-qualified phrase").  `name:(...)` and a field word inside
 // parentheses or inside a mixed-infix AND-run ("field-qualified group") and any
 // other field (`id:`, `namespace:`: "field outside [text, name]") are FG_EUNSUPPORTED.
 // Anything else (mixed AND / OR and parentheses while that switch is off, field:
@@ -431,7 +434,8 @@ struct Clause {
   std::vector<std::string> terms;
   std::vector<uint32_t> pos;
   uint8_t group = 0;  // kGroupAny / kGroupAll; 0: a term or a phrase
-  uint8_t field = 0;  // kFieldText / kFieldName: a field-qualified term (fg_field_clauses); 0: both fields
+  uint8_t field = 0;  // kFieldText / kFieldName: a field-qualified term (fg_field_clauses) or, with
+                      // fg_field_phrases, phrase; 0: both fields
 };
 constexpr uint8_t kGroupAny = 1, kGroupAll = 2;
 constexpr uint8_t kFieldText = 1, kFieldName = 2;
@@ -564,7 +568,9 @@ int parse_group(std::string_view body, Clause& cl, std::string& why, bool member
 
 // A word `FIELD:WORD` (fg_field_clauses is on, w holds a `:`, the prefix is behind it): the field and the rest, or
 // `why` (a code < 0).  1: of that form; 0: not (an empty or non-word field name), the caller's checks answer as before.
-int field_word(std::string_view w, uint8_t& field, std::string_view& rest, std::string& why) {
+// phrases (fg_field_phrases): the rest may be a quoted literal "..." -- nothing behind the closing
+// quote (slop, prefix, boost), no `\` inside --, returned without its quotes, `quoted` set.
+int field_word(std::string_view w, bool phrases, uint8_t& field, std::string_view& rest, bool& quoted, std::string& why) {
   const size_t colon = w.find(':');
   if (colon == 0 || colon == std::string_view::npos) return 0;
   const std::string_view name = w.substr(0, colon);
@@ -575,7 +581,18 @@ int field_word(std::string_view w, uint8_t& field, std::string_view& rest, std::
     }
   if (name != "text" && name != "name") { why = "field outside [text, name]"; return FG_EUNSUPPORTED; }
   rest = w.substr(colon + 1);
-  if (!rest.empty() && rest[0] == '"') { why = "field-qualified phrase"; return FG_EUNSUPPORTED; }
+  if (!rest.empty() && rest[0] == '"') {
+    if (!phrases) { why = "field-qualified phrase"; return FG_EUNSUPPORTED; }
+    if (rest.find('"', 1) != rest.size() - 1) {
+      why = "query syntax beyond bare/+/-/AND/OR terms and plain quoted phrases (slop, prefix, boost)";
+      return FG_EUNSUPPORTED;
+    }
+    rest = rest.substr(1, rest.size() - 2);
+    if (rest.find('\\') != std::string_view::npos) { why = "escape inside a quoted literal"; return FG_EUNSUPPORTED; }
+    quoted = true;
+    field = name == "text" ? kFieldText : kFieldName;
+    return 1;
+  }
   if (rest.find('(') != std::string_view::npos || rest.find(')') != std::string_view::npos) {
     why = "field-qualified group";
     return FG_EUNSUPPORTED;
@@ -594,6 +611,7 @@ int parse_clauses(std::string_view q, std::vector<Clause>& out, std::string& why
   const bool groups = fg_group_clauses(-1) > 0;
   const bool members = groups && fg_group_member_phrases(-1) > 0;  // a group may hold phrase members
   const bool fields = fg_field_clauses(-1) > 0;  // `text:WORD` / `name:WORD`
+  const bool fphrases = fields && fg_field_phrases(-1) > 0;  // `name:"..."`, a WORD of several tokens
   struct Item { std::string_view body; bool quoted; bool prefixed; uint8_t occur; bool group = false; };
   std::vector<Item> items;
   auto space = [](char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r'; };
@@ -733,13 +751,14 @@ int parse_clauses(std::string_view q, std::vector<Clause>& out, std::string& why
     Clause cl;
     cl.occur = it.occur;
     std::string_view w = it.body;
+    bool quoted = it.quoted;
     if (fields && !it.quoted && w.find(':') != std::string_view::npos) {
       std::string_view rest;
-      const int rc = field_word(w, cl.field, rest, why);
+      const int rc = field_word(w, fphrases, cl.field, rest, quoted, why);
       if (rc < 0) return rc;
       if (rc > 0) w = rest;
     }
-    if (!it.quoted) {
+    if (!quoted) {
       if (w == "AND" || w == "OR" || w == "NOT" || w == "IN" || w == "TO") {
         why = "operator outside the supported forms";
         return FG_EUNSUPPORTED;
@@ -756,7 +775,7 @@ int parse_clauses(std::string_view q, std::vector<Clause>& out, std::string& why
       why = "a term analyzes to no token";
       return FG_EUNSUPPORTED;
     }
-    if (cl.field && cl.terms.size() > 1) {
+    if (cl.field && cl.terms.size() > 1 && !fphrases) {
       why = "field-qualified phrase";
       return FG_EUNSUPPORTED;
     }
@@ -784,7 +803,7 @@ int parse_query(std::string_view q, std::vector<std::string>& terms, std::vector
       return FG_EUNSUPPORTED;
     }
     if (c.field) {
-      why = "a field-qualified term";
+      why = c.terms.size() > 1 ? "a field-qualified phrase" : "a field-qualified term";
       return FG_EUNSUPPORTED;
     }
     if (c.terms.size() != 1) {

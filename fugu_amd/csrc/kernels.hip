@@ -2447,6 +2447,8 @@ __global__ __launch_bounds__(kThreads) void k_phrase(DevIndex ix0, DevPlan pl) {
 // A slot with a facet filter (fg_filter_clauses): (a) drops a doc
 // whose clause bits are 0 -- from every pass alike, so a hit still leaves exactly
 // one pass -- and (b) adds f_tab[bits] after the clauses are joined.
+// (k_fphrase below repeats this kernel's stages and join with a field per clause: a change here is to be
+// mirrored there by hand.)
 struct BPhraseShared {
   ScanShared s;
   uint64_t queue[kChunk];      // survivors (doc ids)
@@ -3556,6 +3558,219 @@ __global__ __launch_bounds__(kThreads, 4) void k_field(DevIndex ix0, DevPlan pl)
   flush_candidates(pl, q, sh.s.buf, sh.s.n_buf, sh.s.thr, sh.s.scratch);
 }
 
+// ---------------------------------------------------------------- k_fphrase
+// Queries with a field-qualified phrase clause (`name:"annual report"`, `name:e-mail`,
+// `+name:"q3 report" +budget`) or a field term clause beside a phrase clause
+// (`name:report e-mail`): tantivy's PhraseQuery / TermQuery on ONE field;
+// fg_field_phrases on top of fg_field_clauses, DESIGN.md §21.  The slot is
+// k_bphrase's -- the clause table in the order of the score sum, the clauses' terms
+// clause after clause in q_terms / q_pterm / q_ppos, a phrase's anchor first, a
+// clause's weights in q_wt / q_wn -- with a field clause marked kClText or kClName;
+// the work items, the lead (the first term of the pass's clause, its MERGED list),
+// the passes and the join are k_bphrase's too: a lane per lead doc in (a), a wave
+// per survivor in (b).  What the field adds:
+//  (a) field drop: when the pass's clause names a field, the lane reads the lead
+//      posting's tf byte of that field (tfn / tfn_name low byte; coalesced, one
+//      byte per lead doc) and drops a doc whose byte is 0 -- the doc is in the
+//      merged list for the other field alone -- before the probes and before a wave
+//      is spent on it;
+//  (b) per-field presence: each of the n lanes that looked a field clause's term up
+//      reads that term's tf byte of the named field from its own posting; the
+//      clause goes on only if every term has a nonzero byte there (an escaped byte,
+//      kTfEsc, is nonzero).  A field phrase walks the named field's forward index
+//      alone and scores field_score(count, the first term's posting's fieldnorm of
+//      that field, the clause's weight of that field): 0.0 + the part, the bits of
+//      the unqualified phrase clause on a doc that holds the phrase in that field
+//      only.  A field term zeroes the other field's tf as k_field's field_member
+//      does.  An unqualified clause is scored bit for bit as k_bphrase scores it;
+//  (d) lone-clause bound: a slot whose only clause is a field phrase applies
+//      k_phrase's lead-tf bound restricted to the named field in (a) -- the
+//      phrase's count in the field is at most the lead term's tf there, and
+//      field_score rises with the count (an escaped byte: the weight itself) -- against
+//      the threshold read at the chunk's start.  Slots with several clauses verify
+//      every survivor, as k_bphrase does.
+// A MustNot or earlier-pass field TERM clause is not probed in (a): the merged
+// list says nothing about one field; (b) decides it.
+// (The stages and the join repeat k_bphrase's: a change to either copy is to be mirrored in the other by hand.)
+template <bool kMulti>
+__global__ __launch_bounds__(kThreads, 4) void k_fphrase(DevIndex ix0, DevPlan pl) {
+  __shared__ BPhraseShared sh;
+  const uint32_t tid = threadIdx.x, lane = lane_id();
+  // after the k_field items
+  const uint32_t w = pl.total_chunks + pl.n_scan + pl.n_phrase + pl.n_bphrase + pl.n_group + pl.n_gphrase + pl.n_mgroup +
+                     pl.n_field + blockIdx.x;
+  const uint32_t q = pl.work_q[w];
+  const DevIndex ix = kMulti ? seg_index(pl, __builtin_amdgcn_readfirstlane(q / pl.seg_nq)) : ix0;
+  const uint32_t ql = kMulti ? __builtin_amdgcn_readfirstlane(q % pl.seg_nq) : q;
+  const uint32_t chunk0 = pl.work_c[w];
+  const uint32_t nchunk = pl.work_n[w] & ((1u << kBpPassShift) - 1u);
+  const uint32_t K = pl.k;
+  uint64_t* gthr = &pl.thresh[ql];
+  const uint64_t thr0 = pl.q_thr0[q];  // the plan's starting threshold (0 for these slots: plan_field_phrase)
+  const uint32_t qm = pl.q_m[q];
+  const uint32_t ncl = min(qm_terms(qm), kMaxTerms), nt = min(qm_phrase_terms(qm), kMaxTerms);
+  if (ncl == 0 || nt == 0) return;  // (never planned; uniform)
+  const uint32_t pass = min(pl.work_n[w] >> kBpPassShift, ncl - 1);
+  const size_t row = (size_t)q * kMaxTerms;
+  if (tid < nt) {
+    const uint32_t t = pl.q_terms[row + tid];
+    sh.lterm[tid] = t;
+    sh.pterm[tid] = pl.q_pterm[row + tid];
+    sh.ppos[tid] = pl.q_ppos[row + tid];
+    sh.tmeta[tid] = ix.tmeta[t];
+    sh.tdir[tid] = ix.dir_off[t];
+    sh.toff[tid] = ix.off[t];
+    sh.act[tid] = 0;
+  }
+  if (tid < ncl) {
+    sh.cl[tid] = pl.q_clause[row + tid];
+    sh.cwt[tid] = pl.q_wt[row + tid];
+    sh.cwn[tid] = pl.q_wn[row + tid];
+  }
+  if (tid == 0) {
+    sh.s.n_buf = 0;
+    sh.n_q = 0;
+    sh.s.thr = start_threshold(pl, thr0, ql, gthr);
+  }
+  __syncthreads();
+  const bool must = cl_occur(sh.cl[0]) == kClMust;  // (the Musts stand first)
+  if (tid < ncl) {
+    const uint32_t c = sh.cl[tid], oc = cl_occur(c), n = cl_terms(c), t0 = cl_first(c);
+    const bool required = must ? oc == kClMust : tid == pass;
+    // (a field term's absence from its field is not its absence from the merged list)
+    const bool barred = n == 1 && !(c & (kClText | kClName)) &&
+                        (oc == kClMustNot || (!must && oc == kClShould && tid < pass));
+    for (uint32_t x = t0; x < min(t0 + n, nt); ++x) sh.act[x] = required ? 1u : barred ? 2u : 0u;
+  }
+  __syncthreads();
+  const uint32_t pcw = sh.cl[pass];
+  const uint32_t li = min(cl_first(pcw), nt - 1);  // the lead: the pass clause's first term
+  const uint32_t lead = sh.lterm[li];
+  const uint64_t base = sh.toff[li];
+  const uint32_t df = (uint32_t)(ix.off[lead + 1] - base);
+  const bool name = ix.tfn_name != nullptr && ix.fwd_off_name != nullptr;
+  // the pass clause's field: its payload bytes ((fieldnorm << 8) | tf, little-endian), weight and tf cache
+  const uint32_t lfield = pcw & (kClText | kClName);
+  const uint8_t* __restrict__ lpay = reinterpret_cast<const uint8_t*>(lfield == kClName ? ix.tfn_name : ix.tfn);
+  const float lw = lfield == kClName ? sh.cwn[pass] : sh.cwt[pass];
+  const float* __restrict__ lcache = ix.cache + (lfield == kClName ? 256 : 0);
+  const bool lone = ncl == 1 && lfield != 0u && (pcw & kClPhrase) != 0u;
+  for (uint32_t c = 0; c < nchunk; ++c) {
+    // (a) the chunk's lead docs that are alive, hold the lead term in the pass clause's field, the required
+    // clauses' terms and none of the barred ones
+    const uint32_t i0 = (chunk0 + c) * kChunk;
+    const uint64_t thr_a = sh.s.thr;  // (uniform: written before the last barrier)
+    for (uint32_t j = 0; j < kItems; ++j) {
+      const uint32_t i = i0 + j * kThreads + tid;
+      bool keep = i < df;
+      uint32_t d = 0;
+      if (keep) {
+        d = ix.doc[base + i];
+        keep = doc_alive(ix, d);
+      }
+      if (keep && lfield) {
+        const uint32_t tb = lpay ? lpay[2 * (base + i)] : 0u;
+        keep = tb != 0u;
+        // (d) the only clause: no count in the field exceeds the lead term's tf there
+        if (keep && lone) {
+          const float ub = tb == kTfEsc ? lw : field_score(tb, lpay[2 * (base + i) + 1], lw, lcache);
+          keep = make_key(ub, d) >= thr_a;
+        }
+      }
+      for (uint32_t u = 0; u < nt; ++u) {
+        const uint32_t a = sh.act[u];
+        if (keep && a && u != li) keep = term_has_doc(ix, sh.tmeta[u], sh.toff[u], sh.tdir[u], d) == (a == 1u);
+      }
+      wave_append(keep, (uint64_t)d, sh.queue, &sh.n_q, kChunk);
+    }
+    __syncthreads();
+    // (b), (c) one wave per survivor, kRound survivors between truncations
+    const uint32_t nsv = min(sh.n_q, kChunk);
+    for (uint32_t r0 = 0; r0 < nsv; r0 += kRound) {
+      const uint64_t thr = sh.s.thr;
+      const uint32_t r1 = min(nsv, r0 + kRound);
+      for (uint32_t x = r0 + wave_id(); x < r1; x += kThreads / 64) {
+        const uint32_t d = __builtin_amdgcn_readfirstlane((uint32_t)sh.queue[x]);
+        float req = 0.0f, oth = 0.0f, opt = 0.0f;
+        uint32_t nm = 0;
+        bool any = false, drop = false;
+        for (uint32_t ci = 0; ci < ncl && !drop; ++ci) {
+          const uint32_t cw = sh.cl[ci], oc = cl_occur(cw), n = cl_terms(cw), t0 = min(cl_first(cw), nt - 1);
+          const uint32_t fld = cw & (kClText | kClName);
+          // every term of the clause in the doc -- a field clause: in that field? (a lane each); lane 0 holds
+          // the first term's posting
+          uint32_t pos = kInvalid;
+          bool have = false;
+          if (lane < n && t0 + lane < nt) {
+            pos = posting_pos(ix, sh.lterm[t0 + lane], d);
+            have = pos != kInvalid;
+            if (have && fld) {
+              const uint64_t pl_ = sh.toff[t0 + lane] + pos;
+              have = fld == kClName ? (name && (ix.tfn_name[pl_] & 0xFFu) != 0u) : (ix.tfn[pl_] & 0xFFu) != 0u;
+            }
+          }
+          const bool all = __ballot(have) == (1ull << n) - 1ull;
+          float s = 0.0f;
+          bool on = false;
+          if (all) {
+            const uint64_t p0 = sh.toff[t0] + __builtin_amdgcn_readfirstlane(pos);
+            uint32_t v = ix.tfn[p0];
+            if (ix.tfn_name) v |= (uint32_t)ix.tfn_name[p0] << 16;
+            v = __builtin_amdgcn_readfirstlane(v);
+            const float wt = sh.cwt[ci], wn = sh.cwn[ci];
+            if (!(cw & kClPhrase)) {
+              // a field term: the other field's tf zeroed (k_field's field_member)
+              if (fld == kClName) v &= 0xFFFF0000u;
+              if (fld == kClText) v &= 0x0000FFFFu;
+              s = tfn_score(ix, p0, v, wt, wn, ix.cache, ix.cache + 256);
+              on = true;
+            } else {
+              uint32_t span = 0;  // the phrase's largest offset
+              for (uint32_t j = 0; j < n; ++j) span = max(span, sh.ppos[t0 + j]);
+              uint32_t ct = 0, cn = 0;
+              if (fld != kClName && (v & 0xFFu))
+                ct = phrase_count_at(ix.fwd, ix.fwd_off[d], ix.fwd_off[d + 1], sh.pterm + t0, sh.ppos + t0, n, span);
+              if (fld != kClText && name && ((v >> 16) & 0xFFu))
+                cn = phrase_count_at(ix.fwd_name, ix.fwd_off_name[d], ix.fwd_off_name[d + 1], sh.pterm + t0,
+                                     sh.ppos + t0, n, span);
+              if (ct) s += field_score(ct, (v >> 8) & 0xFFu, wt, ix.cache);
+              if (cn) s += field_score(cn, v >> 24, wn, ix.cache + 256);
+              on = (ct | cn) != 0;
+            }
+          }
+          if (oc == kClMust) {
+            if (!on) drop = true;
+            else if (nm == 0) req = s;
+            else if (nm == 1) req = req + s;
+            else oth = oth + s;
+            ++nm;
+          } else if (oc == kClMustNot) {
+            drop = on;
+          } else if (!must && ci <= pass && on != (ci == pass)) {
+            drop = true;  // an earlier pass's doc, or the pass clause does not match
+          } else if (on) {
+            opt = opt + s;
+            any = true;
+          }
+        }
+        float sc = opt;
+        if (must) {
+          if (nm > 1) req = req + oth;
+          sc = 0.0f + req;
+          if (any) sc = sc + opt;
+        }
+        const uint64_t key = make_key(sc, d);
+        wave_append(lane == 0 && !drop && key >= thr, key, sh.s.buf, &sh.s.n_buf, kBufD);
+      }
+      __syncthreads();
+      scan_truncate(sh.s, K, kTrunc, gthr, false, pl.pub_mask, pl, ql);
+    }
+    if (tid == 0) sh.n_q = 0;
+    scan_truncate(sh.s, K, K, gthr, true, pl.pub_mask, pl, ql);
+  }
+  flush_candidates(pl, q, sh.s.buf, sh.s.n_buf, sh.s.thr, sh.s.scratch);
+}
+
 // ---------------------------------------------------------------- k_final
 // Dynamic LDS (80 KB: 2 workgroups per CU): candidate keys, the k winners,
 // the radix histogram.  Keeps 16-B alignment of the dynamic base (no static
@@ -3929,6 +4144,13 @@ hipError_t launch_field(const DevIndex& ix, const DevPlan& pl, hipStream_t s) {
   if (pl.n_field == 0) return hipSuccess;
   if (pl.segs) k_field<true><<<pl.n_field, kThreads, 0, s>>>(ix, pl);
   else k_field<false><<<pl.n_field, kThreads, 0, s>>>(ix, pl);
+  return hipGetLastError();
+}
+
+hipError_t launch_fphrase(const DevIndex& ix, const DevPlan& pl, hipStream_t s) {
+  if (pl.n_fphrase == 0) return hipSuccess;
+  if (pl.segs) k_fphrase<true><<<pl.n_fphrase, kThreads, 0, s>>>(ix, pl);
+  else k_fphrase<false><<<pl.n_fphrase, kThreads, 0, s>>>(ix, pl);
   return hipGetLastError();
 }
 

@@ -36,6 +36,9 @@ std::atomic<int> group_phrase_clauses_on{0};
 std::atomic<int> group_member_phrases_on{0};
 // fg_field_clauses: queries with a field-qualified term clause run on the device (k_field); the same contract
 std::atomic<int> field_clauses_on{0};
+// fg_field_phrases: on top of fg_field_clauses, a field may stand on a phrase clause and a field term beside a
+// phrase clause (k_fphrase); the same contract
+std::atomic<int> field_phrases_on{0};
 
 // stable LSD radix sort of `a` by its bits 32..63 (three 11-bit passes)
 void radix_sort_hi32(std::vector<uint64_t>& a, std::vector<uint64_t>& tmp) {
@@ -72,15 +75,15 @@ struct PlanTables {
   std::vector<uint64_t> f_woff;
   std::vector<float> f_tab, f_max;
   std::vector<uint32_t> ch_f, ch_c, ch_t, ch_s;
-  // work items: k_conj's, k_disj's, k_scan's, k_phrase's, k_bphrase's, k_group's, k_gphrase's, k_mgroup's, k_field's; items: all
+  // work items: k_conj's, k_disj's, k_scan's, k_phrase's, k_bphrase's, k_group's, k_gphrase's, k_mgroup's, k_field's, k_fphrase's; items: all
   // of them as the kernels run them (order_items, joined tables only)
-  std::vector<WItem> citems, ditems, scan, phrase, bphrase, group, gphrase, mgroup, field, items;
+  std::vector<WItem> citems, ditems, scan, phrase, bphrase, group, gphrase, mgroup, field, fphrase, items;
   // (a thread's plans reuse one set: assign / push_back into kept capacity, no
   // page faults on fresh arrays -- ~0.2 ms of an 8-snapshot batch's planning)
   void clear() {
     auto all = [](auto&... v) { (v.clear(), ...); };
     all(q_m, q_terms, lead, q_filter, ngroup, q_hlo, q_hhi, q_hsh, thr0, q_ub, q_wt, q_wn, q_rup, f_shift, f_seg, f_woff,
-        f_tab, f_max, ch_f, ch_c, ch_t, ch_s, citems, ditems, scan, phrase, bphrase, group, gphrase, mgroup, field, items, q_pterm, q_ppos, q_clause, q_member,
+        f_tab, f_max, ch_f, ch_c, ch_t, ch_s, citems, ditems, scan, phrase, bphrase, group, gphrase, mgroup, field, fphrase, items, q_pterm, q_ppos, q_clause, q_member,
         q_probe, q_tier);
     nf = 0;
   }
@@ -105,6 +108,8 @@ struct PlanTables {
 // groups of the chunks of the shortest list among the Must clauses' first terms;
 // without, one pass per Should clause over that clause's first term's list; the
 // clause led from rides in the item's count word above kBpPassShift.
+// (plan_field_phrase below repeats this function's absence rule, order, rows and item spreading with a field per
+// clause: a change here is to be mirrored there by hand.)
 int plan_bool_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t nq_size, uint32_t n_segs,
                      PlanTables& h, bool filters, bool nomatch) {
   const uint32_t b = q->q_off[i], e = q->q_off[i + 1];
@@ -838,12 +843,150 @@ int plan_field(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t
   return FG_OK;
 }
 
+// Query i of the batch when it holds a field-qualified phrase clause, or a field
+// term clause beside a phrase clause, and fg_field_phrases is on top of
+// fg_field_clauses (the clause table was checked by plan_phrase: term and phrase
+// clauses, some carrying FG_CLAUSE_TEXT / FG_CLAUSE_NAME, no group):
+// never with facet clauses, on a snapshot with positions, else FG_EUNSUPPORTED.
+// A field clause is that field's TermQuery / PhraseQuery: absent in a snapshot
+// where one of its terms has no posting in that field (df_text / df_name 0), and a
+// `name` clause also where the snapshot has no name postings or no name forward
+// index; absence, the order of the score sum and the passes are plan_bool_phrase's.
+// A clause's cost: an unqualified term's df_text + df_name and an unqualified
+// phrase's the sum over the fields of its terms' smallest doc count there, as
+// plan_bool_phrase's; a field term's the field's doc count (plan_field's); a field
+// phrase's the smallest doc count in that field among its terms -- the phrase's
+// rule with the other field's summand dropped.  The slot's rows are
+// plan_bool_phrase's, the clause word carrying the field (fg_internal.h kClText /
+// kClName) beside kClPhrase; a field phrase's first row, its anchor, is the first
+// occurrence of its term with the fewest postings in THAT field.  q_wt / q_wn [c]
+// hold clause c's weights; a field clause uses its field's.  The slot starts at
+// threshold 0 and takes no k-th floor, as plan_field argues.  Work items
+// (k_fphrase): with a Must, groups of the chunks of the shortest merged list among
+// the Must clauses' first terms; without, a pass per Should clause.
+// (The absence rule, the order, the rows and the item spreading repeat plan_bool_phrase's: a change to either
+// copy is to be mirrored in the other by hand.)
+int plan_field_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t nq_size, uint32_t n_segs,
+                      PlanTables& h, bool nomatch) {
+  constexpr uint32_t kFlags = FG_CLAUSE_TEXT | FG_CLAUSE_NAME;
+  const uint32_t b = q->q_off[i], e = q->q_off[i + 1];
+  if (q->f_off && q->f_off[i + 1] > q->f_off[i])
+    return fail(FG_EUNSUPPORTED, "query %u: field clause with facet filters", i);
+  if (!ix->has_positions) return fail(FG_EUNSUPPORTED, "query %u: snapshot built without positions", i);
+  const bool has_name = ix->d.tfn_name != nullptr && ix->d.fwd_off_name != nullptr;
+  auto len = [&](uint32_t t) { return ix->off[t + 1] - ix->off[t]; };
+  struct Cl { uint32_t at, n, oc, field, anchor; uint64_t cost; float wt, wn; };
+  Cl cl[fg::kMaxTerms];
+  uint32_t lt[fg::kMaxTerms];  // the query's terms as the snapshot's ids
+  uint32_t ncl = 0, nm = 0, ns = 0;
+  bool must_missing = false;
+  for (uint32_t j = b; j < e;) {
+    const uint32_t raw = q->phrase_len[j], n = raw & ~kFlags;
+    const uint32_t oc = q->occur ? q->occur[j] : (q->mode == FG_MODE_OR ? FG_OCCUR_SHOULD : FG_OCCUR_MUST);
+    if (oc > FG_OCCUR_MUST_NOT) return fail(FG_EINVAL, "query %u: bad occur %u", i, oc);
+    if (n >= 2 && q->phrase_pos[j + n - 1] >= (1u << 30)) return fail(FG_EINVAL, "query %u: phrase offset too large", i);
+    Cl c{j - b, n, oc, raw & FG_CLAUSE_TEXT ? fg::kClText : raw & FG_CLAUSE_NAME ? fg::kClName : 0u, 0, 0, 0.0f, 0.0f};
+    bool present = c.field != fg::kClName || has_name;
+    uint64_t ct = ~0ull, cn = ~0ull, ca = ~0ull;  // smallest doc counts: text, name; the anchor's in the clause's field
+    float it = 0.0f, in = 0.0f;
+    for (uint32_t x = 0; x < n && present; ++x) {
+      const uint32_t t = lt[c.at + x] = fgh::local_term(ix, q->terms[j + x]);
+      present = t < ix->n_terms && ix->off[t + 1] > ix->off[t];
+      if (!present) break;
+      const uint64_t dt = ix->df_text[t], dn = ix->df_name[t];
+      // a field clause: every term has postings in that field here
+      if ((c.field == fg::kClText && dt == 0) || (c.field == fg::kClName && dn == 0)) { present = false; break; }
+      ct = std::min(ct, dt);
+      cn = std::min(cn, dn);
+      it += ix->idf_text[t];
+      in += ix->idf_name[t];
+      const uint64_t fewest = c.field == fg::kClText ? dt : c.field == fg::kClName ? dn : (uint64_t)len(t);
+      if (fewest < ca) { ca = fewest; c.anchor = x; }
+    }
+    j += n;
+    if (!present) {
+      must_missing |= oc == FG_OCCUR_MUST;
+      continue;
+    }
+    c.cost = c.field == fg::kClText ? ct : c.field == fg::kClName ? cn : ct + cn;  // (one term: its own counts)
+    if (n == 1) {
+      c.wt = ix->w_text[lt[c.at]];
+      c.wn = ix->w_name[lt[c.at]];
+    } else {
+      c.wt = it * (1.0f + 1.2f);  // (1 + K1), as bm25_weight's
+      c.wn = in * (1.0f + 1.2f);
+    }
+    nm += oc == FG_OCCUR_MUST;
+    ns += oc == FG_OCCUR_SHOULD;
+    cl[ncl++] = c;
+  }
+  // a Must matches nothing, no positive clause, or facet clauses that match no doc: no hits
+  if (must_missing || nm + ns == 0 || nomatch) return FG_OK;
+  if (nm == 0 && ns == 1)
+    for (uint32_t c = 0; c < ncl; ++c)
+      if (cl[c].oc == FG_OCCUR_SHOULD) { cl[c].oc = FG_OCCUR_MUST; nm = 1; ns = 0; }
+  // the order of the score sum
+  auto rank = [&](const Cl& c) {
+    if (nm) return c.oc == FG_OCCUR_MUST ? 0 : c.oc == FG_OCCUR_MUST_NOT ? 1 : 2;
+    return c.oc == FG_OCCUR_SHOULD ? 0 : 1;
+  };
+  std::stable_sort(cl, cl + ncl, [&](const Cl& x, const Cl& y) {
+    const int rx = rank(x), ry = rank(y);
+    if (rx != ry) return rx < ry;
+    return nm && rx == 0 && x.cost < y.cost;  // (stable: ties and the other kinds by clause position)
+  });
+  const size_t row = (size_t)i * fg::kMaxTerms;
+  uint32_t first[fg::kMaxTerms], o = 0;
+  for (uint32_t c = 0; c < ncl; ++c) {
+    const Cl& x = cl[c];
+    first[c] = o;
+    for (uint32_t u = 0, at = 1; u < x.n; ++u) {
+      const uint32_t dst = o + (u == x.anchor ? 0 : at++);
+      h.q_terms[row + dst] = lt[x.at + u];
+      h.q_pterm[row + dst] = q->terms[b + x.at + u];
+      h.q_ppos[row + dst] = q->phrase_pos[b + x.at + u];
+    }
+    h.q_clause[row + c] = fg::cl_pack(o, x.n, x.oc, x.n >= 2, c) | x.field;
+    h.q_wt[row + c] = x.wt;
+    h.q_wn[row + c] = x.wn;
+    o += x.n;
+  }
+  h.q_m[i] = fg::qm_phrase(ncl, o);
+  // (h.thr0[i] stays 0: the per-term K-th scores are the merged clause's, plan_field)
+  // the passes: the Must clause with the shortest first list, or every Should clause
+  const uint32_t cdiv = n_segs <= 1 ? 1u : n_segs;
+  const uint32_t per_q = std::max<uint32_t>(
+      1, std::min<uint32_t>(64, std::max<uint32_t>(fg::kConjGroupsPerQuery, 1024 / std::max(nq_size, 1u))) / cdiv);
+  auto lead_len = [&](uint32_t c) { return (uint64_t)len(h.q_terms[row + first[c]]); };
+  uint32_t lo = 0, hi = nm ? 1 : ns;
+  if (nm)
+    for (uint32_t c = 1; c < nm; ++c)
+      if (lead_len(c) < lead_len(lo)) lo = c;
+  if (nm) hi = lo + 1;
+  h.lead[i] = (uint32_t)lead_len(lo);
+  uint32_t total = 0;
+  for (uint32_t c = lo; c < hi; ++c) {
+    const uint32_t nch = (uint32_t)((lead_len(c) + fg::kChunk - 1) / fg::kChunk);
+    if (h.fphrase.size() + nch > 0x7FFFFFFFull)
+      return fail(FG_EUNSUPPORTED, "batch too large (%zu work items)", h.fphrase.size());
+    const uint32_t G = std::min<uint32_t>(fg::kPhraseMaxGroup, std::max<uint32_t>(1, (nch + per_q - 1) / per_q));
+    const uint32_t ng = (nch + G - 1) / G;
+    for (uint32_t g = 0; g < ng; ++g)
+      h.fphrase.push_back(WItem{(g + 0.5) / ng, i, g * G, std::min(G, nch - g * G) | (c << fg::kBpPassShift)});
+    total += ng;
+  }
+  h.ngroup[i] = total;
+  return FG_OK;
+}
+
 // Query i of the batch when it holds a phrase clause (fg_query_batch::phrase_len
 // >= 2; *phrase = 0 otherwise, after checking the clause table; a group clause,
 // fg_group_clauses, goes to plan_group, one beside a phrase clause, with
 // fg_group_phrase_clauses `gphrase`, to plan_group_phrase; a group that holds a
 // phrase member, with fg_group_member_phrases `members`, to plan_member_group; a query
-// with a field-qualified term clause, fg_field_clauses `fields`, to plan_field): the device
+// with a field-qualified term clause, fg_field_clauses `fields`, to plan_field; one with a field-qualified
+// phrase clause, or a field term clause beside a phrase clause, fg_field_phrases `fphrases`, to
+// plan_field_phrase): the device
 // subset -- the phrase is the query's only clause (`beside`, fg_phrase_clauses:
 // other clauses beside it go to plan_bool_phrase), facet clauses only with
 // `filters` (fg_filter_clauses; `nomatch`: they match no doc of the snapshot, so
@@ -857,10 +1000,10 @@ int plan_field(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t
 // (1 + K1).  Work items (k_phrase): groups of the lead list's chunks, as k_conj's.
 int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_t nq_size, uint32_t n_segs,
                 PlanTables& h, int* phrase, bool beside, bool groups, bool filters, bool gphrase, bool members, bool fields,
-                bool nomatch) {
+                bool fphrases, bool nomatch) {
   *phrase = 0;
   const uint32_t b = q->q_off[i], e = q->q_off[i + 1], m = e - b;
-  uint32_t n_clauses = 0, n_phr = 0, n_grp = 0, n_fld = 0;
+  uint32_t n_clauses = 0, n_phr = 0, n_grp = 0, n_fld = 0, n_fphr = 0;  // (n_phr counts the field-qualified phrases too)
   bool has_pm = false;  // a group holds a nonzero offset: a phrase member (fg_group_member_phrases)
   for (uint32_t j = b; j < e;) {
     uint32_t n = q->phrase_len[j];
@@ -870,7 +1013,24 @@ int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_
       if ((n & (FG_CLAUSE_TEXT | FG_CLAUSE_NAME)) == (FG_CLAUSE_TEXT | FG_CLAUSE_NAME))
         return fail(FG_EINVAL, "query %u: bad phrase_len at term %u", i, j - b);
       if (n & (FG_CLAUSE_ANY | FG_CLAUSE_ALL)) return fail(FG_EUNSUPPORTED, "query %u: field-qualified group", i);
-      if ((n & ~(FG_CLAUSE_TEXT | FG_CLAUSE_NAME)) != 1) return fail(FG_EUNSUPPORTED, "query %u: field-qualified phrase", i);
+      const uint32_t cnt = n & ~(FG_CLAUSE_TEXT | FG_CLAUSE_NAME);
+      if (cnt != 1) {
+        if (!fphrases) return fail(FG_EUNSUPPORTED, "query %u: field-qualified phrase", i);
+        // a field-qualified phrase clause (fg_field_phrases): flag | n on a phrase clause's first entry, the
+        // other entries and the offsets as an unqualified phrase's
+        if (cnt == 0 || cnt > e - j) return fail(FG_EINVAL, "query %u: bad phrase_len at term %u", i, j - b);
+        for (uint32_t x = 1; x < cnt; ++x)
+          if (q->phrase_len[j + x] != 0) return fail(FG_EINVAL, "query %u: phrase_len inside a phrase must be 0", i);
+        if (q->phrase_pos[j] != 0) return fail(FG_EINVAL, "query %u: a phrase's first offset must be 0", i);
+        for (uint32_t x = 1; x < cnt; ++x)
+          if (q->phrase_pos[j + x] <= q->phrase_pos[j + x - 1])
+            return fail(FG_EINVAL, "query %u: phrase offsets must increase", i);
+        ++n_fphr;
+        ++n_phr;
+        ++n_clauses;
+        j += cnt;
+        continue;
+      }
       ++n_fld;
       ++n_clauses;
       ++j;
@@ -920,10 +1080,12 @@ int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_
     ++n_clauses;
     j += n;
   }
-  if (n_fld) {  // (whatever the other switches say)
+  if (n_fld || n_fphr) {  // (whatever the other switches say)
     *phrase = 1;
-    if (n_phr) return fail(FG_EUNSUPPORTED, "query %u: field clause beside a phrase clause", i);
-    if (n_grp) return fail(FG_EUNSUPPORTED, "query %u: field clause beside a group clause", i);
+    if (n_phr && !fphrases) return fail(FG_EUNSUPPORTED, "query %u: field clause beside a phrase clause", i);
+    if (n_grp && n_fld) return fail(FG_EUNSUPPORTED, "query %u: field clause beside a group clause", i);
+    if (n_grp) return fail(FG_EUNSUPPORTED, "query %u: field-qualified phrase beside a group clause", i);
+    if (n_phr) return plan_field_phrase(ix, q, i, nq_size, n_segs, h, nomatch);  // fg_field_phrases
     return plan_field(ix, q, i, nq_size, n_segs, h, nomatch);
   }
   if (n_grp) {
@@ -993,10 +1155,11 @@ int plan_phrase(const fg_index* ix, const fg_query_batch* q, uint32_t i, uint32_
 // qtime: the plan forms its scores at query time (some snapshot's statistics
 // changed since its build: DevPlan::feat), so the descriptors point at payloads
 // beside, groups, filters, gphrase, members, fields: fg_phrase_clauses, fg_group_clauses, fg_filter_clauses,
-// fg_group_phrase_clauses, fg_group_member_phrases, fg_field_clauses as the plan's creation read them
+// fg_group_phrase_clauses, fg_group_member_phrases, fg_field_clauses as the plan's creation read them;
+// fphrases: fg_field_phrases, with fields
 int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t n_segs, PlanTables& h,
               uint32_t nq_size, bool qtime, bool beside, bool groups, bool filters, bool gphrase, bool members,
-              bool fields) {
+              bool fields, bool fphrases) {
   if (!ix || !q || (q->n_queries && !q->q_off)) return fail(FG_EINVAL, "bad arguments");
   if (q->n_queries && q->q_off[q->n_queries] > q->q_off[0] && !q->terms) return fail(FG_EINVAL, "q_off without terms");
   if (q->f_off && q->n_queries && q->f_off[q->n_queries] > q->f_off[0] && !q->f_terms)
@@ -1144,7 +1307,7 @@ int plan_host(const fg_index* ix, const fg_query_batch* q, uint32_t k, uint32_t 
     if (q->phrase_len) {
       int phrase = 0;
       if (int rc = plan_phrase(ix, q, i, nq_size, n_segs, h, &phrase, beside, groups, filters, gphrase, members, fields,
-                               q_nomatch[i] != 0))
+                               fphrases, q_nomatch[i] != 0))
         return rc;
       if (phrase) continue;
     }
@@ -1367,7 +1530,8 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
   const bool gphrase = group_phrase_clauses_on.load(std::memory_order_relaxed) != 0;
   const bool members = group_member_phrases_on.load(std::memory_order_relaxed) != 0;
   const bool fields = field_clauses_on.load(std::memory_order_relaxed) != 0;
-  if (S == 1) return plan_host(ixs[0], q, k, S, hs[0], nq1, qt, beside, groups, filters, gphrase, members, fields);  // (used in place: nothing to join)
+  const bool fphrases = fields && field_phrases_on.load(std::memory_order_relaxed) != 0;  // (only on top of it)
+  if (S == 1) return plan_host(ixs[0], q, k, S, hs[0], nq1, qt, beside, groups, filters, gphrase, members, fields, fphrases);  // (used in place: nothing to join)
   J.clear();
   const size_t nq = (size_t)S * nq1, nqt = nq * fg::kMaxTerms;
   for (auto* v : {&J.q_m, &J.lead, &J.ngroup, &J.q_tier}) v->resize(nq);
@@ -1401,14 +1565,14 @@ int plan_pieces(fg_index* const* ixs, uint32_t S, const fg_query_batch* q, uint3
       qp.n_queries = b - a;
       qp.q_off = q->q_off + a;
       if (q->f_off) qp.f_off = q->f_off + a;
-      if ((rcs[p] = plan_host(ixs[p / pc.P], &qp, k, S, hs[p], nq1, qt, beside, groups, filters, gphrase, members, fields))) errs[p] = fg_last_error();
+      if ((rcs[p] = plan_host(ixs[p / pc.P], &qp, k, S, hs[p], nq1, qt, beside, groups, filters, gphrase, members, fields, fphrases))) errs[p] = fg_last_error();
       else put_slot(p);
     });
     for (uint32_t p = 0; p < n; ++p)
       if (rcs[p]) return fail(rcs[p], "snapshot %u: %s", p / pc.P, errs[p].c_str());
   } else {
     for (uint32_t s = 0; s < S; ++s) {
-      if (int rc = plan_host(ixs[s], q, k, S, hs[s], nq1, qt, beside, groups, filters, gphrase, members, fields)) {
+      if (int rc = plan_host(ixs[s], q, k, S, hs[s], nq1, qt, beside, groups, filters, gphrase, members, fields, fphrases)) {
         const std::string e = fg_last_error();
         return fail(rc, "snapshot %u: %s", s, e.c_str());
       }
@@ -1447,6 +1611,7 @@ PlanTables& join_pieces(const Pieces& pc, std::vector<PlanTables>& hs, PlanTable
     for (WItem x : h.gphrase) { x.q += vb; J.gphrase.push_back(x); }
     for (WItem x : h.mgroup) { x.q += vb; J.mgroup.push_back(x); }
     for (WItem x : h.field) { x.q += vb; J.field.push_back(x); }
+    for (WItem x : h.fphrase) { x.q += vb; J.fphrase.push_back(x); }
     J.nf += h.nf;
   }
   // one bin geometry per batch query over the snapshots where it has work
@@ -1562,9 +1727,9 @@ void sort_sweep(std::vector<WItem>& items, bool conj, const PlanTables& t, uint3
 struct WorkList {
   std::vector<uint32_t> work_q, work_c, work_n;
   std::vector<uint64_t> cand_off;
-  uint64_t n_single = 0, n_conj = 0, n_main = 0, n_scan = 0, n_phrase = 0, n_bphrase = 0, n_group = 0, n_gphrase = 0, n_mgroup = 0, n_field = 0;
+  uint64_t n_single = 0, n_conj = 0, n_main = 0, n_scan = 0, n_phrase = 0, n_bphrase = 0, n_group = 0, n_gphrase = 0, n_mgroup = 0, n_field = 0, n_fphrase = 0;
   uint32_t xcd_first[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // DevPlan::xcd_first
-  uint64_t count() const { return n_main + n_scan + n_phrase + n_bphrase + n_group + n_gphrase + n_mgroup + n_field; }
+  uint64_t count() const { return n_main + n_scan + n_phrase + n_bphrase + n_group + n_gphrase + n_mgroup + n_field + n_fphrase; }
 };
 
 // k_conj's multi-list items (sorted) cut into the 8 XCDs' stretches by expected
@@ -1599,13 +1764,13 @@ void xcd_stretches(const PlanTables& t, WorkList& w) {
 int order_items(PlanTables& t, uint32_t nq, uint32_t k, WorkList& w) {
   if (t.f_woff[t.nf] * 4 > (8ull << 30)) return fail(FG_EUNSUPPORTED, "facet masks of this batch exceed 8 GiB");
   if (t.ch_f.size() > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "facet postings of this batch too large");
-  if (t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size() + t.mgroup.size() + t.field.size() > 0x7FFFFFFFull)
+  if (t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size() + t.mgroup.size() + t.field.size() + t.fphrase.size() > 0x7FFFFFFFull)
     return fail(FG_EUNSUPPORTED, "batch too large (%zu work items)",
-                t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size() + t.mgroup.size() + t.field.size());
+                t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size() + t.mgroup.size() + t.field.size() + t.fphrase.size());
   sort_sweep(t.citems, true, t, nq);
   sort_sweep(t.ditems, false, t, nq);
   auto& items = t.items;
-  items.reserve(t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size() + t.mgroup.size() + t.field.size());
+  items.reserve(t.citems.size() + t.ditems.size() + t.scan.size() + t.phrase.size() + t.bphrase.size() + t.group.size() + t.gphrase.size() + t.mgroup.size() + t.field.size() + t.fphrase.size());
   items.insert(items.end(), t.citems.begin(), t.citems.end());
   w.n_conj = t.citems.size();
   items.insert(items.end(), t.ditems.begin(), t.ditems.end());
@@ -1633,7 +1798,10 @@ int order_items(PlanTables& t, uint32_t nq, uint32_t k, WorkList& w) {
   // k_field: the same sweep
   std::stable_sort(t.field.begin(), t.field.end(), [](const WItem& a, const WItem& b) { return a.key < b.key; });
   w.n_field = t.field.size();
-  const uint64_t chunks = w.count();  // work items (k_conj / k_disj, then k_scan, k_phrase, k_bphrase, k_group, k_gphrase, k_mgroup, k_field)
+  // k_fphrase: the same sweep
+  std::stable_sort(t.fphrase.begin(), t.fphrase.end(), [](const WItem& a, const WItem& b) { return a.key < b.key; });
+  w.n_fphrase = t.fphrase.size();
+  const uint64_t chunks = w.count();  // work items (k_conj / k_disj, then k_scan, k_phrase, k_bphrase, k_group, k_gphrase, k_mgroup, k_field, k_fphrase)
   if (chunks > 0x7FFFFFFFull) return fail(FG_EUNSUPPORTED, "batch too large (%llu work items)", (unsigned long long)chunks);
   items.insert(items.end(), t.scan.begin(), t.scan.end());
   items.insert(items.end(), t.phrase.begin(), t.phrase.end());
@@ -1642,6 +1810,7 @@ int order_items(PlanTables& t, uint32_t nq, uint32_t k, WorkList& w) {
   items.insert(items.end(), t.gphrase.begin(), t.gphrase.end());
   items.insert(items.end(), t.mgroup.begin(), t.mgroup.end());
   items.insert(items.end(), t.field.begin(), t.field.end());
+  items.insert(items.end(), t.fphrase.begin(), t.fphrase.end());
   w.work_q.resize(chunks);
   w.work_c.resize(chunks);
   w.work_n.resize(chunks);
@@ -1841,6 +2010,7 @@ void fill_view(fg_plan* p, fg_index* const* ixs, PlanTables& t, const WorkList& 
   p->d.n_gphrase = (uint32_t)w.n_gphrase;
   p->d.n_mgroup = (uint32_t)w.n_mgroup;
   p->d.n_field = (uint32_t)w.n_field;
+  p->d.n_fphrase = (uint32_t)w.n_fphrase;
   p->d.n_single = (uint32_t)w.n_single;
   std::copy(w.xcd_first, w.xcd_first + 9, p->d.xcd_first);
   p->d.k = p->k;
@@ -1955,6 +2125,11 @@ int fg_group_member_phrases(int on) {
 int fg_field_clauses(int on) {
   if (on < 0) return field_clauses_on.load(std::memory_order_relaxed);
   return field_clauses_on.exchange(on != 0 ? 1 : 0, std::memory_order_relaxed);
+}
+
+int fg_field_phrases(int on) {
+  if (on < 0) return field_phrases_on.load(std::memory_order_relaxed);
+  return field_phrases_on.exchange(on != 0 ? 1 : 0, std::memory_order_relaxed);
 }
 
 int fg_plan_tiered_slots(const fg_plan* p, uint32_t* out) {

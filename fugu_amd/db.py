@@ -236,7 +236,7 @@ def parse_query_clause_lines(query: str):
 def parse_query_groups(query: str):
     """[(occur, kind, [term, ...])] with kind "term", "phrase", "any" or "all": the query's
     clauses with group clauses (native.group_clauses) told apart; a field-qualified term
-    (native.field_clauses) has kind "text" or "name".  A phrase member of a group
+    (native.field_clauses) or phrase (native.field_phrases: several tokens) has kind "text" or "name".  A phrase member of a group
     (native.group_member_phrases) is a list of its tokens inside the group's list."""
     out = []
     for line in parse_query_clause_lines(query):
@@ -245,8 +245,8 @@ def parse_query_groups(query: str):
             kind = "any" if " | " in body else "all"
             mem = body[1:-1].split(" | " if kind == "any" else " & ")
             out.append((oc, kind, [[x.rsplit("@", 1)[0] for x in m.split(" ")] if " " in m else m for m in mem]))
-        elif body.startswith(("text:", "name:")):  # a field-qualified term (native.field_clauses)
-            out.append((oc, body[:4], [body[5:].rsplit("@", 1)[0]]))
+        elif body.startswith(("text:", "name:")):  # a field-qualified term (native.field_clauses), or phrase
+            out.append((oc, body[:4], [x.rsplit("@", 1)[0] for x in body[5:].split(" ")]))  # (native.field_phrases)
         else:
             toks = [x.rsplit("@", 1)[0] for x in body.split(" ")]
             out.append((oc, "term" if len(toks) == 1 else "phrase", toks))
@@ -255,12 +255,15 @@ def parse_query_groups(query: str):
 
 def parse_query_fields(query: str):
     """[(occur, term, field)] of a query of term clauses, field None (both fields), "text" or "name"
-    (native.field_clauses: `name:report`); Unsupported when a clause is a phrase or a group."""
+    (native.field_clauses: `name:report`); Unsupported when a clause is a phrase or a group.  With
+    native.field_phrases on top, a phrase clause (`name:"annual report"`, `e-mail`) is reported too, the
+    list of its tokens in the term's place."""
     out = []
+    phrases = native.field_clauses() > 0 and native.field_phrases() > 0
     for oc, kind, toks in parse_query_groups(query):
-        if kind not in ("term", "text", "name"):
+        if kind not in ("term", "text", "name") and not (phrases and kind == "phrase"):
             raise native.Unsupported(native.FG_EUNSUPPORTED, f"a {kind} clause")
-        out.append((oc, toks[0], None if kind == "term" else kind))
+        out.append((oc, toks[0] if len(toks) == 1 else list(toks), None if kind in ("term", "phrase") else kind))
     return out
 
 

@@ -42,7 +42,7 @@ OCCUR_SHOULD = 1
 OCCUR_MUST_NOT = 2
 CLAUSE_ANY = 0x80000000  # fugu.h FG_CLAUSE_ANY / FG_CLAUSE_ALL: phrase_len flags of a group clause
 CLAUSE_ALL = 0x40000000
-CLAUSE_TEXT = 0x20000000  # fugu.h FG_CLAUSE_TEXT / FG_CLAUSE_NAME: phrase_len flags of a field-qualified term clause
+CLAUSE_TEXT = 0x20000000  # fugu.h FG_CLAUSE_TEXT / FG_CLAUSE_NAME: phrase_len flags of a field-qualified term (or, field_phrases, phrase) clause
 CLAUSE_NAME = 0x10000000
 FIELD_TEXT = 0
 FIELD_NAME = 1
@@ -68,7 +68,7 @@ EXPORTS = (
     "fg_index_build_positional", "fg_index_positions_get",
     "fg_index_bands_get", "fg_index_band_read", "fg_plan_tiered_slots",
     "fg_phrase_clauses", "fg_group_clauses", "fg_filter_clauses", "fg_count_clauses", "fg_count_clause_trace",
-    "fg_group_phrase_clauses", "fg_group_member_phrases", "fg_field_clauses",
+    "fg_group_phrase_clauses", "fg_group_member_phrases", "fg_field_clauses", "fg_field_phrases",
 )
 BAND_TIERS = 5  # fugu.h FG_BAND_TIERS
 LADDER_KS = (1, 2, 3, 5, 10, 13, 20, 25, 50, 100, 125, 250, 500, 1000)  # FG_LADDER_LEVELS ranks
@@ -201,6 +201,8 @@ if hasattr(_lib, "fg_group_member_phrases"):  # (likewise)
     _sig("fg_group_member_phrases", C.c_int, C.c_int)
 if hasattr(_lib, "fg_field_clauses"):  # (likewise)
     _sig("fg_field_clauses", C.c_int, C.c_int)
+if hasattr(_lib, "fg_field_phrases"):  # (likewise)
+    _sig("fg_field_phrases", C.c_int, C.c_int)
 if hasattr(_lib, "fg_count_clauses"):  # (likewise)
     _sig("fg_count_clauses", C.c_int, C.c_int)
     _sig("fg_count_clause_trace", C.c_int, C.c_int, _f64p, _u32p)
@@ -331,6 +333,18 @@ def field_clauses(on: int = -1) -> int:
     if not hasattr(_lib, "fg_field_clauses"):
         raise Unsupported(FG_EUNSUPPORTED, "this libfugu has no fg_field_clauses")
     return int(_lib.fg_field_clauses(int(on)))
+
+
+def field_phrases(on: int = -1) -> int:
+    """fg_field_phrases: on top of field_clauses(1), CLAUSE_TEXT / CLAUSE_NAME may stand on a phrase
+    clause's first phrase_len entry (flag | n, n >= 2: `name:"annual report"`, one field's
+    PhraseQuery) and a field term clause beside a phrase clause; such queries run on the device
+    (k_fphrase).  Alone it changes nothing; no other switch is consulted.  Process-wide, off by
+    default, read when a plan is created.  on: 1 / 0 sets it, < 0 only asks; returns the previous
+    setting."""
+    if not hasattr(_lib, "fg_field_phrases"):
+        raise Unsupported(FG_EUNSUPPORTED, "this libfugu has no fg_field_phrases")
+    return int(_lib.fg_field_phrases(int(on)))
 
 
 def count_clauses(on: "int | None" = None) -> int:

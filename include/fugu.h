@@ -527,7 +527,8 @@ int fg_group_member_phrases(int on);
  * without a field clause plans exactly as before.
  * FG_EINVAL "bad phrase_len at term N": both flags on one entry.
  * FG_EUNSUPPORTED, whatever the other switches say: a field flag on an entry
- * whose count is not 1 ("field-qualified phrase"), together with FG_CLAUSE_ANY /
+ * whose count is not 1 ("field-qualified phrase"; lifted, like "field clause beside a
+ * phrase clause", by fg_field_phrases below), together with FG_CLAUSE_ANY /
  * FG_CLAUSE_ALL or on a group's member row ("field-qualified group"), "field
  * clause beside a phrase clause", "field clause beside a group clause", "field
  * clause with facet filters", a field clause in fg_model_batch, and one in
@@ -535,6 +536,45 @@ int fg_group_member_phrases(int on);
 #define FG_CLAUSE_TEXT 0x20000000u
 #define FG_CLAUSE_NAME 0x10000000u
 int fg_field_clauses(int on);
+
+/* Field-qualified phrase clauses -- `name:"annual report"`, `name:e-mail`,
+ * `+name:"q3 report" +budget` -- and a field term clause beside a phrase clause
+ * (`name:report e-mail`) run on the device (k_fphrase) when on != 0
+ * AND fg_field_clauses is on; alone it changes nothing.  The contract of
+ * fg_field_clauses: process-wide, off by default, read when a plan is created;
+ * on: 1 / 0 sets it, < 0 only asks; returns the previous setting.  No other
+ * switch is consulted.  Off: every entry point answers as before ("field-qualified
+ * phrase", "field clause beside a phrase clause").
+ * FG_CLAUSE_TEXT or FG_CLAUSE_NAME may then stand on a phrase clause's first
+ * phrase_len entry: flag | n, n >= 2, the n - 1 entries after it 0, phrase_pos as
+ * an unqualified phrase's.  The clause is that field's PhraseQuery at slop 0:
+ * present in a doc iff the phrase occurs in THAT field's token stream (a doc that
+ * holds it in the other field only does not match), scored by the field's part
+ * alone, weight_f * (c / (c + cache_f[fieldnorm_f])) with c the count there and
+ * weight_f = (the terms' idfs in that field summed in phrase order from 0.0, a
+ * repeated term each time) * (1 + K1): the bits of the unqualified phrase's part
+ * for that field, and of the whole unqualified clause on a doc that holds the
+ * phrase in that field only.  Among the Musts the order is (cost, position); a
+ * field phrase costs the smallest doc count in that field among its terms, inside
+ * the snapshot (the unqualified phrase's rule with the other field's summand
+ * dropped; a field term and an unqualified clause keep theirs).  The clauses join
+ * as the clauses of `occur` do.  A snapshot that lacks one of the terms in that
+ * field -- or, for FG_CLAUSE_NAME, has no name postings or no name forward index
+ * -- lacks the clause: a Must empties the query there, a Should or MustNot drops
+ * out.  (The cost rule is stated as upstream knowledge; it is not pinned against
+ * tantivy.)
+ * The device subset: the query holds a field-qualified phrase clause, or a field
+ * term clause beside a phrase clause; every other clause is a plain term, a field
+ * term or a plain phrase, any occur, within FG_MAX_TERMS, on snapshots built with
+ * positions ("snapshot built without positions" otherwise).  A query whose field
+ * clauses are all single terms, with no phrase, plans as fg_field_clauses plans it.
+ * FG_EINVAL "bad phrase_len at term N": both flags on one entry, a count of 0 or
+ * past the query's end.  FG_EUNSUPPORTED stay: a flag together with FG_CLAUSE_ANY /
+ * FG_CLAUSE_ALL or on a group's member row ("field-qualified group"), a group
+ * clause anywhere in such a query ("field clause beside a group clause",
+ * "field-qualified phrase beside a group clause"), "field clause with facet
+ * filters", fg_model_batch and fg_count_batch ("field clause in a count query"). */
+int fg_field_phrases(int on);
 
 /* Plan a batch: host-side query planning (tantivy Weight creation: terms
  * ordered by cost, query/intersection.rs) and upload of the plan to HBM.

@@ -57,7 +57,11 @@
  * process-wide, off by default: k_field), with which `text:WORD` / `name:WORD`, WORD a
  * plain word of one token, is that field's TermQuery; fg_parse_query_clauses prints it
  * "<occur>:name:report@0", fg_parse_query and fg_parse_query_occur refuse it, and so do
- * the count entry points --,
+ * the count entry points; with fg_field_phrases(1) on top of it (fugu.h; process-wide,
+ * off by default: k_fphrase) WORD may analyze to several tokens or be a plain quoted
+ * literal, that field's PhraseQuery (`name:"annual report"`, `name:e-mail`, printed
+ * "<occur>:name:annual@0 report@1"; a quoted literal of one token is a field term), and
+ * a field term may stand beside a phrase clause --,
  * boosts, a text query with filters that parse to no facet term) return
  * FG_EUNSUPPORTED: the reference host then runs tantivy; this library never
  * answers them on the CPU.  Empty queries (AllQuery), facet-only queries and

@@ -263,6 +263,7 @@ extern "C" {
     pub fn fg_group_phrase_clauses(on: c_int) -> c_int;
     pub fn fg_group_member_phrases(on: c_int) -> c_int;
     pub fn fg_field_clauses(on: c_int) -> c_int;
+    pub fn fg_field_phrases(on: c_int) -> c_int;
     pub fn fg_plan_create(ix: *mut fg_index, q: *const fg_query_batch, k: u32, out: *mut *mut fg_plan) -> c_int;
     pub fn fg_plan_create_multi(ixs: *const *mut fg_index, n_segs: u32, q: *const fg_query_batch, k: u32,
                                 out: *mut *mut fg_plan) -> c_int;
